@@ -2,6 +2,7 @@
 """Headline benchmark of the render hot path: rendered rays/s.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--precision fp32] [--config 2|3|4|5] [--scaling strong|weak]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,15 +15,22 @@ samples -> compositing -> inverse-CDF resampling -> fine MLP @128 samples -> com
 The workload is the SAME at every N: BASELINE config #2, the one the metric is quoted on (504x378 <- 252x189, 2x
 supersampling, NDC, 190,512 rays), cut into N contiguous LR-pixel blocks; every rank generates and renders its own block
 and ONE all-gather of the rendered LR pixels closes the step -- strong scaling, one metric string for the whole 1/2/4/8
-curve.  BASELINE config #4 (ONE 1008x756 <- 252x189 frame, 4x supersampling, 762,048 rays: the frame BASELINE shards
-over 8 GPUs) is cut and timed the same way right after, in the same process, and reported as the ``config4``
-sub-object.  ``--scaling weak`` renders one whole frame per rank instead; ``--config`` picks one frame geometry
+curve.  ``--scaling weak`` renders one whole frame per rank instead; ``--config`` picks one frame geometry
 explicitly.  Weights are synthetic (nerf_sr_amd.weights, "smooth" field), inputs are generated on the device: nothing
 crosses PCIe inside the timed region.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects: ``roofline`` (fine-MLP
-launch, algorithmic FLOPs / HIP-event duration vs the dense MFMA peak of the dtype) and ``cpu_baseline`` (the
-torch-CPU oracle port timed on this host, N = 1 only).
+Rank 0 prints ONE JSON line (contract in the task statement) with an extra ``roofline`` object (fine-MLP launch,
+algorithmic FLOPs / HIP-event duration vs the dense MFMA peak of the dtype).  A plain run does only what that line needs:
+set-up, warm-up, the timed steps, the line.  ``--full`` adds everything else the benchmark measures, after the headline
+steps in the same process: BASELINE config #4 (ONE 1008x756 <- 252x189 frame, 4x supersampling, 762,048 rays: the frame
+BASELINE shards over 8 GPUs) cut and timed the same way as the ``config4`` sub-object; on one GPU the ``config5`` (+
+``refine``), ``train`` (+ ``fast_path``), ``config1`` and ``arch`` sub-objects; and ``cpu_baseline`` (the torch-CPU
+oracle port timed on this host) with the ``parity`` block against it, N = 1 only.  ``--no-config4`` / ``--no-extras`` /
+``--no-cpu-baseline`` drop parts of it again.
+
+``--dump-outputs DIR`` writes what the timed path computed in its LAST timed step as ``DIR/<name>.npy`` (float32; see
+``dump_outputs``), so that two builds can be compared output for output: weights and inputs are seeded, so the same
+arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -211,7 +219,7 @@ def train_cpu_baseline(sd_c, sd_f, rays_cpu, target_cpu, s2: int, draws):
 CHAIN_PRECISIONS = ("f16x3", "f16x3_bwd3", "f16x3_bwd2", "f16x3_bwd1", "f16x3_bwdm")   # the chain kernels (include/nsr_train.h)
 
 
-def train_bench(args, rank, local, world, steps=None, warmup=None, cpu=True, shape="downx"):
+def train_bench(args, rank, local, world, steps=None, warmup=None, cpu=True, shape="downx", dump=""):
     """Training-step benchmark (not the headline).  shape "downx": scripts/train_llff_downX.sh's batch -- 512 LR pixels x 4
     sub-rays = 2,048 rays per GPU per step, 64 + 128 samples, randomized sampling, noise_std 1 -- through
     Trainer.optimize_parameters (forward, s^2-mean MSE losses, backward, one gradient all-reduce for N > 1, Adam).
@@ -253,6 +261,10 @@ def train_bench(args, rank, local, world, steps=None, warmup=None, cpu=True, sha
         t.optimize_parameters()
     fence()
     dt = time.perf_counter() - t0
+    if dump and rank == 0:
+        # what the last step left a caller: its losses and outputs, and both networks' weights after its Adam update
+        dump_outputs(dump, {"losses": t.losses, **t.out,
+                            **{f"{n}_params": torch.cat([v.reshape(-1) for v in p.values()]) for n, p in zip(("coarse", "fine"), t.params)}})
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -370,7 +382,7 @@ def main_train(args):
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (the product has no CPU path)")
     torch.cuda.set_device(local)
-    res = train_bench(args, rank, local, world)
+    res = train_bench(args, rank, local, world, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:
@@ -491,6 +503,25 @@ def refine_pmc_busy():
     return (sum(v["ms_under_pmc"] * v["mfma_busy"] for v in ks) / t if ok and t > 0 else None), src
 
 
+DUMP_BYTES = 64_000_000         # --dump-outputs: all arrays of one run together
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """``--dump-outputs``: one ``<name>.npy`` (float32) per array of what the last timed step returned.  Every array gets an
+    equal share of DUMP_BYTES; one within its share is written whole, a larger one (the per-sample ``*_weights`` arrays,
+    per-ray arrays of the 4x frames) is cut to its rows at a fixed seeded sample of row indices, sorted: the same rows in
+    every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        keep = DUMP_BYTES // len(arrays) // max(4, t[0].numel() * 4 if t.dim() else 4)
+        if t.dim() and t.shape[0] > keep:
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -499,6 +530,13 @@ def main():
     ap.add_argument("--precision", default=os.environ.get("NSR_PRECISION", "f16x3"), choices=list(PEAK_TFLOPS),
                     help="MLP arithmetic: f16x3 (default; split-fp16 MFMA, fp32-grade: passes the 1e-4 RGB contract) "
                          "or fp32 (fp32 MFMA); f16 / bf16 = single 16-bit operands, fast but outside the parity contract")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also time and check everything else the benchmark measures: config #4 "
+                         "(`config4`), config #5 + its refinement pass, the training steps and the non-default architecture "
+                         "(`config5`, `train`, `config1`, `arch`; one GPU), the CPU baseline and the parity block against the "
+                         "oracle (`cpu_baseline`, `parity`; one GPU); off: the line carries the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--mode", default="render", choices=["render", "train"],
                     help="render (default): the headline metric; train: one optimize_parameters iteration per step "
@@ -512,21 +550,23 @@ def main():
                          "network-then-compositor route, sample counts other than 64 / 128 are not composited in the MLP launch)")
     ap.add_argument("--config", type=int, default=0, choices=[0] + sorted(RENDER_CONFIGS),
                     help="BASELINE.json render configuration; default: #2 (the one the metric is quoted on) at every N, with "
-                         "#4 (the 1008x756 frame BASELINE shards over 8 GPUs) timed after it as the `config4` sub-object")
+                         "#4 (the 1008x756 frame BASELINE shards over 8 GPUs) timed after it as the `config4` sub-object under --full")
     ap.add_argument("--scaling", default="", choices=["", "strong", "weak"],
                     help="strong (default, every N): ONE frame cut into N contiguous LR-pixel blocks + one all-gather; "
                          "weak (N > 1) = one whole frame per rank (an N-frame batch)")
     ap.add_argument("--no-config4", action="store_true",
-                    help="skip the `config4` sub-object (config #4's frame sharded over the same ranks, timed after the headline)")
+                    help="--full: skip the `config4` sub-object (config #4's frame sharded over the same ranks, timed after the headline)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the `train` and `config5` (+ `refine`) sub-objects of the default N = 1 line")
+                    help="--full: skip the `train`, `config1`, `config5` (+ `refine`) and `arch` sub-objects of the N = 1 line")
     ap.add_argument("--arch", default="6,192,1+3",
                     help="D,W,skips (skips joined by +): a NON-default network architecture timed on the layer-by-layer route "
-                         "(ops.GenericMLP) as the `arch` sub-object of the default N = 1 line; '' skips it")
+                         "(ops.GenericMLP) as the `arch` sub-object of the --full N = 1 line; '' skips it")
     ap.add_argument("--with-refine", action="store_true",
                     help="config #5 only: after the timed render steps run depth -> warp -> refinement network on the "
                          "rendered frame and report that pass separately (`refine` object; not part of `value`)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_config4 = args.no_extras = True
     global N_IMPORTANCE, FLOP_PER_RAY
     if args.n_importance != N_IMPORTANCE:
         if args.n_importance < 1 or N_COARSE + args.n_importance > 256:
@@ -634,7 +674,7 @@ def main():
                 "n_lr": n_lr, "my_rays": my_rays, "rays_per_step": rays_per_step, "dt": dt, "steps": steps, "warmup": warmup,
                 "value": rays_per_step * steps / dt, "ms_per_step": dt / steps * 1e3,
                 "fine_ms": sum(fine_ms) / len(fine_ms), "coarse_ms": sum(coarse_ms) / len(coarse_ms),
-                "rays": rays, "o": o, "c2w": c2w, "focal": focal,
+                "rays": rays, "o": o, "frame": frame, "c2w": c2w, "focal": focal,
                 "bytes_per_rank": (cap[1] - cap[0]) * width * 4 if world > 1 else 0, "gathered_ok": gathered_ok}
 
     def workload(r) -> str:
@@ -650,10 +690,13 @@ def main():
                 f"{N_COARSE} coarse + {N_COARSE + N_IMPORTANCE} fine samples/ray, {r['rays_per_frame']:,} rays per frame" + how)
 
     # The headline workload is the SAME at every N: config #2's frame (the one BASELINE's metric is quoted on), cut into N
-    # LR-pixel blocks.  Config #4 (the frame BASELINE shards over 8 GPUs) is timed the same way in the same process and
-    # reported as the `config4` sub-object.
+    # LR-pixel blocks.  Under --full, config #4 (the frame BASELINE shards over 8 GPUs) is timed the same way in the same
+    # process and reported as the `config4` sub-object.
     cfg_id = args.config or 2
     main_r = time_config(cfg_id, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        # the s^2 means of the frame (every rank's block after the all-gather for N > 1) and this rank's per-ray outputs
+        dump_outputs(args.dump_outputs, {"lr_rgb": main_r["frame"], **main_r["o"]})
     c4 = None
     # The sub-objects must never cost the headline line: a failure in one of them is recorded as {"error": ...}.
     extras_err = {}
@@ -668,8 +711,8 @@ def main():
         # config #4's collective carries what the reference's test loop delivers: the HR frame (12 B per ray)
         c4 = guarded("config4", lambda: time_config(4, min(args.steps, 3), 1, gather="hr")) if world == 1 else \
             time_config(4, min(args.steps, 3), 1, gather="hr")     # (N > 1: every rank must take the same collectives)
-    # the other measured paths of SURVEY 8f ride in the default one-GPU line as sub-objects (VERDICT r3 "next" #2), so that the
-    # driver's run records them: BASELINE config #5's render pass + its refinement tail, the training step, and BASELINE
+    # the other measured paths of SURVEY 8f ride in the --full one-GPU line as sub-objects (VERDICT r3 "next" #2), so that one
+    # run records them: BASELINE config #5's render pass + its refinement tail, the training step, and BASELINE
     # config #1 (the vanilla model's training iteration)
     c5 = train_res = c1_res = None
     if not args.config and not args.no_extras and world == 1:

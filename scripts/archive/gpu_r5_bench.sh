@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/r5_bench
 mkdir -p $O
 cd $R
-( time timeout 900 python bench.py --steps 5 --warmup 2 > $O/bench.json 2> $O/bench.err ) 2>&1 | grep real
+( time timeout 900 python bench.py --full --steps 5 --warmup 2 > $O/bench.json 2> $O/bench.err ) 2>&1 | grep real
 python - <<PY
 import json
 d = json.loads(open("$O/bench.json").read().strip().splitlines()[-1])

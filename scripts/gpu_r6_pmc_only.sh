@@ -18,4 +18,4 @@ json.dump(rec, open("$O/r6_train_traffic.json", "w"), indent=1)
 print("train hbm bytes per step", rec["hbm_bytes_per_step"])
 PY
 timeout 600 python scripts/pmc_refine.py $O/r6_refine_pmc.json > $O/refine_pmc.log 2>&1; tail -1 $O/refine_pmc.log | cut -c1-120
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-200
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; tail -1 $O/bench.json | cut -c1-200

@@ -354,8 +354,8 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     torch.distributed.run on a free port -- round 5), on THIS box: both ranks share the one GPU and exchange over gloo
     (NSR_DIST_BACKEND; RCCL refuses two ranks per device).  Checks the N > 1 code path end to end: the SAME workload and
     metric string as N = 1 (config #2's frame cut in two LR-pixel blocks), config #4 cut the same way as the `config4`
-    sub-object with the HR frame as its collective's payload (12 B per ray), one all-gather per step whose result is verified
-    identical on both ranks, max-over-ranks timing, one JSON line from rank 0 with the contract's fields."""
+    sub-object of `--full` with the HR frame as its collective's payload (12 B per ray), one all-gather per step whose result
+    is verified identical on both ranks, max-over-ranks timing, one JSON line from rank 0 with the contract's fields."""
     import json
     import os
     import subprocess
@@ -363,7 +363,7 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(NSR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"]
     res = subprocess.run(cmd, env=env, cwd=repo, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
