@@ -116,7 +116,7 @@ def build(force: bool = False, verbose: bool = True, variant: str = "", defines=
 #    SGPRs with v_readlane, a VMEM read of a VALU-written SGPR needs five wait states, and the hazard pass cannot see through
 #    inline asm: every global_load_lds / global_store inside an asm block must read a pair written by an s_mov_b64 inside the
 #    SAME block.
-ISA_UNITS = ["nsr_mlp_f16.hip", "nsr_train_chain.hip", "nsr_gemm_f16.hip", "nsr_wgrad_f16.hip"]
+ISA_UNITS = ["nsr_mlp_f16.hip", "nsr_train_chain.hip", "nsr_gemm_f16.hip", "nsr_wgrad_f16.hip", "nsr_mlp.hip", "nsr_mlp_h1.hip"]
 ISA_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-S",
              "--cuda-device-only"]
 
@@ -160,34 +160,17 @@ def compile_listing(unit: str, defines=(), out_dir=None) -> str:
 # defines, the translation units they touch, what they are for.  tests/test_variants.py compiles every one of them on the CPU
 # box (and runs the ISA contract on the listing), so a variant cannot rot silently.
 VARIANTS = {
-    "persistent": (["-DNSR_PERSISTENT"], ["nsr_mlp_f16.hip"],
-                   "ray kernels loop over tiles, one workgroup per CU, weight ring streaming across tiles (DESIGN 3.1 round 4: complete, bit-identical, not faster)"),
-    "enc_overlap": (["-DNSR_PERSISTENT", "-DNSR_ENC_OVERLAP"], ["nsr_mlp_f16.hip"],
-                    "persistent + the next tile's encoding in the matrix shadow (150 pinned pieces)"),
     "timeline": (["-DNSR_ABL_TIMELINE"], ["nsr_mlp_f16.hip", "nsr_train_chain.hip"],
                  "s_memtime stamps at the phase boundaries of every tile (scripts/timeline.py)"),
     "abl_chain": (["-DNSR_ABL_NO_AMAX", "-DNSR_ABL_NO_DENSITY_MMA", "-DNSR_ABL_FWD_NO_STORE", "-DNSR_ABL_BWD_NO_STORE", "-DNSR_ABL_BWD_STORE_L2"],
                   ["nsr_mlp_f16.hip", "nsr_train_chain.hip"],
                   "what the range tracking / the density block's MFMAs / the training panel stores cost (profiles/r5_headline_experiments.json)"),
-    "halo_no_multi": (["-DNSR_HALO_NO_MULTI"], ["nsr_gemm_f16.hip"],
-                      "refinement pass with the 8 x 8-pixel plain layers on the staged tiles (round 6 A/B; other K order: not bit-identical)"),
-    "store_policy": (["-DNSR_PANEL_STORE_POLICY=\"\"", "-DNSR_ABL_BWD_DEFAULT_STORE"], ["nsr_mlp_f16.hip", "nsr_train_chain.hip"],
-                     "training panel stores with the default cache policy instead of non-temporal (A/B)"),
     "abl_ring": (["-DNSR_ABL_NO_DMA", "-DNSR_ABL_NO_BARRIER", "-DNSR_ABL_NO_DRAIN", "-DNSR_ABL_NO_CONVERT"], ["nsr_mlp_f16.hip"],
                  "round 1's measurement ladder of the weight ring (profiles/r1_f16x3_pmc.txt)"),
-    "abl_fenced_barrier": (["-DNSR_ABL_FENCED_BARRIER", "-DNSR_ABL_NO_TILE_LAUNDER"], ["nsr_mlp_f16.hip"],
+    "abl_fenced_barrier": (["-DNSR_ABL_FENCED_BARRIER"], ["nsr_mlp_f16.hip"],
                            "round 4's publish-point A/B (__syncthreads instead of s_barrier)"),
-    "dev_switches": (["-DNSR_DEV_SWITCHES"], ["nsr_gemm_f16.hip", "nsr_refine.hip"],
-                     "environment-read A/B switches of the refinement GEMMs (NSR_GEMM_TILE / _TK / _FULLN, NSR_REFINE_SEPARATE_MAX)"),
     "abl_halo": (["-DNSR_ABL_HALO_NO_PATCH", "-DNSR_ABL_HALO_NO_BDMA", "-DNSR_ABL_HALO_NO_BARRIER", "-DNSR_ABL_HALO_NO_EPILOGUE"],
                  ["nsr_gemm_f16.hip"], "ablations of conv_halo_kernel (profiles/r4_refine_halo.txt)"),
-    "halo_pairs": (["-DNSR_HALO_PAIR=0", "-DNSR_HALO_PAIR_WIDE=1", "-DNSR_HALO_GROUPED_QUARTER", "-DNSR_HALO_NO_LAST"], ["nsr_gemm_f16.hip"],
-                   "round 6's A/B partners of conv_halo_kernel: one workgroup per CU for the half shape; the 256-column plain layers on "
-                   "paired half tiles (measured: nothing); the grouped 128-column layer as pairs of 128 x 128 workgroups (measured: nothing)"),
-    "bwd_waves4": (["-DNSR_BWD_WAVES=4"], ["nsr_train_chain.hip"],
-                   "reduced-term backward chains on 4-wave workgroups (one wave per SIMD for two terms; round 6: 425 vs 371 us per pass)"),
-    "gemm_alt": (["-DNSR_GEMM_NO_HALO", "-DNSR_GEMM_NO_XCD", "-DNSR_GEMM_NO_WROWS", "-DNSR_GEMM_K32_ONLY=1", "-DNSR_HALO_S2_MIN_CIN=256",
-                  "-DNSR_ABL_RELU_FMAX"], ["nsr_gemm_f16.hip"], "staged-kernel-only build and the other GEMM A/B partners"),
 }
 
 

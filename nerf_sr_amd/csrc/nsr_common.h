@@ -15,15 +15,9 @@
 
 static inline hipStream_t nsr_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
-// Development switches (A/B runs on one box: NSR_GEMM_TILE / NSR_GEMM_TK / NSR_GEMM_FULLN / NSR_REFINE_SEPARATE_MAX) are
-// environment reads, and getenv is not safe against a concurrent setenv: the release library does not contain them
-// (include/nsr.h promises no ambient process state; tests/test_abi.py checks that `getenv` is not even imported); build
-// with -DNSR_DEV_SWITCHES to get them back.  The training step's path is an argument (NSR_F16X3_GEMM, include/nsr_train.h).
-#ifdef NSR_DEV_SWITCHES
-static inline const char* nsr_dev_env(const char* name) { return getenv(name); }
-#else
-static inline const char* nsr_dev_env(const char*) { return nullptr; }
-#endif
+// No environment reads: getenv is not safe against a concurrent setenv, and include/nsr.h promises no ambient process state
+// (tests/test_abi.py checks that `getenv` is not even imported).  The training step's path is an argument (NSR_F16X3_GEMM,
+// include/nsr_train.h).
 
 // ---- tail of every packed weight blob (include/nsr.h "numerics status word"): 16 bytes behind the 16-byte-aligned
 // payload of the precision's own layout: word 0 = sticky NSR_FLAG_* status, word 1 = colour-head options
@@ -56,11 +50,7 @@ __device__ __forceinline__ float nsr_colour_activation(float s, unsigned opts) {
 __device__ __forceinline__ float nsr_max_nan(float a, float b) { return (a != a) ? a : ((b != b) ? b : fmaxf(a, b)); }
 // torch.relu keeps NaN (networks.py: nn.ReLU after every BatchNorm); fmaxf(NaN, 0) = 0 would hide a diverged feature
 // (x <= 0: -0.0 becomes +0.0, so the result is +0, positive, +inf or NaN -- see nsr_max_relu)
-#ifdef NSR_ABL_RELU_FMAX   // ablation: what keeping NaN costs (profiles/r4_refine_halo.txt)
-__device__ __forceinline__ float nsr_relu_nan(float x) { return fmaxf(x, 0.0f); }
-#else
 __device__ __forceinline__ float nsr_relu_nan(float x) { return (x <= 0.0f) ? 0.0f : x; }
-#endif
 // NaN-propagating maximum of two nsr_relu_nan results in one instruction: on +0 / positive / +inf the unsigned order of the bit
 // patterns is the numeric order, and a NaN of either sign is above +inf.  (With the general nsr_max_nan the compiler wraps every
 // maximum of the epilogue in an EXEC-mask branch: 4,047 -> 8,089 instructions in conv_halo_kernel's grouped epilogue.)

@@ -90,7 +90,7 @@ struct NsrCompOut {
 // (r, g, b, sigma) and z in `lds` (>= 640 floats, free for the workgroup to use; the caller has drained its DMAs), then
 // one wavefront per ray composites.  `mine`: this lane holds the result of point wave * 32 + m.  `tile`: index of the
 // 128-point tile in the launch (blockIdx.x for one-tile workgroups).  DEDICATED: `lds` is used for nothing else and at
-// least one workgroup barrier lies between two calls (persistent kernels), so the barrier that protects the previous
+// least one workgroup barrier lies between two calls, so the barrier that protects the previous
 // content is not needed.
 template <int NS, bool DEDICATED = false>
 __device__ __forceinline__ void composite_tile(float* lds, bool mine, int wave, int m, int lane, float4 value, float zk,

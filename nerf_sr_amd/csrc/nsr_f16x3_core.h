@@ -407,20 +407,17 @@ __device__ __forceinline__ const char* panel_block(const PanelRef& t, int panel,
 }
 // this lane's byte offset inside unit U (0 / 1) of a block: slot (2m + h) ^ 8U
 __device__ __forceinline__ unsigned unit_voff(int m, int h, int u) { return 16u * (unsigned)((2 * m + h) ^ (8 * u)); }
-// cache policy of the panel stores: write-once streams far larger than the caches, so non-temporal (round 2, same box,
-// 2,048-ray training step: default policy 7.51-7.54 ms, "sc0 sc1" 7.38 ms, "nt" 6.50 ms)
-#ifndef NSR_PANEL_STORE_POLICY
-#define NSR_PANEL_STORE_POLICY " nt"
-#endif
 // unit U of the block at `blk`: v = the four packed pairs, voff = unit_voff(m, h, U)
 template <int U>
 __device__ __forceinline__ void unit_store(const u32x4& v, const char* blk, unsigned voff) {
 #ifdef NSR_ABL_FWD_NO_STORE   // ablation (scripts/): how much of the TRAIN forward kernel is its panel writes
   if (voff != 0xffffffffu) return;
 #endif
-  // base through an in-statement SALU copy: see glds16_asm (VALU-restored SGPR -> VMEM hazard behind inline asm)
+  // base through an in-statement SALU copy: see glds16_asm (VALU-restored SGPR -> VMEM hazard behind inline asm).  Cache
+  // policy: write-once streams far larger than the caches, so non-temporal (round 2, same box, 2,048-ray training step:
+  // default policy 7.51-7.54 ms, "sc0 sc1" 7.38 ms, "nt" 6.50 ms)
   unsigned long long tmp;
-  asm volatile("s_mov_b64 %0, %3\n\tglobal_store_dwordx4 %1, %2, %0 offset:%4" NSR_PANEL_STORE_POLICY : "=&s"(tmp) : "v"(voff), "v"(v), "s"(blk), "n"(U * 1024) : "memory");
+  asm volatile("s_mov_b64 %0, %3\n\tglobal_store_dwordx4 %1, %2, %0 offset:%4 nt" : "=&s"(tmp) : "v"(voff), "v"(v), "s"(blk), "n"(U * 1024) : "memory");
 }
 
 // Sign panels: one bit per pre-activation ([z < 0], i.e. "the ReLU zeroes it"; +0.0 counts as active) of the layers whose

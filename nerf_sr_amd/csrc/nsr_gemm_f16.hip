@@ -1,15 +1,14 @@
 // Split-fp16 GEMM of the forward products (nsr_gemm.h: gemm_f16x3), v_mfma_f32_32x32x16_f16 x 3 per product.
 //
-// Workgroup = 2 x WN waves, each wave a 64 x 64 quadrant (2 x 2 accumulator blocks): 4 waves on a 128 x 128 tile, or
-// 8 waves on 128 x 256 when N >= 256 (the A panel -- activations, HBM traffic -- is then read once); K tiles of 32 =
-// two MFMA k-steps.  LDS holds the tile as four fp16 arrays (A hi, A lo, B hi, B lo; row stride 40 halves = 80 B,
+// Workgroup = 2 x WN waves (every launch: WN = 2, four waves), each wave a 64 x 64 quadrant (2 x 2 accumulator blocks) of a
+// 128 x 128 tile, or with BN = 4 a 64 x 128 half of a 128 x 256 tile when N >= 256 (the A panel -- activations, HBM
+// traffic -- is then read once); K tiles of 32 = two MFMA k-steps.  LDS holds the tile as four fp16 arrays (A hi, A lo, B hi, B lo; row stride 40 halves = 80 B,
 // which makes the 16-byte fragment reads of eight consecutive rows hit eight different 16-byte bank groups; the staging
 // stores need their own lane -> row assignment to stay conflict-free at that pitch, see stage_row);
-// single buffered with register prefetch (40 / 60 KB per workgroup; two waves per SIMD: two 4-wave workgroups or
-// one 8-wave workgroup per CU, so the MFMAs of one wave hide the staging and barriers of the other).  A is fp32 in memory and is split into (hi, lo) on its way from
+// single buffered with register prefetch (40 / 60 KB per workgroup; two waves per SIMD: two 4-wave workgroups per CU, so
+// the MFMAs of one wave hide the staging and barriers of the other).  A is fp32 in memory and is split into (hi, lo) on its way from
 // registers to LDS; B arrives pre-split.  Optional implicit im2col: the A rows are gathered from an NHWC activation
 // (a K tile of 32 channels never straddles a tap because cin % 32 == 0), so a 3 x 3 convolution needs no col matrix.
-#include <stdlib.h>
 #include <type_traits>
 #include "nsr_gemm.h"
 #include "nsr_gemm_epilogue.h"
@@ -21,10 +20,6 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// development switch: -DNSR_GEMM_K32_ONLY=1 keeps every launch on K tiles of 32 (A/B in profiles/)
-#ifndef NSR_GEMM_K32_ONLY
-#define NSR_GEMM_K32_ONLY 0
-#endif
 constexpr int kTM = 128, kTK = 32;   // row tile; default K tile (the kernels pad LDS rows by 8 halves)
 
 // Staging row of a thread (16-byte chunks, kCh per row and plane).  K tiles of 32: a row is 64 B of data at an 80 B pitch
@@ -32,15 +27,12 @@ constexpr int kTM = 128, kTK = 32;   // row tile; default K tile (the kernels pa
 // lanes 4-7 on row r + 1 overlap by four banks, a 2-way conflict on EVERY staging store (PMC, profiles/r3_refine_pmc.json:
 // 7.7 conflict cycles per store, 16 array cycles against the instruction's 13).  Rows r and r + 4 are 320 B = 16 banks
 // apart and do not collide, so the eight lanes take rows {r, r + 4}.  K tiles of 64: eight lanes = one 128 B row, no conflict.
-// (-DNSR_GEMM_NO_WROWS: the consecutive-row assignment, for A/B runs.)
 template <int kCh>
 __device__ __forceinline__ int stage_row(int tid) {
-#ifndef NSR_GEMM_NO_WROWS
   if constexpr (kCh == 4) {
     const int g8 = tid >> 3;
     return (g8 >> 2) * 8 + (g8 & 3) + 4 * ((tid >> 2) & 1);
   }
-#endif
   return tid / kCh;
 }
 
@@ -252,12 +244,8 @@ __device__ __forceinline__ void epilogue_planes(const GemmF16Args& a, f32x16 (&a
 
 // launch index -> tile index, see the kernel
 __device__ __forceinline__ int64_t xcd_tile(int64_t launch_idx, int64_t n_blocks) {
-#ifdef NSR_GEMM_NO_XCD
-  return launch_idx;
-#else
   const int64_t per_xcd = (n_blocks + 7) / 8;
   return (launch_idx % 8) * per_xcd + launch_idx / 8;
-#endif
 }
 
 // APL: A comes as (hi, lo) fp16 planes.  TK: K tile, 32 or (plane A only) 64 halves -- twice the MFMAs between two
@@ -574,14 +562,11 @@ struct HaloGeo {
 // waves per SIMD, and one workgroup's prologue (cold patch + weight fetch) and un-overlapped epilogue run under the other's
 // k-steps (VERDICT r5 "next" #3a; DESIGN 9: the epilogue was 3.1 ms of the pass with nothing beside it).  The other shapes
 // use the whole register file as the accumulator, or more than 80 KiB.
-#ifndef NSR_HALO_PAIR
-#define NSR_HALO_PAIR 1
-#endif
 template <int BN, int BM, bool GROUPED, int S>
 struct HaloOcc {
   using G = HaloGeo<BN, BM, GROUPED, S>;
   static constexpr int kLds = G::PATCH0 + G::PATCH1 + 4 * G::SLOT;
-  static constexpr int kWaves = (NSR_HALO_PAIR && BN * BM <= 8 && S == 1 && kLds <= 81920) ? 2 : 1;
+  static constexpr int kWaves = (BN * BM <= 8 && S == 1 && kLds <= 81920) ? 2 : 1;
 };
 // MULTI (round 6; with GROUPED's geometry): the eight images of a block are eight consecutive PLAIN images -- the 8 x 8-pixel
 // layers of the decoder and of the encoder over the synthesised patches, whose images are smaller than a plain block (16 x 16).
@@ -892,8 +877,6 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
   // conv_halo_kernel first: stride-1 3 x 3 gathers from pre-split planes into plane outputs with ReLU, whole 128 / 256
   // column tiles, whole spatial blocks, 32-bit byte offsets into A (round 6: the stride-2 layers, the 8 x 8-pixel layers and
   // the 3-channel first layer run here too; patch shapes that are not whole blocks stay on the staged tiles below)
-#ifndef NSR_GEMM_NO_HALO
-#ifndef NSR_HALO_NO_LAST
   // the refinement network's last layer: stride-1 gather from pre-split planes, 64 padded columns, tanh, fp32 NHWC output
   // (conv_halo_kernel<2, 2, false, 1>: 256 pixels x 64 columns per workgroup, 64 KiB of LDS, pairs per CU).  A matter of shape
   // only, like the choice below.
@@ -908,15 +891,11 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
     if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
     return NSR_OK;
   }
-#endif
   if (a.Ah && a.Ch && a.Bs && a.conv.cin > 0 && (a.conv.stride == 1 || a.conv.stride == 2) && (a.conv.cin % 16) == 0 && (g.N % 128) == 0 &&
       g.n_valid == g.N && !g.mask && !g.col_sums && g.act == kActRelu && g.acc_scale != 0.0f && g.acc_scale != 1.0f &&
       (a.group == 8 || a.group <= 1) && g.K == 9 * a.conv.cin && (reinterpret_cast<uintptr_t>(a.Bs) & 15) == 0) {
     // stride 2: every such layer of the network, the 128-channel one included (round 4 left it on the staged tile: measured
-    // slower here BEFORE the fragment-ordered weight copy existed; -DNSR_HALO_S2_MIN_CIN=256 restores that for A/B runs)
-#ifndef NSR_HALO_S2_MIN_CIN
-#define NSR_HALO_S2_MIN_CIN 128
-#endif
+    // slower here BEFORE the fragment-ordered weight copy existed)
     const bool grouped = a.group == 8, s2 = a.conv.stride == 2;
     const int64_t per_img = (int64_t)a.conv.Ho * a.conv.Wo;
     const int64_t in_rows = (g.M / per_img) * a.conv.Hs * a.conv.Ws;      // images x source pixels
@@ -927,7 +906,7 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
     // layer of the refinement network, whose entry points cut it first (nsr_refine.hip, sets_per_pass)
     const bool range32 = (a.a_plane + in_rows * g.lda) * 2 < ((int64_t)1 << 32) &&
                          16 * (grouped ? per_img : 1) * g.ldc < ((int64_t)1 << 32);
-    const bool common = (g.M % (per_img * (grouped ? 8 : 1))) == 0 && geometry && (!s2 || a.conv.cin >= NSR_HALO_S2_MIN_CIN) && range32;
+    const bool common = (g.M % (per_img * (grouped ? 8 : 1))) == 0 && geometry && (!s2 || a.conv.cin >= 128) && range32;
     // Shapes (rows x columns of a workgroup): 256 x 256 where N allows it, else 512 x 128 (stride 1) -- the whole register
     // file as the accumulator; 256 x 128 (half of it) where that wastes fewer CU-rounds: a 16 x 16 decoder layer is 338 of the
     // big tiles, two rounds of 256 CUs with the second a third full, against three rounds of half-size tiles.
@@ -944,13 +923,9 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
     // the halo shapes among themselves are bit-identical (same k-steps, same order per output element)
     // Round 6: where the half shape runs as a PAIR of workgroups per CU (plain stride-1 layers, HaloOcc) it is always taken:
     // a CU then holds the same 256 x 256 outputs as one big tile, with one workgroup's prologue / epilogue under the other's
-    // k-steps (same k order per output element: bit-identical; -DNSR_HALO_PAIR_WIDE=0 keeps the CU-rounds rule for A/B runs)
-#ifndef NSR_HALO_PAIR_WIDE
-#define NSR_HALO_PAIR_WIDE 0   // measured (one box, interleaved, bit-identical): 28.77 vs 28.80 ms -- nothing: the 256-column layers keep the big tile
-#endif
-    // ... and always on the 128-column plain layers (round 6: layer 0, all epilogue): the alternative there is ONE 512 x 128
-    // workgroup per CU with nothing beside its epilogue
-#ifndef NSR_HALO_NO_MULTI
+    // k-steps (same k order per output element: bit-identical) -- on the 128-column plain layers (round 6: layer 0, all
+    // epilogue), where the alternative is ONE 512 x 128 workgroup per CU with nothing beside its epilogue.  The 256-column
+    // layers keep the big tile: pairs there too measured nothing (one box, interleaved, bit-identical: 28.77 vs 28.80 ms).
     // Round 6: plain layers over 8 x 8-pixel images (smaller than a plain block): eight images per block on the grouped
     // geometry, 8 x 4 pixels x 8 images x 128 columns per workgroup (MULTI above).  Until then they ran on the staged tile at a
     // third of the matrix pipe (340 workgroups of 144 K tiles: 1.33 CU-rounds, nine-fold re-reads of the activations).  A
@@ -964,8 +939,7 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
       if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
       return NSR_OK;
     }
-#endif
-    const bool paired = NSR_HALO_PAIR && (NSR_HALO_PAIR_WIDE || !wide) && !grouped && !s2 && half_ok;
+    const bool paired = !wide && !grouped && !s2 && half_ok;
     const bool use_half = half_ok && (paired || !big_ok || 0.5 * 1.05 * rounds(half_blk) < rounds(big_blk));
     const bool use_big = !use_half && big_ok;
     if (use_half || use_big) {
@@ -977,17 +951,6 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
     if (grouped) hipLaunchKernelGGL((conv_halo_kernel<BN_, BM_, true, S_>), hgrid, dim3(256), 0, st, a, n_ct, n_blk);       \
     else hipLaunchKernelGGL((conv_halo_kernel<BN_, BM_, false, S_>), hgrid, dim3(256), 0, st, a, n_ct, n_blk);               \
   } while (0)
-#ifdef NSR_HALO_GROUPED_QUARTER
-      // experiment (round 6): the grouped 128-column layer as PAIRS of 128 x 128 workgroups (8 images x 8 x 2 pixels each, 80 KiB)
-      // instead of one 512 x 128 workgroup per CU
-      if (grouped && !s2 && !wide && !use_half && (a.conv.Ho % 2) == 0 && (g.M % 128) == 0) {
-        const int64_t q_blk = (g.M / 128) * (g.N / 128);
-        const dim3 qgrid((unsigned)(((q_blk + 7) / 8) * 8));
-        hipLaunchKernelGGL((conv_halo_kernel<4, 1, true, 1>), qgrid, dim3(256), 0, st, a, g.N / 128, q_blk);
-        if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
-        return NSR_OK;
-      }
-#endif
       if (s2) {
         if (use_half) NSR_HALO_LAUNCH(4, 2, 2); else NSR_HALO_LAUNCH(8, 2, 2);
       } else if (use_half) {
@@ -1002,38 +965,24 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
       return NSR_OK;
     }
   }
-#endif
   if ((g.K % kTK) != 0 || (a.conv.cin > 0 && (a.conv.cin % kTK) != 0)) return NSR_ERR_INVALID_ARG;   // staged tiles: K tiles of 32 inside a tap
   const int64_t row_tiles = (g.M + kTM - 1) / kTM;
-  const bool quad_ok = g.N >= 256 && (g.N % 256) == 0 && a.Ah && a.Ch;
-  bool wide = false;                                   // the 8-wave tile: NSR_GEMM_TILE=wide only
-  bool four_wave_wide = quad_ok && row_tiles * (g.N / 256) >= 1024;
-  // development switches (A/B runs on one box): NSR_GEMM_TILE=narrow|wide|quad overrides the choice, NSR_GEMM_TK=32 keeps K tiles of 32
-  const char* e_tile = nsr_dev_env("NSR_GEMM_TILE");
-  const char* e_tk = nsr_dev_env("NSR_GEMM_TK");
-  const char* e_fulln = nsr_dev_env("NSR_GEMM_FULLN");      // =0: keep the column test in the k-steps (A/B)
-  if (e_tile && e_tile[0] == 'n') four_wave_wide = false;
-  if (e_tile && e_tile[0] == 'w') { wide = g.N >= 256; four_wave_wide = false; }
-  if (e_tile && e_tile[0] == 'q') four_wave_wide = quad_ok;
-  if (four_wave_wide) wide = true;   // 128 x 256 tile on four waves (64 x 128 each)
+  // 128 x 256 tile on four waves (64 x 128 each) where there are enough row tiles to fill the chip with it
+  const bool wide = g.N >= 256 && (g.N % 256) == 0 && a.Ah && a.Ch && row_tiles * (g.N / 256) >= 1024;
   const int tn = wide ? 256 : 128;
   const int n_col_tiles = (g.N + tn - 1) / tn;
   const int64_t n_blocks = row_tiles * n_col_tiles;
   const dim3 grid((unsigned)(((n_blocks + 7) / 8) * 8));
   if (a.Ah) {
-    const bool k64 = (g.K % 64) == 0 && (a.conv.cin <= 0 || (a.conv.cin % 64) == 0) && !NSR_GEMM_K32_ONLY &&
-                     !(e_tk && e_tk[0] == '3');
-    const bool fulln = (g.N % 128) == 0 && !(e_fulln && e_fulln[0] == '0');   // four-wave 128 x 128 tiles only
-    if (four_wave_wide) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 32, 4>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
-    else if (wide && k64) hipLaunchKernelGGL((gemm_f16x3_kernel<4, true, 64>), grid, dim3(512), 0, st, a, n_col_tiles, n_blocks);
-    else if (wide) hipLaunchKernelGGL((gemm_f16x3_kernel<4, true>), grid, dim3(512), 0, st, a, n_col_tiles, n_blocks);
+    const bool k64 = (g.K % 64) == 0 && (a.conv.cin <= 0 || (a.conv.cin % 64) == 0);
+    const bool fulln = (g.N % 128) == 0;   // 128 x 128 tiles only
+    if (wide) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 32, 4>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
     else if (k64 && fulln) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 64, 2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
     else if (k64) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 64>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
     else if (fulln) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 32, 2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
     else hipLaunchKernelGGL((gemm_f16x3_kernel<2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
-  } else {
-    if (wide) hipLaunchKernelGGL((gemm_f16x3_kernel<4, false>), grid, dim3(512), 0, st, a, n_col_tiles, n_blocks);
-    else hipLaunchKernelGGL((gemm_f16x3_kernel<2, false>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
+  } else {   // fp32 A: the 128 x 128 tile (the wide tile wants plane A)
+    hipLaunchKernelGGL((gemm_f16x3_kernel<2, false>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
   }
   if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
   return NSR_OK;

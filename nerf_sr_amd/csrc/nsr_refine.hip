@@ -14,7 +14,6 @@
 // same 4 bytes per element as fp32), written by the producing GEMM's epilogue and staged by the consuming GEMM as
 // they are -- a 3 x 3 convolution reads every activation nine times, splitting it once instead of nine times is what
 // the kernel's issue slots were spent on (nsr_gemm.h: GemmF16Args::Ah / Ch).
-#include <stdlib.h>
 #include "nsr_common.h"
 #include "nsr_gemm.h"
 #include "../../include/nsr_refine.h"
@@ -499,7 +498,7 @@ int forward(const void* packed_v, int prec, int v, const float* x_synth, const f
   if (v == 0) {
     // encoder on the B * R reference patches, then the max over the R references (F_max_i)
     const Act fc0{k.fc0, nref * px0, 128, 0}, fc1{k.fc1, nref * px1, 256, 0}, fc2{k.fc2, nref * px2, 512, 0}, fc3{k.fc3, nref * px3, 512, 0};
-    const bool fused_max = prec == NSR_F16X3 && R == 8 && !nsr_dev_env("NSR_REFINE_SEPARATE_MAX");   // env: A/B runs
+    const bool fused_max = prec == NSR_F16X3 && R == 8;
     if (fused_max) {
       // the reference's 8 patches per tile (llff_refine_dataset.py: num_ref_patches): the producing GEMMs reduce over them
       // in their epilogues -- the four max kernels (1.1 ms per 800 x 800 frame, 5.1 GB read at 4.5 TB/s) are gone

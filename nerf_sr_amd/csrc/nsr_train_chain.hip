@@ -274,11 +274,7 @@ __device__ __forceinline__ void bwd_unit_store(const u32x4& v, const char* blk, 
 #ifdef NSR_ABL_BWD_STORE_L2   // ablation: the same store instructions, but every block of a wave lands on ONE 2 KiB run (L2-resident: no HBM writes)
   dst = reinterpret_cast<u32x4*>(reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(blk) & ~(uintptr_t)0x3FFF)) + U * 1024 + voff);
 #endif
-#ifdef NSR_ABL_BWD_DEFAULT_STORE   // A/B: the default cache policy instead of non-temporal
-  *dst = v;
-#else
   __builtin_nontemporal_store(v, dst);
-#endif
 }
 __device__ __forceinline__ void bwd_store_step(int s, const u32x4& h0, const u32x4& h1, const char* blk, unsigned voff0,
                                                unsigned voff1) {
@@ -582,18 +578,19 @@ chain_bwd_kernel(const float* __restrict__ packed, const unsigned* __restrict__ 
 // v_fma_mix per register pair, and one (NT = 2) or two (NT = 1) of the three MFMAs.  Error of a gradient tensor against
 // the fp64 oracle, predicted on the CPU (scripts/study_bwd_terms.py -> profiles/r6_bwd_terms_study.txt) and measured on
 // the device (tests/test_gpu_train.py, tolerances unchanged: 2e-3 of the norm, 5e-4 on the heads): see DESIGN 7.1.
-// A workgroup is still 4 waves x 32 points; with <= 256 registers and a 48 KiB ring (NT = 1) two workgroups share a CU,
-// so one wave's re-split VALU, LDS reads and DMA issue run under the other's MFMAs.
+// A workgroup is 8 waves x 32 points, two waves per SIMD sharing the ring (256 points per tile: half the L2 -> LDS weight
+// traffic per point), so one wave's re-split VALU, LDS reads and DMA issue run under the other's MFMAs.  (Round 6 also built
+// 4-wave workgroups, one wave per SIMD: 425 vs 371 us per pass; removed after commit 93a8826, recoverable from git.)
 // =========================================================================================================
-template <int NT, int W>
+constexpr int kHWaves = 8;   // waves per workgroup
+template <int NT>
 struct HCfg {
   static_assert(NT == 1 || NT == 2, "reduced-term chain: one or two MFMAs per product");
-  static_assert(W == 4 || W == 8, "waves per workgroup: one or two per SIMD");
   static constexpr int kChunkPieces = NT == 1 ? 16 : 32;       // 16 k-steps x hi (x lo)
   static constexpr int kSlotB = kChunkPieces * 1024;           // one ring slot
   static constexpr int kLayerPieces = 8 * kChunkPieces;
   static constexpr int kPieces = kLayerPieces * kBwdLayers;
-  static constexpr int kMine = kChunkPieces / W;               // pieces of every chunk one wave moves
+  static constexpr int kMine = kChunkPieces / kHWaves;         // pieces of every chunk one wave moves
   // ring depth: the chunk of sequence number q lives in slot q % kDepth and is fetched kDepth - 1 chunks ahead, during chunk
   // q - kDepth + 1, into the slot chunk q - kDepth has just left.
   static constexpr int kDepth = 3;
@@ -611,29 +608,22 @@ struct HCfg {
 };
 // the same count for block `nb` of the FIRST layer (global block b = nb): block 0 stores nothing (no pending block), and the
 // chunks 1 .. kDepth - 2 were fetched -- and waited for -- by the prologue (63 = no wait)
-template <int NT, int W>
+template <int NT>
 constexpr int hyoung_first(int nb) {
-  using C = HCfg<NT, W>;
+  using C = HCfg<NT>;
   const int lo = nb - C::kDepth + 2;           // the block that issued chunk nb + 1
   if (lo < 0) return 63;
   int n = lo == 0 ? 0 : 2;
   for (int i = lo + 1; i < nb; ++i) n += C::kMine + (i == 0 ? 0 : 2);
   return n;
 }
-template <int NT, int W>
-struct HOcc {
-  // waves per SIMD: W = 8 is one workgroup of two waves per SIMD sharing the ring (256 points per tile: half the L2 -> LDS
-  // weight traffic per point); W = 4 is one wave per SIMD
-  static constexpr int kWavesPerEu = W == 8 ? 2 : 1;
-};
-// the contiguous share of a chunk that wave `wave` of W moves
-template <int W>
+// the contiguous share of a chunk that wave `wave` of kHWaves moves
 __device__ __forceinline__ ChunkRef make_ref_w(int piece0, int pieces, int wave) {
   ChunkRef c;
   c.piece0 = piece0;
   c.pieces = pieces;
-  c.first = (wave * pieces) / W;
-  c.count = ((wave + 1) * pieces) / W - c.first;
+  c.first = (wave * pieces) / kHWaves;
+  c.count = ((wave + 1) * pieces) / kHWaves - c.first;
   return c;
 }
 // MODE = MFMA terms per product over the nine layers of the chain: 1 or 2 = that many everywhere; 12 = MIXED (round 6): two
@@ -652,12 +642,12 @@ __device__ __host__ constexpr int layer_piece0(int lam) {      // first 1 KiB pi
 }
 template <int MODE>
 __device__ __host__ constexpr int stream_pieces() { return layer_piece0<MODE>(kBwdLayers); }
-template <int MODE, int W>
+template <int MODE>
 __device__ __forceinline__ ChunkRef hseq(int q, int wave) {   // chunk q = 8 lam + nb; past the end chunk 0 again (idle slot)
   const int qq = q < 8 * kBwdLayers ? q : 0;
   const int lam = qq >> 3, nb = qq & 7;
   const int pieces = (MODE == 12 ? (lam < 6 ? 2 : 1) : MODE) == 1 ? 16 : 32;
-  return make_ref_w<W>(layer_piece0<MODE>(lam) + nb * pieces, pieces, wave);
+  return make_ref_w(layer_piece0<MODE>(lam) + nb * pieces, pieces, wave);
 }
 struct PreH {
   u32x4 ah[kPF], al[kPF];   // al: NT = 2 only
@@ -774,7 +764,7 @@ __device__ __forceinline__ void hsplit_gap(int s, int g, Acc& p, unsigned mz, Sc
 }
 
 // bwd_layer without the lo operand set (see there for the flags)
-template <int MODE, int NT, int NTN, int W, bool PREV_MASK, bool MASK, bool ADD, bool LAST, bool NEXT_MASK, bool FIRST = false>
+template <int MODE, int NT, int NTN, bool PREV_MASK, bool MASK, bool ADD, bool LAST, bool NEXT_MASK, bool FIRST = false>
 __device__ __forceinline__ void bwd_layer_h(int lam, int prev_panel, int panel, int next_panel, u32x4 (&bh)[16], u32x4 (&oh)[16],
                                             const float* wsig_h, float d_sigma, Loader& ld, unsigned ring0, Acc& pend, PreH& pre,
                                             unsigned (&mz)[2], Scale& prev, const BwdCtx& cx) {
@@ -787,9 +777,9 @@ __device__ __forceinline__ void bwd_layer_h(int lam, int prev_panel, int panel, 
 #pragma unroll
   for (int nb = 0; nb < 8; ++nb) {
     const int q = 8 * lam + nb;
-    constexpr int D = HCfg<NT, W>::kDepth;
-    constexpr unsigned kSlot = (unsigned)HCfg<max_nt<MODE>(), W>::kSlotB;      // slots are sized for the chain's widest chunk
-    const ChunkRef c2 = hseq<MODE, W>(q + D - 1, ld.wave);     // the chunk fetched during this block
+    constexpr int D = HCfg<NT>::kDepth;
+    constexpr unsigned kSlot = (unsigned)HCfg<max_nt<MODE>()>::kSlotB;      // slots are sized for the chain's widest chunk
+    const ChunkRef c2 = hseq<MODE>(q + D - 1, ld.wave);     // the chunk fetched during this block
     // slots of chunks q, q + 1 and of the chunk fetched now (= the slot chunk q - 1 has left)
     ld.slot_cur = ring0 + ((unsigned)q % D) * kSlot;
     ld.slot_next = ring0 + ((unsigned)(q + 1) % D) * kSlot;
@@ -814,7 +804,7 @@ __device__ __forceinline__ void bwd_layer_h(int lam, int prev_panel, int panel, 
     // the chunk fetched during this block (q + 2) and the one whose first fragments are prefetched at its end (q + 1) belong to
     // the next layer from blocks 6 / 7 on
     auto mma = [&](auto young, auto fetch_nt, auto pre_nt) {
-      block_mma_h<NT, HCfg<decltype(fetch_nt)::value, W>::kMine, kBar, decltype(young)::value>(
+      block_mma_h<NT, HCfg<decltype(fetch_nt)::value>::kMine, kBar, decltype(young)::value>(
           acc, pre, a_addr, ld, c2, [&](int s) -> u32x4 { return bh[s]; },
           [&](int s, int g) {
             if (nb == 0) {
@@ -837,13 +827,13 @@ __device__ __forceinline__ void bwd_layer_h(int lam, int prev_panel, int panel, 
     };
     if (FIRST) {
       switch (nb) {   // nb is a constant after unrolling
-#define NSR_YF(B) case B: mma_nb(std::integral_constant<int, hyoung_first<NT, W>(B)>{}); break;
+#define NSR_YF(B) case B: mma_nb(std::integral_constant<int, hyoung_first<NT>(B)>{}); break;
         NSR_YF(0) NSR_YF(1) NSR_YF(2) NSR_YF(3) NSR_YF(4) NSR_YF(5) NSR_YF(6) NSR_YF(7)
 #undef NSR_YF
         default: break;
       }
     } else {
-      mma_nb(std::integral_constant<int, HCfg<NT, W>::kYoungSteady>{});
+      mma_nb(std::integral_constant<int, HCfg<NT>::kYoungSteady>{});
     }
     if (ADD) {
 #pragma unroll
@@ -855,22 +845,22 @@ __device__ __forceinline__ void bwd_layer_h(int lam, int prev_panel, int panel, 
   prev = cur;
 }
 
-template <int MODE, int W>
-__global__ void __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(HOcc<max_nt<MODE>(), W>::kWavesPerEu, HOcc<max_nt<MODE>(), W>::kWavesPerEu)))
+template <int MODE>
+__global__ void __launch_bounds__(64 * kHWaves) __attribute__((amdgpu_waves_per_eu(2, 2)))   // two waves per SIMD
 chain_bwd_h_kernel(const float* __restrict__ packed, const unsigned* __restrict__ sgn, char* __restrict__ dpan,
                    const float* __restrict__ d_rgb, int d_rgb_stride, const float* __restrict__ d_sigma, int d_sigma_stride,
                    int64_t P, unsigned* __restrict__ gmax, float* __restrict__ pscale) {
   constexpr int NT = max_nt<MODE>();         // ring geometry: the widest chunk
   constexpr int NT0 = nt_of<MODE>(0);
-  using C = HCfg<NT, W>;
+  using C = HCfg<NT>;
   constexpr int kAux0 = C::kDepth * C::kSlotB / 4;
-  __shared__ __attribute__((aligned(16))) float ring[kAux0 + kBwdAuxFloats + 16 + W * 64];
+  __shared__ __attribute__((aligned(16))) float ring[kAux0 + kBwdAuxFloats + 16 + kHWaves * 64];
   unsigned* lmax = reinterpret_cast<unsigned*>(ring + kAux0 + kBwdAuxFloats);
   if (threadIdx.x < 16) lmax[threadIdx.x] = 0u;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int m = lane & 31, h = lane >> 5;
-  for (int i = threadIdx.x; i < kBwdAuxFloats; i += 64 * W) ring[kAux0 + i] = packed[stream_pieces<MODE>() * 256 + i];
+  for (int i = threadIdx.x; i < kBwdAuxFloats; i += 64 * kHWaves) ring[kAux0 + i] = packed[stream_pieces<MODE>() * 256 + i];
 
   Loader ld;
   ld.stream = packed;
@@ -883,16 +873,16 @@ chain_bwd_h_kernel(const float* __restrict__ packed, const unsigned* __restrict_
   // chunks 0 .. kDepth - 2 stream in behind the prologue
 #pragma unroll
   for (int c = 0; c < C::kDepth - 1; ++c) {
-    loader_prepare_dma(ld, hseq<MODE, W>(c, wave), ring0 + (unsigned)c * (unsigned)C::kSlotB);
+    loader_prepare_dma(ld, hseq<MODE>(c, wave), ring0 + (unsigned)c * (unsigned)C::kSlotB);
 #pragma unroll
-    for (int i = 0; i < HCfg<NT0, W>::kMine; ++i) loader_issue(ld, i);       // chunks 0, 1: layer 0's geometry
+    for (int i = 0; i < HCfg<NT0>::kMine; ++i) loader_issue(ld, i);       // chunks 0, 1: layer 0's geometry
   }
 
   // panels are laid out in point groups of 32 (one wave), four per 128-point tile of the FORWARD kernel: n_groups follows
-  // from P alone.  With W = 8 the last workgroup may hold up to four waves past the end: they repeat the last real group
+  // from P alone.  The last workgroup may hold up to four waves past the end: they repeat the last real group
   // (same inputs, same results, same stores: a benign duplicate) so that every wave's DMA / store counts stay uniform.
   const int64_t n_groups = ((P + 127) / 128) * 4;
-  int64_t group = (int64_t)blockIdx.x * W + wave;
+  int64_t group = (int64_t)blockIdx.x * kHWaves + wave;
   group = group < n_groups ? group : n_groups - 1;
   const int64_t p = group * 32 + m;
   const int64_t pc = p < P ? p : P - 1;
@@ -967,7 +957,7 @@ chain_bwd_h_kernel(const float* __restrict__ packed, const unsigned* __restrict_
   PreH pre;
 #pragma unroll
   for (int k = 0; k < kPF; ++k) prefetch_frag_h<NT0>(pre, k, ld.slot_cur + ld.lane_off);
-  loader_prepare_dma(ld, hseq<MODE, W>(C::kDepth - 1, wave), ld.slot_free);   // replaced at the first publish point; keeps the descriptor defined
+  loader_prepare_dma(ld, hseq<MODE>(C::kDepth - 1, wave), ld.slot_free);   // replaced at the first publish point; keeps the descriptor defined
 
   Acc pend;
 #pragma unroll
@@ -977,8 +967,8 @@ chain_bwd_h_kernel(const float* __restrict__ packed, const unsigned* __restrict_
   if constexpr (MODE == 12) {
     // nine layers written out: each with its own and its successor's geometry (the register sets swap roles layer by layer)
 #define NSR_L(LAM, PM, M, ADDF, LASTF, NM, FIRSTF, PP, P_, NP, IN, OUT)                                                                   \
-    bwd_layer_h<MODE, nt_of<MODE>(LAM), nt_of<MODE>(LAM < 8 ? LAM + 1 : 0), W, PM, M, ADDF, LASTF, NM, FIRSTF>(LAM, PP, P_, NP, IN, OUT, wsig_h, \
-                                                                                                               gs, ld, ring0, pend, pre, mz, prev, cx)
+    bwd_layer_h<MODE, nt_of<MODE>(LAM), nt_of<MODE>(LAM < 8 ? LAM + 1 : 0), PM, M, ADDF, LASTF, NM, FIRSTF>(LAM, PP, P_, NP, IN, OUT, wsig_h, \
+                                                                                                            gs, ld, ring0, pend, pre, mz, prev, cx)
     NSR_L(0, false, false, false, false, true, true, -1, 8, 7, bh, oh);
     NSR_L(1, false, true, true, false, true, false, 8, 7, 6, oh, bh);
     NSR_L(2, true, true, false, false, true, false, 7, 6, 5, bh, oh);
@@ -990,15 +980,15 @@ chain_bwd_h_kernel(const float* __restrict__ packed, const unsigned* __restrict_
     NSR_L(8, true, true, false, true, false, false, 1, 0, -1, bh, oh);
 #undef NSR_L
   } else {
-  bwd_layer_h<MODE, NT, NT, W, false, false, false, false, true, true>(0, -1, 8, 7, bh, oh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
-  bwd_layer_h<MODE, NT, NT, W, false, true, true, false, true>(1, 8, 7, 6, oh, bh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
+  bwd_layer_h<MODE, NT, NT, false, false, false, false, true, true>(0, -1, 8, 7, bh, oh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
+  bwd_layer_h<MODE, NT, NT, false, true, true, false, true>(1, 8, 7, 6, oh, bh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
 #pragma unroll 1
   for (int pair = 0; pair < 3; ++pair) {
     const int lam = 2 + 2 * pair;
-    bwd_layer_h<MODE, NT, NT, W, true, true, false, false, true>(lam, 9 - lam, 8 - lam, 7 - lam, bh, oh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
-    bwd_layer_h<MODE, NT, NT, W, true, true, false, false, true>(lam + 1, 8 - lam, 7 - lam, 6 - lam, oh, bh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
+    bwd_layer_h<MODE, NT, NT, true, true, false, false, true>(lam, 9 - lam, 8 - lam, 7 - lam, bh, oh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
+    bwd_layer_h<MODE, NT, NT, true, true, false, false, true>(lam + 1, 8 - lam, 7 - lam, 6 - lam, oh, bh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
   }
-  bwd_layer_h<MODE, NT, NT, W, true, true, false, true, false>(8, 1, 0, -1, bh, oh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
+  bwd_layer_h<MODE, NT, NT, true, true, false, true, false>(8, 1, 0, -1, bh, oh, wsig_h, gs, ld, ring0, pend, pre, mz, prev, cx);
   }
   {
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");   // MFMA write-back before inline asm reads the accumulators
@@ -1057,11 +1047,6 @@ extern "C" NSR_INTERNAL int nsr_chain_bwd(const void* packed, const unsigned* sg
                                           float* pscale, int terms, int gmax_is_zero, void* stream) {
   if (!bwd_terms_ok(terms)) return NSR_ERR_INVALID_ARG;
   if (P <= 0) return NSR_OK;
-#ifdef NSR_BWD_WAVES   // A/B builds: 4 = one wave per SIMD for the two-term chain / two 4-wave workgroups per CU for the one-term chain
-  const int waves = NSR_BWD_WAVES;
-#else
-  const int waves = 8;
-#endif
   // gmax_is_zero: the caller's previous kernel has cleared the ten words (the training step: composite_bwd_kernel)
   if (!gmax_is_zero && hipMemsetAsync(gmax, 0, 10 * sizeof(unsigned), nsr_stream(stream)) != hipSuccess) return NSR_ERR_LAUNCH;
   const dim3 grid((unsigned)((P + 127) / 128)), block(256);
@@ -1070,17 +1055,13 @@ extern "C" NSR_INTERNAL int nsr_chain_bwd(const void* packed, const unsigned* sg
   char* dp = static_cast<char*>(dpan);
   hipStream_t st = nsr_stream(stream);
   if (terms == 12)
-    hipLaunchKernelGGL((chain_bwd_h_kernel<12, 8>), grid8, block8, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
+    hipLaunchKernelGGL((chain_bwd_h_kernel<12>), grid8, block8, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
   else if (terms == 3)
     hipLaunchKernelGGL(chain_bwd_kernel, grid, block, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
-  else if (terms == 2 && waves == 8)
-    hipLaunchKernelGGL((chain_bwd_h_kernel<2, 8>), grid8, block8, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
   else if (terms == 2)
-    hipLaunchKernelGGL((chain_bwd_h_kernel<2, 4>), grid, block, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
-  else if (waves == 8)
-    hipLaunchKernelGGL((chain_bwd_h_kernel<1, 8>), grid8, block8, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
+    hipLaunchKernelGGL((chain_bwd_h_kernel<2>), grid8, block8, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
   else
-    hipLaunchKernelGGL((chain_bwd_h_kernel<1, 4>), grid, block, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
+    hipLaunchKernelGGL((chain_bwd_h_kernel<1>), grid8, block8, 0, st, pk, sgn, dp, d_rgb, d_rgb_stride, d_sigma, d_sigma_stride, P, gmax, pscale);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }

@@ -1,8 +1,7 @@
-"""Every documented build variant (nerf_sr_amd/build.py VARIANTS: the persistent tile loop, the in-shadow encoding, the timeline
-stamps, the ablation switches of the measurement ladders, the environment-read development switches) still COMPILES for gfx950
-and still honours the inline-asm ISA contract -- on the CPU box, so that the alternative kernels inside the product translation
-units cannot rot between the rounds that use them (VERDICT r4 'next' #6).  hipcc -S of the touched units only; listings are
-cached by source hash, a cold run takes about a minute on 8 cores."""
+"""Every documented build variant (nerf_sr_amd/build.py VARIANTS: the timeline stamps and the ablation switches of the
+measurement ladders) still COMPILES for gfx950 and still honours the inline-asm ISA contract -- on the CPU box, so that the
+instruments inside the product translation units cannot rot between the rounds that use them (VERDICT r4 'next' #6).  hipcc -S
+of the touched units only; listings are cached by source hash."""
 import os
 import shutil
 from concurrent.futures import ThreadPoolExecutor
@@ -26,7 +25,7 @@ def test_every_switch_in_the_sources_belongs_to_a_documented_variant():
     """A preprocessor switch in csrc/ that no VARIANTS entry defines is one nobody compiles: list it or delete it."""
     import re
     known = {d.split("=")[0][2:] for defs, _, _ in nsr_build.VARIANTS.values() for d in defs}
-    tunables = {"NSR_MAX_SPLITS", "NSR_H1_WAVES", "NSR_HALO_SPREAD", "NSR_PANEL_STORE_POLICY", "NSR_F16X3_KPF", "NSR_SLICE_INLINE"}  # #ifndef X / #define X default
+    tunables = {"NSR_MAX_SPLITS", "NSR_H1_WAVES", "NSR_HALO_SPREAD", "NSR_F16X3_KPF", "NSR_SLICE_INLINE"}  # #ifndef X / #define X default
     seen = set()
     for fn in os.listdir(nsr_build.CSRC):
         if fn.endswith((".hip", ".h")):
