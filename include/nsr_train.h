@@ -128,6 +128,40 @@ int nsr_train_loss_and_grads_var(const float* const* w_coarse, const float* cons
                                  void* workspace, size_t workspace_bytes, void* stream, const nsr_train_var_losses* var,
                                  float* var_losses);
 
+/* The same training step as a FORWARD / BACKWARD pair, for a loss the caller writes (torch autograd: nerf_sr_amd/train.py
+ * forward_rays_train; the reference's calculate_losses, regularize_patch, --sisr_path / --with_ref terms, gradient clipping).
+ * nsr_train_forward is the first half of nsr_train_loss_and_grads: train-mode forward_rays (:280-313) with the same draws,
+ * render_flags, precisions, ray strides, `ray_chunk` and 32-point rule, the same kernels and the same outputs bit for bit
+ * (outs[0] and outs[4] required, the other six may be NULL); no target, no s2, no loss.  Every argument is checked before
+ * anything is enqueued.  It ORs the same NSR_FLAG_* bits into the workspace's sticky status block (nsr_train_status).
+ * What the backward needs stays in the caller's `saved` buffer (>= nsr_train_saved_bytes, 256-byte aligned; one per forward
+ * call that is still to be differentiated -- the workspace is scratch and may be shared by any number of them): a header with
+ * the run's parameters, the backward weight streams of both networks (NSR_F16X3*), and per ray chunk and network the (rgb,
+ * sigma) of every sample point, its depth z, and the forward activations -- the chain kernels' 2-byte panels and sign words
+ * (NSR_F16X3*) or the per-layer fp32 matrices (NSR_FP32, NSR_F16X3_GEMM).  At the bench's training batch (2,048 rays,
+ * 64 + 64 samples = 393,216 sample points, one chunk): 2.13 GB under NSR_F16X3 (5.4 KB per sample point; the two weight streams
+ * are 6 MB of it), 3.99 GB under NSR_FP32 (10.1 KB per point).
+ * nsr_train_saved_bytes: 0 on invalid arguments (R <= 0 included); depends on its arguments only.
+ *
+ * nsr_train_backward: d(loss)/d(weights) of both networks from the upstream gradients g_outs[8] (DEVICE pointers in the outs
+ * order: (R, 3) (R) (R) (R, Nc) coarse, the same with Nc + Ni columns fine; any entry NULL = zero).  The fine pass samples from
+ * the DETACHED coarse weights (:302): the coarse `weights` gradient reaches the coarse network only.  g_coarse / g_fine are
+ * OVERWRITTEN, chunk by chunk in the fused step's order, so that given the upstream gradient the fused step computes
+ * internally the result is bit-identical to nsr_train_loss_and_grads.  R, the sample counts, render_flags, precision and
+ * ray_chunk are read back from `saved` (the call waits for the stream to read the header: at the bench's batch the GPU idles
+ * ~30 us in front of the backward, and the call cannot be captured into a graph): a buffer that no forward call
+ * wrote is NSR_ERR_INVALID_ARG, one smaller than its header says NSR_ERR_WORKSPACE; the workspace must be large enough for
+ * that run (nsr_train_workspace_bytes_for).  The weights must be the forward call's (the GEMM path re-reads them).  `saved`
+ * is not modified: a second backward of the same forward is allowed and gives the same gradients. */
+size_t nsr_train_saved_bytes(int precision, int64_t R, int n_coarse, int n_importance, int64_t ray_chunk);
+int nsr_train_forward(const float* const* w_coarse, const float* const* w_fine, const float* rays, int ray_stride, int64_t R,
+                      int n_coarse, int n_importance, int render_flags, int lindisp, const float* u_coarse, const float* u_fine,
+                      const float* noise_coarse, const float* noise_fine, float noise_std, int precision, int64_t ray_chunk,
+                      float* const* outs, void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream);
+int nsr_train_backward(const float* const* w_coarse, const float* const* w_fine, const float* const* g_outs,
+                       float* const* g_coarse, float* const* g_fine, void* workspace, size_t workspace_bytes,
+                       const void* saved, size_t saved_bytes, void* stream);
+
 /* Numerics status of the training step (the reference drops into pdb on NaN colours, nerf_downX_model.py:273-274; a
  * replacement reports instead).  The FIRST 64 BYTES of the workspace are a sticky status block: with NSR_F16X3 every
  * nsr_train_loss_and_grads ORs NSR_FLAG_WEIGHT_RANGE (a weight of the iteration's re-pack is non-finite or |w| >= 1023.75:

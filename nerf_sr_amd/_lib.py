@@ -74,6 +74,12 @@ SIGNATURES = {
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_int, c_int64,
                                              POINTER(c_void_p), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p,
                                              c_void_p, c_void_p]),
+    "nsr_train_saved_bytes": (c_size_t, [c_int, c_int64, c_int, c_int, c_int64]),
+    "nsr_train_forward": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64, POINTER(c_void_p),
+                                  c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "nsr_train_backward": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                   c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "nsr_train_status_reset": (c_int, [c_void_p, c_void_p]),
     "nsr_train_status": (c_int, [c_void_p, c_int, POINTER(c_uint), c_void_p]),
     "nsr_adam_step": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int,

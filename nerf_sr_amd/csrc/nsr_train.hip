@@ -245,12 +245,15 @@ __device__ __forceinline__ float colour_head_bwd(float g, float y, int head) {
 // Outputs in the GEMM path's training layout: d_rgb (P, 32) columns 0..2 (3..31 zeroed); d_sigma into column 256 of
 // g1 (P, 288) (257..287 zeroed).  COMPACT (chain path): one float4 per point, d4[p] = (d_rgb_pre 0..2, d_sigma) -- 16 bytes
 // instead of 256 written per point, and one 16-byte read per point for the backward chain instead of two strided ones.
-template <int K, bool COMPACT>
+// FULL (nsr_train_backward: upstream gradients of every output): gw_k also takes + g_opacity (opacity = sum_k w_k) and
+// + g_weights[k]; either pointer may be null.  The fused step's instantiations (FULL = false) do not contain the two terms.
+template <int K, bool COMPACT, bool FULL>
 __global__ void __launch_bounds__(256) composite_bwd_kernel(const float* __restrict__ rgb4, const float* __restrict__ sigma,
                                                             const float* __restrict__ z, const float* __restrict__ g_comp,
                                                             int64_t R, int N, int white,
                                                             float* __restrict__ d_rgb, float* __restrict__ g1,
-                                                            const float* __restrict__ g_depth, float* __restrict__ bias_part) {
+                                                            const float* __restrict__ g_depth, float* __restrict__ bias_part,
+                                                            const float* __restrict__ g_opacity, const float* __restrict__ g_weights) {
   const int lane = threadIdx.x & 63;
   // COMPACT (chain path): `g1` carries the backward chain's ten gmax words, cleared here -- the kernel that runs right in front
   // of the chain -- instead of by a memset launch of their own (round 6)
@@ -310,6 +313,10 @@ __global__ void __launch_bounds__(256) composite_bwd_kernel(const float* __restr
     w[i] = __fmul_rn(alpha[i], T[i]);
     gw[i] = gc0 * c0[i] + gc1 * c1[i] + gc2 * c2[i] - white_term;
     if (g_depth) gw[i] += gd * zk[i];
+    if (FULL) {
+      if (g_opacity) gw[i] += g_opacity[r];
+      if (g_weights && k < N) gw[i] += g_weights[base + k];
+    }
     if (k < N) acc += (double)gw[i] * (double)w[i];
     pre[i] = acc;
   }
@@ -1004,24 +1011,214 @@ int chain_bwd_terms(int precision) {
 bool train_precision_ok(int precision) { return precision == NSR_FP32 || chain_selected(precision) || precision == NSR_F16X3_GEMM; }
 int gemm_precision(int precision) { return precision == NSR_F16X3_GEMM ? NSR_F16X3 : precision; }   // what the GEMM path's helpers expect
 
-int composite_bwd(hipStream_t st, const Work& k, const float* z, int64_t R, int N, int white, bool compact, const float* g_depth) {
+// g_opacity / g_weights (nsr_train_backward only): non-null selects the FULL instantiation
+int composite_bwd(hipStream_t st, const Work& k, const float* z, const float* g_comp, int64_t R, int N, int white, bool compact,
+                  const float* g_depth, const float* g_opacity = nullptr, const float* g_weights = nullptr) {
   const dim3 block(256), grid((unsigned)((R + 3) / 4));
   const int K = (N + 63) / 64;
-#define NSR_LAUNCH_CB(KK)                                                                                                          \
+  const bool full = g_opacity || g_weights;
+#define NSR_LAUNCH_CB(KK, FF)                                                                                                      \
   do {                                                                                                                             \
-    if (compact) hipLaunchKernelGGL((composite_bwd_kernel<KK, true>), grid, block, 0, st, k.rgb, k.sig, z, k.g_comp, R, N, white, k.d4, reinterpret_cast<float*>(k.gmax), g_depth, k.bias_part); \
-    else hipLaunchKernelGGL((composite_bwd_kernel<KK, false>), grid, block, 0, st, k.rgb, k.sig, z, k.g_comp, R, N, white, k.drgb, k.g1, g_depth, nullptr);   \
+    if (compact) hipLaunchKernelGGL((composite_bwd_kernel<KK, true, FF>), grid, block, 0, st, k.rgb, k.sig, z, g_comp, R, N, white, k.d4, reinterpret_cast<float*>(k.gmax), g_depth, k.bias_part, g_opacity, g_weights); \
+    else hipLaunchKernelGGL((composite_bwd_kernel<KK, false, FF>), grid, block, 0, st, k.rgb, k.sig, z, g_comp, R, N, white, k.drgb, k.g1, g_depth, nullptr, g_opacity, g_weights); \
+  } while (0)
+#define NSR_LAUNCH_CB2(KK)            \
+  do {                                \
+    if (full) NSR_LAUNCH_CB(KK, true); \
+    else NSR_LAUNCH_CB(KK, false);    \
   } while (0)
   switch (K) {
-    case 1: NSR_LAUNCH_CB(1); break;
-    case 2: NSR_LAUNCH_CB(2); break;
-    case 3: NSR_LAUNCH_CB(3); break;
-    case 4: NSR_LAUNCH_CB(4); break;
+    case 1: NSR_LAUNCH_CB2(1); break;
+    case 2: NSR_LAUNCH_CB2(2); break;
+    case 3: NSR_LAUNCH_CB2(3); break;
+    case 4: NSR_LAUNCH_CB2(4); break;
     default: return NSR_ERR_UNSUPPORTED;
   }
+#undef NSR_LAUNCH_CB2
 #undef NSR_LAUNCH_CB
   NSR_CHECK_LAUNCH();
   return NSR_OK;
+}
+
+// ---- one training call, split into its forward and backward halves ----------------------------------------------------
+// nsr_train_loss_and_grads runs the two halves of every (chunk, network) pass back to back on ONE set of buffers (the
+// workspace's Work); nsr_train_forward / nsr_train_backward run them in two calls, with what a backward half reads kept
+// per pass in the caller's `saved` buffer (SavedPass below) and pointed to by the same Work fields.
+struct Run {   // the validated arguments of one call
+  int64_t R, chunk;
+  int nc, ni, flags, precision, lindisp, ray_stride;
+  float noise_std;
+  bool chain;
+};
+
+// the rules every training entry point shares, in train_impl's order: sample counts and precision (NSR_ERR_UNSUPPORTED),
+// R and the chunk multiples of s2 (NSR_ERR_INVALID_ARG), a multiple of 32 points per pass in both networks
+// (NSR_ERR_UNSUPPORTED).  ray_chunk <= 0 or > R becomes R.
+int check_shape(int64_t R, int s2, int n_coarse, int n_importance, int precision, int64_t& ray_chunk) {
+  if (n_coarse < 2 || n_importance < 1 || n_coarse + n_importance > 256) return NSR_ERR_UNSUPPORTED;
+  if (!train_precision_ok(precision)) return NSR_ERR_UNSUPPORTED;
+  if (R % s2 != 0) return NSR_ERR_INVALID_ARG;
+  if (ray_chunk <= 0 || ray_chunk > R) ray_chunk = R;
+  if (ray_chunk % s2 != 0) return NSR_ERR_INVALID_ARG;
+  // the split-K weight-gradient GEMM contracts over the chunk's sample points in K tiles of 32: every chunk,
+  // the shorter last one included, must hold a multiple of 32 points in both passes -- checked BEFORE anything
+  // is enqueued, so a rejected call leaves outputs and gradients untouched
+  for (int64_t r0 = 0; r0 < R; r0 += ray_chunk) {
+    const int64_t rc = (R - r0 < ray_chunk) ? R - r0 : ray_chunk;
+    if ((rc * n_coarse) % 32 != 0 || (rc * (n_coarse + n_importance)) % 32 != 0) return NSR_ERR_UNSUPPORTED;
+  }
+  return NSR_OK;
+}
+// the option word (include/nsr_train.h): the renderer's two bits + the colour head's two + stop_grad
+constexpr int kTrainOpts = NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS | NSR_TRAIN_GAMMA_CORRECT | NSR_TRAIN_COLOR_NONE | NSR_TRAIN_STOP_GRAD;
+int check_flags(int flags) {
+  if ((flags & ~kTrainOpts) != 0) return NSR_ERR_INVALID_ARG;
+  // pow(x, 1 / 2.2) of an unbounded head: NaN for every negative value
+  if ((flags & NSR_TRAIN_GAMMA_CORRECT) && (flags & NSR_TRAIN_COLOR_NONE)) return NSR_ERR_UNSUPPORTED;
+  return NSR_OK;
+}
+
+// the weights of both networks in the form the path's kernels read, once per call
+int prepare_call(hipStream_t st, const Work& k, const float* const* w_coarse, const float* const* w_fine, const Run& c,
+                 void* stream) {
+  if (c.chain) {
+    // the weights are re-packed every iteration: a run whose weights drift beyond what the split-fp16 stream carries
+    // (|w| >= 1023.75, or NaN) raises NSR_FLAG_WEIGHT_RANGE in the step's status word, like nsr_pack_weights does.
+    // Round 6: both networks per launch (6 launches -> 3), and the backward pack also clears the loss carries and writes
+    // word 1 of the status block = the colour-head option word the TRAIN instantiation of the forward kernel reads (the
+    // blob tail's layout, nsr_common.h; written every call, so a workspace that was never reset cannot switch an option on)
+    NSR_TRY(nsr_check_weights_range2(w_coarse, w_fine, NSR_F16X3, k.status, stream));
+    NSR_TRY(nsr_f16x3_pack2(w_coarse, k.stream_f[0], w_fine, k.stream_f[1], stream));
+    NSR_TRY(nsr_chain_bwd_pack2(w_coarse, k.stream_b[0], w_fine, k.stream_b[1], (c.flags & NSR_TRAIN_STOP_GRAD) != 0,
+                                chain_bwd_terms(c.precision), k.carry, 8, k.status + 1,
+                                (c.flags & NSR_TRAIN_COLOR_NONE) ? kOptColorNone : 0u, stream));
+  } else {
+    NSR_TRY(prepare_weights(st, w_coarse, k.pack[0], gemm_precision(c.precision)));
+    NSR_TRY(prepare_weights(st, w_fine, k.pack[1], gemm_precision(c.precision)));
+    if (hipMemsetAsync(k.carry, 0, 8 * sizeof(double), st) != hipSuccess) return NSR_ERR_LAUNCH;
+  }
+  return NSR_OK;
+}
+
+// forward half of the pass of network `net` over the rays [r0, r0 + rc): stratified samples (coarse) or inverse-CDF samples
+// from the detached coarse weights w_c over z_c (fine) into z, the network (what its backward reads stays in k's buffers),
+// density noise, --gamma_correct, compositing.  u / noise: the call's whole draws; comp / depth / opac / wts: this pass's rows
+// of the outputs (all but comp may be null)
+int pass_forward(hipStream_t st, const Work& k, const Run& c, int net, const float* const* w, const float* rays, int64_t r0,
+                 int64_t rc, const float* u, const float* noise, const float* z_c, const float* w_c, float* z, float* comp,
+                 float* depth, float* opac, float* wts, void* stream) {
+  const int N = net ? c.nc + c.ni : c.nc;
+  const int64_t P = rc * N;
+  const float* rays_c = rays + r0 * c.ray_stride;
+  if (net == 0) {
+    NSR_TRY(nsr_sample_along_rays(rays_c, c.ray_stride, rc, c.nc, c.lindisp, u ? u + r0 * c.nc : nullptr, z, nullptr, stream));
+  } else {
+    NSR_TRY(nsr_resample_along_rays(rays_c, c.ray_stride, z_c, w_c, rc, c.nc, c.ni, u ? u + r0 * c.ni : nullptr, z, nullptr,
+                                    stream));
+  }
+  if (c.chain) {   // the chain path encodes inside its forward kernel
+    NSR_TRY(nsr_f16x3_train_forward(k.stream_f[net], rays_c, c.ray_stride, z, rc, N, k.rgb, k.zpan, k.sgn, k.status, stream));
+  } else {
+    hipLaunchKernelGGL(encode_train_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, rays_c, c.ray_stride, z, P, N,
+                       k.x5, k.gs);
+    NSR_CHECK_LAUNCH();
+    NSR_TRY(net_forward(st, w, k.pack[net], k, P, gemm_precision(c.precision), (c.flags & NSR_TRAIN_COLOR_NONE) != 0));
+  }
+  hipLaunchKernelGGL(sigma_noise_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st,
+                     c.chain ? k.rgb + 3 : k.gs + kSigmaCol, c.chain ? 4 : kGs, (c.noise_std > 0.0f && noise) ? noise + r0 * N : nullptr,
+                     c.noise_std, P, k.sig);
+  NSR_CHECK_LAUNCH();
+  if (c.flags & NSR_TRAIN_GAMMA_CORRECT) {   // render_rays: out_rgbs = pow(out_rgbs, 1 / 2.2) per sample, in training too (nerf_downX_model.py:271-276)
+    hipLaunchKernelGGL(gamma_points_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, k.rgb, P);
+    NSR_CHECK_LAUNCH();
+  }
+  return nsr_composite(k.rgb, 4, k.sig, 1, z, rc, N, c.flags & (NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS), comp, depth, opac, wts, stream);
+}
+
+// backward half of the same pass, from the upstream gradients of its outputs (this pass's rows; g_comp required, the others
+// may be null): compositing backward, then the chain kernels or the layer-by-layer GEMMs.  g: the network's 24 gradient
+// tensors, overwritten (acc = 0) or accumulated
+int pass_backward(hipStream_t st, const Work& k, const Run& c, int net, const float* const* w, int64_t rc, const float* z,
+                  const float* g_comp, const float* g_depth, const float* g_opacity, const float* g_weights, float* const* g,
+                  int acc, void* stream) {
+  const int N = net ? c.nc + c.ni : c.nc;
+  const int64_t P = rc * N;
+  NSR_TRY(composite_bwd(st, k, z, g_comp, rc, N, c.flags, c.chain, g_depth, g_opacity, g_weights));
+  if (c.chain) {
+    NSR_TRY(nsr_chain_bwd(k.stream_b[net], k.sgn, k.dpan, k.d4, 4, k.d4 + 3, 4, P, k.gmax, k.pscale, chain_bwd_terms(c.precision), 1,
+                          stream));
+    return chain_weight_grads(st, k, P, rc, g, acc);
+  }
+  return net_backward(st, w, k.pack[net], k, P, g, acc, (c.flags & NSR_TRAIN_STOP_GRAD) != 0);
+}
+
+// ---- saved state of nsr_train_forward (include/nsr_train.h) ----------------------------------------------------------
+// [header: 256 bytes][chain path: backward weight streams of both networks][chunk 0: coarse pass, fine pass][chunk 1: ...]
+// A pass region holds what pass_backward reads besides the weights: (rgb, sigma) and the noisy sigma, z, and either the
+// forward kernel's activation panels + sign words (chain path) or the per-layer activations (GEMM path).  Every region is
+// sized for a full chunk.
+struct SavedPass {
+  float *x5, *h[9], *gs, *cc, *rgb, *sig, *z;
+  char* zpan;
+  unsigned* sgn;
+};
+int64_t saved_pass_floats(int64_t chunk, int N, bool chain, SavedPass* s, float* base) {
+  const int64_t P = chunk * N;
+  int64_t off = 0;
+  auto take_if = [&](bool on, int64_t n) -> float* {
+    if (!on) return nullptr;
+    float* p = base ? base + off : nullptr;
+    off += align64(n);
+    return p;
+  };
+  SavedPass tmp;
+  SavedPass& q = s ? *s : tmp;
+  q.x5 = take_if(!chain, P * kX5);
+  for (int L = 0; L <= 8; ++L) q.h[L] = (L == 0 || L == 4) ? nullptr : take_if(!chain, P * kW);   // h4 lives in x5[:, 64:]
+  q.gs = take_if(!chain, P * kGs);
+  q.cc = take_if(!chain, P * kDirOut);
+  q.rgb = take_if(true, P * 4);
+  q.sig = take_if(true, P);
+  q.z = take_if(true, P);
+  q.zpan = reinterpret_cast<char*>(take_if(chain, nsr_f16x3_train_panel_bytes(P) / 4));
+  q.sgn = reinterpret_cast<unsigned*>(take_if(chain, nsr_f16x3_train_sign_words(P)));
+  return off;
+}
+void use_saved(Work& k, const SavedPass& s) {
+  k.x5 = s.x5;
+  for (int L = 1; L <= 8; ++L) k.h[L] = s.h[L];
+  k.gs = s.gs; k.cc = s.cc; k.rgb = s.rgb; k.sig = s.sig; k.zpan = s.zpan; k.sgn = s.sgn;
+}
+constexpr uint64_t kSavedMagic = 0x31564153525343ull;   // "CSRSAV1": format of this header and layout
+constexpr int64_t kSavedHeaderFloats = 64;
+struct SavedHeader {
+  uint64_t magic, floats;   // floats: the layout's total, checked against the arguments read back
+  int64_t R, chunk;
+  int nc, ni, flags, precision;
+};
+static_assert(sizeof(SavedHeader) <= kSavedHeaderFloats * 4, "header");
+struct SavedLayout {
+  int64_t stream, pass_c, pass_f, n_chunks, total;   // floats
+};
+SavedLayout saved_layout(int precision, int64_t R, int nc, int ni, int64_t chunk) {
+  const bool chain = chain_selected(precision);
+  SavedLayout L;
+  L.stream = chain ? align64((int64_t)(nsr_chain_bwd_packed_bytes() / 4)) : 0;
+  L.pass_c = saved_pass_floats(chunk, nc, chain, nullptr, nullptr);
+  L.pass_f = saved_pass_floats(chunk, nc + ni, chain, nullptr, nullptr);
+  L.n_chunks = (R + chunk - 1) / chunk;
+  L.total = kSavedHeaderFloats + 2 * L.stream + L.n_chunks * (L.pass_c + L.pass_f);
+  return L;
+}
+float* saved_stream(float* base, const SavedLayout& L, int net) { return base + kSavedHeaderFloats + net * L.stream; }
+float* saved_pass(float* base, const SavedLayout& L, int64_t chunk_index, int net) {
+  return base + kSavedHeaderFloats + 2 * L.stream + chunk_index * (L.pass_c + L.pass_f) + (net ? L.pass_c : 0);
+}
+// the header is written on the stream (the call enqueues, it does not wait) and read back by nsr_train_backward
+__global__ void saved_header_kernel(SavedHeader h, unsigned* __restrict__ dst) {
+  const unsigned* src = reinterpret_cast<const unsigned*>(&h);
+  const int i = threadIdx.x;
+  if (i < (int)(sizeof(SavedHeader) / 4)) dst[i] = src[i];
 }
 
 }  // namespace
@@ -1053,96 +1250,39 @@ int train_impl(const float* const* w_coarse, const float* const* w_fine, float* 
   // torch.var over ONE sub-ray is 0 / 0 (the reference would train on NaN); a depth variance needs the divisor
   if ((rgb_var || depth_var) && s2 < 2) return NSR_ERR_INVALID_ARG;
   if (depth_var && !(var->far > 0.0f)) return NSR_ERR_INVALID_ARG;
-  if (n_coarse < 2 || n_importance < 1 || n_coarse + n_importance > 256) return NSR_ERR_UNSUPPORTED;
-  if (!train_precision_ok(precision)) return NSR_ERR_UNSUPPORTED;
-  if (R % s2 != 0) return NSR_ERR_INVALID_ARG;
-  if (ray_chunk <= 0 || ray_chunk > R) ray_chunk = R;
-  if (ray_chunk % s2 != 0) return NSR_ERR_INVALID_ARG;
-  // the split-K weight-gradient GEMM contracts over the chunk's sample points in K tiles of 32: every chunk,
-  // the shorter last one included, must hold a multiple of 32 points in both passes -- checked BEFORE anything
-  // is enqueued, so a rejected call leaves outputs and gradients untouched
-  for (int64_t r0 = 0; r0 < R; r0 += ray_chunk) {
-    const int64_t rc = (R - r0 < ray_chunk) ? R - r0 : ray_chunk;
-    if ((rc * n_coarse) % 32 != 0 || (rc * (n_coarse + n_importance)) % 32 != 0) return NSR_ERR_UNSUPPORTED;
-  }
+  NSR_TRY(check_shape(R, s2, n_coarse, n_importance, precision, ray_chunk));
   for (int i = 0; i < NSR_N_STATE_TENSORS; ++i)
     if (!w_coarse[i] || !w_fine[i] || !g_coarse[i] || !g_fine[i]) return NSR_ERR_INVALID_ARG;
   if (R == 0) return NSR_OK;
   if (!rays || !target_lr || !outs[0] || !outs[4] || !lr_coarse || !lr_fine || !losses || !workspace)
     return NSR_ERR_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return NSR_ERR_INVALID_ARG;
-  // the step's option word (include/nsr_train.h): the renderer's two bits + the colour head's two
-  constexpr int kTrainOpts = NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS | NSR_TRAIN_GAMMA_CORRECT | NSR_TRAIN_COLOR_NONE | NSR_TRAIN_STOP_GRAD;
-  if ((white_bkgd & ~kTrainOpts) != 0) return NSR_ERR_INVALID_ARG;
-  const int gamma = (white_bkgd & NSR_TRAIN_GAMMA_CORRECT) != 0, color_none = (white_bkgd & NSR_TRAIN_COLOR_NONE) != 0;
-  const int stop_grad = (white_bkgd & NSR_TRAIN_STOP_GRAD) != 0;
-  if (gamma && color_none) return NSR_ERR_UNSUPPORTED;   // pow(x, 1 / 2.2) of an unbounded head: NaN for every negative value
+  NSR_TRY(check_flags(white_bkgd));
   if (workspace_bytes < nsr_train_workspace_bytes_for(precision, ray_chunk, n_coarse, n_importance)) return NSR_ERR_WORKSPACE;
-  const bool noisy = noise_std > 0.0f;
   hipStream_t st = nsr_stream(stream);
+  const Run c{R, ray_chunk, n_coarse, n_importance, white_bkgd, precision, lindisp, ray_stride, noise_std, chain_selected(precision)};
   Work k;
-  work_floats(ray_chunk, n_coarse, n_importance, &k, static_cast<float*>(workspace), chain_selected(precision) ? 2 : 1);
-  const int nc = n_coarse, nf = n_coarse + n_importance;
+  work_floats(ray_chunk, n_coarse, n_importance, &k, static_cast<float*>(workspace), c.chain ? 2 : 1);
+  const int nc = n_coarse;
   const int64_t n_lr_total = R / s2;
   const double mse_scale = 1.0 / (3.0 * (double)n_lr_total);
-
-  const bool chain = chain_selected(precision);
-  if (chain) {
-    // the weights are re-packed every iteration: a run whose weights drift beyond what the split-fp16 stream carries
-    // (|w| >= 1023.75, or NaN) raises NSR_FLAG_WEIGHT_RANGE in the step's status word, like nsr_pack_weights does.
-    // Round 6: both networks per launch (6 launches -> 3), and the backward pack also clears the loss carries and writes
-    // word 1 of the status block = the colour-head option word the TRAIN instantiation of the forward kernel reads (the
-    // blob tail's layout, nsr_common.h; written every call, so a workspace that was never reset cannot switch an option on)
-    NSR_TRY(nsr_check_weights_range2(w_coarse, w_fine, NSR_F16X3, k.status, stream));
-    NSR_TRY(nsr_f16x3_pack2(w_coarse, k.stream_f[0], w_fine, k.stream_f[1], stream));
-    NSR_TRY(nsr_chain_bwd_pack2(w_coarse, k.stream_b[0], w_fine, k.stream_b[1], stop_grad, chain_bwd_terms(precision), k.carry, 8,
-                                k.status + 1, color_none ? kOptColorNone : 0u, stream));
-  } else {
-    NSR_TRY(prepare_weights(st, w_coarse, k.pack[0], gemm_precision(precision)));
-    NSR_TRY(prepare_weights(st, w_fine, k.pack[1], gemm_precision(precision)));
-    if (hipMemsetAsync(k.carry, 0, 8 * sizeof(double), st) != hipSuccess) return NSR_ERR_LAUNCH;
-  }
+  NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream));
 
   for (int64_t r0 = 0; r0 < R; r0 += ray_chunk) {
     const int64_t rc = (R - r0 < ray_chunk) ? R - r0 : ray_chunk;
     const int acc = r0 > 0;
-    const float* rays_c = rays + r0 * ray_stride;
     const int64_t lr0 = r0 / s2, n_lr = rc / s2;
     for (int net = 0; net < 2; ++net) {
-      const int N = net ? nf : nc;
-      const int64_t P = rc * N;
+      const int N = net ? nc + n_importance : nc;
       const float* const* w = net ? w_fine : w_coarse;
       float* const* g = net ? g_fine : g_coarse;
       float* z = net ? k.z_f : k.z_c;
-      if (net == 0) {
-        NSR_TRY(nsr_sample_along_rays(rays_c, ray_stride, rc, nc, lindisp, u_coarse ? u_coarse + r0 * nc : nullptr, z,
-                                      nullptr, stream));
-      } else {
-        const float* wc = outs[3] ? outs[3] + r0 * nc : k.w_c;
-        NSR_TRY(nsr_resample_along_rays(rays_c, ray_stride, k.z_c, wc, rc, nc, n_importance,
-                                        u_fine ? u_fine + r0 * n_importance : nullptr, z, nullptr, stream));
-      }
-      if (!chain) {   // the chain path encodes inside its forward kernel
-        hipLaunchKernelGGL(encode_train_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, rays_c, ray_stride, z,
-                           P, N, k.x5, k.gs);
-        NSR_CHECK_LAUNCH();
-      }
-      if (chain) NSR_TRY(nsr_f16x3_train_forward(k.stream_f[net], rays_c, ray_stride, z, rc, N, k.rgb, k.zpan, k.sgn, k.status, stream));
-      else NSR_TRY(net_forward(st, w, k.pack[net], k, P, gemm_precision(precision), color_none));
-      const float* noise = net ? noise_fine : noise_coarse;
-      hipLaunchKernelGGL(sigma_noise_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st,
-                         chain ? k.rgb + 3 : k.gs + kSigmaCol, chain ? 4 : kGs, (noisy && noise) ? noise + r0 * N : nullptr,
-                         noise_std, P, k.sig);
-      NSR_CHECK_LAUNCH();
       float* comp = outs[4 * net + 0] + r0 * 3;
       float* depth = outs[4 * net + 1] ? outs[4 * net + 1] + r0 : (depth_var ? k.scratch_out : nullptr);   // the depth-variance loss reads it
       float* opac = outs[4 * net + 2] ? outs[4 * net + 2] + r0 : nullptr;
       float* wts = outs[4 * net + 3] ? outs[4 * net + 3] + r0 * N : (net ? nullptr : k.w_c);
-      if (gamma) {   // render_rays: out_rgbs = pow(out_rgbs, 1 / 2.2) per sample, in training too (nerf_downX_model.py:271-276)
-        hipLaunchKernelGGL(gamma_points_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, k.rgb, P);
-        NSR_CHECK_LAUNCH();
-      }
-      NSR_TRY(nsr_composite(k.rgb, 4, k.sig, 1, z, rc, N, white_bkgd & (NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS), comp, depth, opac, wts, stream));
+      NSR_TRY(pass_forward(st, k, c, net, w, rays, r0, rc, net ? u_fine : u_coarse, net ? noise_fine : noise_coarse, k.z_c,
+                           outs[3] ? outs[3] + r0 * nc : k.w_c, z, comp, depth, opac, wts, stream));
       // s^2 mean, loss, dL/d(comp)
       const float lambda = net ? lambda_fine : lambda_coarse;
       const int nblk = (int)((n_lr + 255) / 256);
@@ -1155,18 +1295,117 @@ int train_impl(const float* const* w_coarse, const float* const* w_fine, float* 
       hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, k.block_sums, nblk, mse_scale, lambda, losses, net,
                          k.carry, l_var, l_dvar, var_losses);
       NSR_CHECK_LAUNCH();
-      NSR_TRY(composite_bwd(st, k, z, rc, N, white_bkgd, chain, depth_var ? k.g_depth : nullptr));
-      if (chain) {
-        NSR_TRY(nsr_chain_bwd(k.stream_b[net], k.sgn, k.dpan, k.d4, 4, k.d4 + 3, 4, P, k.gmax, k.pscale, chain_bwd_terms(precision), 1, stream));
-        NSR_TRY(chain_weight_grads(st, k, P, rc, g, acc));
-      } else {
-        NSR_TRY(net_backward(st, w, k.pack[net], k, P, g, acc, stop_grad));
-      }
+      NSR_TRY(pass_backward(st, k, c, net, w, rc, z, k.g_comp, depth_var ? k.g_depth : nullptr, nullptr, nullptr, g, acc, stream));
     }
   }
   return NSR_OK;
 }
 }  // namespace
+
+extern "C" size_t nsr_train_saved_bytes(int precision, int64_t R, int n_coarse, int n_importance, int64_t ray_chunk) {
+  if (R <= 0 || check_shape(R, 1, n_coarse, n_importance, precision, ray_chunk) != NSR_OK) return 0;
+  return (size_t)saved_layout(precision, R, n_coarse, n_importance, ray_chunk).total * sizeof(float);
+}
+
+extern "C" int nsr_train_forward(const float* const* w_coarse, const float* const* w_fine, const float* rays, int ray_stride,
+                                 int64_t R, int n_coarse, int n_importance, int render_flags, int lindisp,
+                                 const float* u_coarse, const float* u_fine, const float* noise_coarse, const float* noise_fine,
+                                 float noise_std, int precision, int64_t ray_chunk, float* const* outs, void* workspace,
+                                 size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream) {
+  if (!w_coarse || !w_fine || !outs || R < 0 || !nsr_ray_stride_ok(ray_stride)) return NSR_ERR_INVALID_ARG;
+  NSR_TRY(check_shape(R, 1, n_coarse, n_importance, precision, ray_chunk));
+  for (int i = 0; i < NSR_N_STATE_TENSORS; ++i)
+    if (!w_coarse[i] || !w_fine[i]) return NSR_ERR_INVALID_ARG;
+  if (R == 0) return NSR_OK;
+  if (!rays || !outs[0] || !outs[4] || !workspace || !saved) return NSR_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0 || (reinterpret_cast<uintptr_t>(saved) & 255) != 0) return NSR_ERR_INVALID_ARG;
+  NSR_TRY(check_flags(render_flags));
+  if (workspace_bytes < nsr_train_workspace_bytes_for(precision, ray_chunk, n_coarse, n_importance)) return NSR_ERR_WORKSPACE;
+  const SavedLayout L = saved_layout(precision, R, n_coarse, n_importance, ray_chunk);
+  if (saved_bytes < (size_t)L.total * sizeof(float)) return NSR_ERR_WORKSPACE;
+  hipStream_t st = nsr_stream(stream);
+  const Run c{R, ray_chunk, n_coarse, n_importance, render_flags, precision, lindisp, ray_stride, noise_std, chain_selected(precision)};
+  Work k;
+  work_floats(ray_chunk, n_coarse, n_importance, &k, static_cast<float*>(workspace), c.chain ? 2 : 1);
+  float* sv = static_cast<float*>(saved);
+  if (c.chain)   // the backward weight streams are packed into the saved state: the backward call uses them as they are
+    for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
+  const SavedHeader h{kSavedMagic, (uint64_t)L.total, R, ray_chunk, n_coarse, n_importance, render_flags, precision};
+  hipLaunchKernelGGL(saved_header_kernel, dim3(1), dim3(64), 0, st, h, reinterpret_cast<unsigned*>(sv));
+  NSR_CHECK_LAUNCH();
+  NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream));
+  for (int64_t r0 = 0, ci = 0; r0 < R; r0 += ray_chunk, ++ci) {
+    const int64_t rc = (R - r0 < ray_chunk) ? R - r0 : ray_chunk;
+    SavedPass s[2];
+    for (int net = 0; net < 2; ++net) {
+      const int N = net ? n_coarse + n_importance : n_coarse;
+      saved_pass_floats(ray_chunk, N, c.chain, &s[net], saved_pass(sv, L, ci, net));
+      use_saved(k, s[net]);
+      float* depth = outs[4 * net + 1] ? outs[4 * net + 1] + r0 : nullptr;
+      float* opac = outs[4 * net + 2] ? outs[4 * net + 2] + r0 : nullptr;
+      float* wts = outs[4 * net + 3] ? outs[4 * net + 3] + r0 * N : (net ? nullptr : k.w_c);
+      NSR_TRY(pass_forward(st, k, c, net, net ? w_fine : w_coarse, rays, r0, rc, net ? u_fine : u_coarse,
+                           net ? noise_fine : noise_coarse, s[0].z, outs[3] ? outs[3] + r0 * n_coarse : k.w_c, s[net].z,
+                           outs[4 * net] + r0 * 3, depth, opac, wts, stream));
+    }
+  }
+  return NSR_OK;
+}
+
+extern "C" int nsr_train_backward(const float* const* w_coarse, const float* const* w_fine, const float* const* g_outs,
+                                  float* const* g_coarse, float* const* g_fine, void* workspace, size_t workspace_bytes,
+                                  const void* saved, size_t saved_bytes, void* stream) {
+  if (!w_coarse || !w_fine || !g_outs || !g_coarse || !g_fine || !workspace || !saved) return NSR_ERR_INVALID_ARG;
+  for (int i = 0; i < NSR_N_STATE_TENSORS; ++i)
+    if (!w_coarse[i] || !w_fine[i] || !g_coarse[i] || !g_fine[i]) return NSR_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0 || (reinterpret_cast<uintptr_t>(saved) & 255) != 0) return NSR_ERR_INVALID_ARG;
+  if (saved_bytes < (size_t)kSavedHeaderFloats * sizeof(float)) return NSR_ERR_WORKSPACE;
+  // the run's parameters, read back from the header the forward call wrote (waits for the stream)
+  hipStream_t st = nsr_stream(stream);
+  SavedHeader h{};
+  if (hipMemcpyAsync(&h, saved, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) return NSR_ERR_LAUNCH;
+  if (hipStreamSynchronize(st) != hipSuccess) return NSR_ERR_LAUNCH;
+  if (h.magic != kSavedMagic) return NSR_ERR_INVALID_ARG;
+  if (h.floats > saved_bytes / sizeof(float)) return NSR_ERR_WORKSPACE;   // the header says the state is larger than the buffer
+  // bounds before anything loops over them (a damaged header may hold anything): every ray and every chunk takes at least
+  // 64 floats of the layout, so neither count can exceed what the buffer holds
+  if (h.R <= 0 || h.chunk <= 0 || h.chunk > h.R || (uint64_t)h.R > h.floats / 64 ||
+      (uint64_t)((h.R + h.chunk - 1) / h.chunk) > h.floats / 64)
+    return NSR_ERR_INVALID_ARG;
+  int64_t chunk = h.chunk;
+  if (check_shape(h.R, 1, h.nc, h.ni, h.precision, chunk) != NSR_OK || chunk != h.chunk || check_flags(h.flags) != NSR_OK)
+    return NSR_ERR_INVALID_ARG;
+  const SavedLayout L = saved_layout(h.precision, h.R, h.nc, h.ni, h.chunk);
+  if ((uint64_t)L.total != h.floats) return NSR_ERR_INVALID_ARG;
+  if (workspace_bytes < nsr_train_workspace_bytes_for(h.precision, h.chunk, h.nc, h.ni)) return NSR_ERR_WORKSPACE;
+  const Run c{h.R, h.chunk, h.nc, h.ni, h.flags, h.precision, 0, 8, 0.0f, chain_selected(h.precision)};
+  Work k;
+  work_floats(c.chunk, c.nc, c.ni, &k, static_cast<float*>(workspace), c.chain ? 2 : 1);
+  float* sv = const_cast<float*>(static_cast<const float*>(saved));   // read only
+  if (c.chain) {
+    for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
+  } else {   // the padded weight copies the layer-by-layer backward reads (deterministic: the forward call's own)
+    NSR_TRY(prepare_weights(st, w_coarse, k.pack[0], gemm_precision(c.precision)));
+    NSR_TRY(prepare_weights(st, w_fine, k.pack[1], gemm_precision(c.precision)));
+  }
+  // the fused step's order: chunk by chunk, coarse then fine; chunk 0 overwrites the gradients, later chunks accumulate
+  for (int64_t r0 = 0, ci = 0; r0 < c.R; r0 += c.chunk, ++ci) {
+    const int64_t rc = (c.R - r0 < c.chunk) ? c.R - r0 : c.chunk;
+    for (int net = 0; net < 2; ++net) {
+      const int N = net ? c.nc + c.ni : c.nc;
+      SavedPass s;
+      saved_pass_floats(c.chunk, N, c.chain, &s, saved_pass(sv, L, ci, net));
+      use_saved(k, s);
+      const float* const* go = g_outs + 4 * net;
+      const float* g_comp = go[0] ? go[0] + r0 * 3 : k.g_comp;
+      if (!go[0] && hipMemsetAsync(k.g_comp, 0, (size_t)rc * 3 * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
+      NSR_TRY(pass_backward(st, k, c, net, net ? w_fine : w_coarse, rc, s.z, g_comp, go[1] ? go[1] + r0 : nullptr,
+                            go[2] ? go[2] + r0 : nullptr, go[3] ? go[3] + r0 * N : nullptr, net ? g_fine : g_coarse, r0 > 0,
+                            stream));
+    }
+  }
+  return NSR_OK;
+}
 
 extern "C" int nsr_train_loss_and_grads(const float* const* w_coarse, const float* const* w_fine, float* const* g_coarse,
                                         float* const* g_fine, const float* rays, int ray_stride, int64_t R, int s2,

@@ -10,6 +10,13 @@ the reference's call protocol:
 All arithmetic runs in libnsr.so (``nsr_train_loss_and_grads``, ``nsr_adam_step``); torch supplies device memory,
 the stream and the random draws (``torch.rand`` / ``torch.randn`` on the device, exactly the four tensors the
 reference draws).  There is no CPU path.
+
+For losses the fused step does not compute (``regularize_patch``'s TV loss, ``--sisr_path``, ``--with_ref``, gradient
+clipping, anything written in torch), ``forward_rays_train`` is train-mode ``forward_rays`` as a ``torch.autograd.Function``
+over ``nsr_train_forward`` / ``nsr_train_backward`` -- the same kernels, split at the loss -- and ``Trainer.forward`` /
+``Trainer.backward`` / ``Trainer.regularize_patch`` / ``Trainer.clip_grads`` drive it with the trainer's own tensors:
+
+    out = t.forward(); loss = my_loss(out); t.backward(loss); t.clip_grads(); t.optimizer_step()
 """
 from __future__ import annotations
 
@@ -18,6 +25,7 @@ from typing import Dict, Optional
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .ops import _f32, _p, _ray_stride, _stream
@@ -68,6 +76,163 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, a
     return (y, yt) if transposed else y
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# train-mode forward_rays as a torch.autograd.Function (nsr_train_forward / nsr_train_backward)
+# ---------------------------------------------------------------------------------------------------------------------
+class TrainWorkspace:
+    """The training workspace: scratch of one pass + the sticky numerics status block at its start (include/nsr_train.h).
+    Any number of pending forwards share it (each keeps its own saved state); it grows on demand and keeps its flags."""
+
+    def __init__(self):
+        self.buf: Optional[torch.Tensor] = None
+
+    def get(self, need: int, device) -> torch.Tensor:
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:      # "cuda" (Trainer's default) is the current device
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.buf is None or self.buf.numel() < need or self.buf.device != device:
+            carried = self.status() if self.buf is not None else 0     # a regrown workspace keeps the sticky flags (ADVICE r4)
+            self.buf = torch.empty(need, dtype=torch.uint8, device=device)
+            _lib.check(_lib.load().nsr_train_status_reset(_p(self.buf), _stream()), "nsr_train_status_reset")
+            if carried:
+                self.buf[:4].copy_(torch.tensor([carried], dtype=torch.int32).view(torch.uint8))
+        return self.buf
+
+    def status(self, clear: bool = False) -> int:
+        if self.buf is None:
+            return 0
+        import ctypes
+        flags = ctypes.c_uint(0)
+        _lib.check(_lib.load().nsr_train_status(_p(self.buf), int(bool(clear)), ctypes.byref(flags), _stream()), "nsr_train_status")
+        return int(flags.value)
+
+
+_DEFAULT_WS: Dict[torch.device, TrainWorkspace] = {}
+
+
+def _weights24(params, name: str):
+    """A network's 24 tensors in state_dict order: a dict keyed like STATE_DICT_SPEC, an nn.Module (``parameters()`` has the
+    state_dict's order), or a sequence of 24 tensors."""
+    if isinstance(params, torch.nn.Module):
+        ts = list(params.parameters())
+    elif isinstance(params, dict):
+        ts = [params[k] for k in STATE_DICT_SPEC]
+    else:
+        ts = list(params)
+    if len(ts) != len(STATE_DICT_SPEC):
+        raise ValueError(f"{name}: expected {len(STATE_DICT_SPEC)} tensors, got {len(ts)}")
+    for i, (t, (k, shape)) in enumerate(zip(ts, STATE_DICT_SPEC.items())):
+        _f32(t, f"{name}.{k}")
+        if k == DIR_W and tuple(t.shape) == (shape[0], shape[1] - 27):
+            # --no_dir (models/networks.py:160-169): the narrow layer with 27 zero columns (weights.pad_no_dir, as Trainer
+            # holds it); the padding is a constant, so autograd hands the narrow weight the gradient of its 256 columns
+            ts[i] = t = pad_no_dir(t)
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: {k} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return [t if t.is_contiguous() else t.contiguous() for t in ts]
+
+
+class _TrainRun:
+    """The arguments of one forward_rays_train call that are not tensors."""
+
+    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace):
+        self.nc, self.ni, self.flags, self.lindisp = nc, ni, flags, lindisp
+        self.noise_std, self.prec, self.chunk, self.workspace = noise_std, prec, chunk, workspace
+
+
+class _ForwardRaysTrain(torch.autograd.Function):
+    """Outputs: the eight OUT_KEYS tensors.  Inputs: the run, rays, the four draws, then the 48 weight tensors."""
+
+    @staticmethod
+    def forward(ctx, run, rays, u_c, u_f, n_c, n_f, *weights):
+        lib = _lib.load()
+        R, nc, ni = rays.shape[0], run.nc, run.ni
+        dev = rays.device
+        outs = [torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, nc, device=dev),
+                torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, nc + ni, device=dev)]
+        nbytes = lib.nsr_train_saved_bytes(run.prec, R, nc, ni, run.chunk)
+        if nbytes == 0:
+            raise _lib.NsrError(f"nsr_train_saved_bytes: no saved state for R={R}, samples {nc} + {ni}, ray_chunk {run.chunk} "
+                                "(every ray chunk must hold a multiple of 32 sample points in both networks)")
+        saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ctx.ws_need = lib.nsr_train_workspace_bytes_for(run.prec, run.chunk if 0 < run.chunk < R else R, nc, ni)
+        ws = run.workspace.get(ctx.ws_need, dev)
+        _lib.check(lib.nsr_train_forward(
+            _ptr_array(weights[:24]), _ptr_array(weights[24:]), _p(rays), _ray_stride(rays), R, nc, ni, run.flags, run.lindisp,
+            _p(u_c), _p(u_f), _p(n_c), _p(n_f), run.noise_std, run.prec, run.chunk, _ptr_array(outs),
+            _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()), "nsr_train_forward")
+        ctx.save_for_backward(*weights)      # an in-place update of a weight before the backward fails autograd's version check
+        ctx.run, ctx.state = run, saved
+        ctx.set_materialize_grads(False)     # an output the loss does not use arrives as None: a NULL upstream gradient
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *g_outs):
+        weights = ctx.saved_tensors
+        saved = ctx.state
+        if saved is None:
+            raise RuntimeError("forward_rays_train: the saved state of this forward was released by its first backward")
+        lib = _lib.load()
+        g_outs = [None if g is None else g.to(torch.float32).contiguous() for g in g_outs]
+        grads = [torch.empty_like(w) for w in weights]
+        ws = ctx.run.workspace.get(ctx.ws_need, saved.device)
+        _lib.check(lib.nsr_train_backward(
+            _ptr_array(weights[:24]), _ptr_array(weights[24:]), (c_void_p * 8)(*[_p(g) for g in g_outs]),
+            _ptr_array(grads[:24]), _ptr_array(grads[24:]), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
+            "nsr_train_backward")
+        ctx.state = None
+        return (None,) * 6 + tuple(grads)
+
+
+def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[Dict[str, Optional[torch.Tensor]]] = None, *,
+                       N_coarse: int = 64, N_importance: int = 64, white_bkgd: bool = False, lindisp: bool = False,
+                       noise_std: float = 0.0, gamma_correct: bool = False, sigma_activation: str = "relu",
+                       color_activation: str = "sigmoid", stop_grad: bool = False, precision: str = "f16x3",
+                       ray_chunk: int = 0, workspace: Optional[TrainWorkspace] = None) -> Dict[str, torch.Tensor]:
+    """Train-mode ``forward_rays`` (``models/nerf_downX_model.py:280-313``) that autograd differentiates with respect to the
+    24 + 24 weight tensors of ``params_c`` / ``params_f`` (the reference's ``netCoarse`` / ``netFine`` modules, their
+    parameter lists, or state-dict-like dicts such as ``Trainer.params``).  Returns the eight ``OUT_KEYS`` outputs; any loss
+    written in torch over them back-propagates through ``nsr_train_backward`` (once: the backward is not differentiable).
+
+    ``draws``: ``u_coarse`` (R, Nc), ``u_fine`` (R, Ni), ``noise_coarse`` (R, Nc), ``noise_fine`` (R, Nc + Ni) on the device,
+    or None for the deterministic branch of that stage (``Trainer.draw`` makes them in the reference's order).  ``ray_chunk``:
+    rays per pass (0 = all).  Every call keeps its own saved state (5.4 KB per sample point under 'f16x3', include/nsr_train.h)
+    until its backward; ``workspace`` (shared scratch + the sticky status block) defaults to one per device."""
+    if rays.requires_grad:
+        raise ValueError("forward_rays_train: rays must not require grad (there is no gradient with respect to rays)")
+    rays = _f32(rays, "rays")
+    _ray_stride(rays)
+    if precision not in _lib.TRAIN_PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(_lib.TRAIN_PRECISIONS)}")
+    if sigma_activation not in ("relu", "softplus") or color_activation not in ("sigmoid", "none"):
+        raise ValueError("sigma_activation: 'relu' or 'softplus'; color_activation: 'sigmoid' or 'none'")
+    wc, wf = _weights24(params_c, "params_c"), _weights24(params_f, "params_f")
+    for t in wc + wf:
+        if t.device != rays.device:
+            raise ValueError("the weights must live on the rays' device")
+    draws = draws or {}
+    d = [None if draws.get(k) is None else _f32(torch.as_tensor(draws[k], device=rays.device), k)
+         for k in ("u_coarse", "u_fine", "noise_coarse", "noise_fine")]
+    flags = (_lib.NSR_WHITE_BKGD if white_bkgd else 0) | (_lib.NSR_TRAIN_GAMMA_CORRECT if gamma_correct else 0) \
+        | (_lib.NSR_SIGMA_SOFTPLUS if sigma_activation == "softplus" else 0) \
+        | (_lib.NSR_TRAIN_COLOR_NONE if color_activation == "none" else 0) | (_lib.NSR_TRAIN_STOP_GRAD if stop_grad else 0)
+    if workspace is None:
+        workspace = _DEFAULT_WS.setdefault(rays.device, TrainWorkspace())
+    run = _TrainRun(int(N_coarse), int(N_importance), flags, int(bool(lindisp)), float(noise_std),
+                    _lib.TRAIN_PRECISIONS[precision], int(ray_chunk), workspace)
+    outs = _ForwardRaysTrain.apply(run, rays, *d, *wc, *wf)
+    return dict(zip(OUT_KEYS, outs))
+
+
+def tv_loss(x: torch.Tensor) -> torch.Tensor:
+    """Total-variation loss of an (H, W, C) image as the reference's TVLoss defines it (models/criterions.py:56-69): the mean
+    squared difference of vertically adjacent pixels plus that of horizontally adjacent ones."""
+    dh = x[1:, :, :] - x[:-1, :, :]
+    dw = x[:, 1:, :] - x[:, :-1, :]
+    return dh.pow(2).sum() / dh.numel() + dw.pow(2).sum() / dw.numel()
+
+
 class Trainer:
     """Coarse + fine networks, gradients, Adam state and one-call training iterations."""
 
@@ -78,7 +243,13 @@ class Trainer:
                  precision: str = "f16x3", device="cuda", gamma_correct: bool = False,
                  use_var_loss: bool = False, lambda_coarse_var: float = 0.01, lambda_fine_var: float = 0.01,
                  use_depth_var_loss: bool = False, lambda_coarse_depth_var: float = 0.01, lambda_fine_depth_var: float = 0.01,
-                 no_dir: bool = False, sigma_activation: str = "relu", color_activation: str = "sigmoid", stop_grad: bool = False):
+                 no_dir: bool = False, sigma_activation: str = "relu", color_activation: str = "sigmoid", stop_grad: bool = False,
+                 grad_clip_val: float = 0.0, grad_clip_type: str = "norm"):
+        # --grad_clip_val / --grad_clip_type (models/nerf_downX_model.py:403-407): both networks' gradients together, between
+        # the backward and the optimiser step; 0 = off
+        if grad_clip_type not in ("norm", "value"):
+            raise ValueError("grad_clip_type: 'norm' or 'value'")
+        self.grad_clip_val, self.grad_clip_type = float(grad_clip_val), grad_clip_type
         # render_rays applies rgb ** (1 / 2.2) per sample under --gamma_correct (models/nerf_downX_model.py:271-276) in training
         # too: NSR_TRAIN_GAMMA_CORRECT of the step's option word (include/nsr_train.h)
         self.gamma_correct = bool(gamma_correct)
@@ -127,9 +298,14 @@ class Trainer:
         self.var_losses = torch.zeros(4, dtype=torch.float32, device=self.device)
         self.ray_chunk = int(ray_chunk) - int(ray_chunk) % self.s2
         self.step = 0
-        self._ws = None
+        self._workspace = TrainWorkspace()     # shared by loss_and_grads and the autograd pair (forward / backward)
+        self._leaves = None
         self.losses = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.out: Dict[str, torch.Tensor] = {}
+
+    @property
+    def _ws(self) -> Optional[torch.Tensor]:
+        return self._workspace.buf
 
     # -- reference protocol ------------------------------------------------------------------------------
     def set_input(self, rays: torch.Tensor, rgbs: torch.Tensor):
@@ -170,12 +346,7 @@ class Trainer:
         need = lib.nsr_train_workspace_bytes_for(self._prec, chunk, nc, self.N_importance)   # the buffers of the path this precision takes
         if need == 0:
             raise _lib.NsrError("sample counts outside the built path")
-        if self._ws is None or self._ws.numel() < need:
-            carried = self.status() if self._ws is not None else 0     # a regrown workspace keeps the sticky flags
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            _lib.check(_lib.load().nsr_train_status_reset(_p(self._ws), _stream()), "nsr_train_status_reset")
-            if carried:
-                self._ws[:4].copy_(torch.tensor([carried], dtype=torch.int32).view(torch.uint8))
+        self._workspace.get(need, self.device)
         dev = self.device
         o = {"coarse_comp_rgbs": torch.empty(R, 3, device=dev), "coarse_depth": torch.empty(R, device=dev),
              "coarse_opacity": torch.empty(R, device=dev), "coarse_weights": torch.empty(R, nc, device=dev),
@@ -218,6 +389,80 @@ class Trainer:
         self.out = o
         return self.losses, self.grads
 
+    # -- autograd protocol: forward() -> any loss in torch -> backward(loss) -> [clip_grads()] -> optimizer_step() ---------
+    def _weight_leaves(self):
+        """Per network 24 tensors that alias ``self.params`` and require grad (autograd leaves; they share the storage and the
+        version counter, so an in-place update of a weight between a forward and its backward is caught: a torch in-place op
+        bumps the counter itself, ``optimizer_step`` -- which writes through raw pointers -- bumps it explicitly)."""
+        if self._leaves is None:
+            self._leaves = [[p.detach().requires_grad_(True) for p in self.params[n].values()] for n in range(2)]
+        return self._leaves
+
+    def forward(self, draws: Optional[Dict[str, Optional[torch.Tensor]]] = None, rays: Optional[torch.Tensor] = None):
+        """Train-mode ``forward_rays`` of the current batch (or of ``rays``: a patch, a ``--with_ref`` batch) through the
+        autograd pair: the eight outputs, differentiable with respect to both networks' weights.  Losses of several forwards
+        may be summed before ONE ``backward``."""
+        rays = self.data_rays if rays is None else _f32(rays.reshape(-1, rays.shape[-1]), "rays")
+        if draws is None:
+            draws = self.draw(rays.shape[0])
+        draws = {k: v for k, v in draws.items() if k != "noise_std"}
+        lc, lf = self._weight_leaves()
+        return forward_rays_train(lc, lf, rays, draws, N_coarse=self.N_coarse, N_importance=self.N_importance,
+                                  white_bkgd=self.white_bkgd, lindisp=self.lindisp, noise_std=self.noise_std,
+                                  gamma_correct=self.gamma_correct, sigma_activation=self.sigma_activation,
+                                  color_activation=self.color_activation, stop_grad=self.stop_grad, precision=self.precision,
+                                  ray_chunk=self.ray_chunk, workspace=self._workspace)
+
+    def backward(self, loss: torch.Tensor):
+        """d(loss)/d(weights) of the forwards behind ``loss`` into ``self.grads`` / ``self.flat_grads`` (OVERWRITTEN; scaled by
+        1 / world like ``loss_and_grads``, see ``grad_scale``), where ``all_reduce_grads`` and ``optimizer_step`` find them.
+        A weight the loss does not reach gets a zero gradient."""
+        from .dist import _world
+        gs = float(self.grad_scale) if self.grad_scale is not None else 1.0 / _world(self.group)[1]
+        leaves = self._weight_leaves()
+        flat = leaves[0] + leaves[1]
+        grads = torch.autograd.grad(loss, flat, grad_outputs=None if gs == 1.0 else torch.full_like(loss, gs), allow_unused=True)
+        dst = list(self.grads[0].values()) + list(self.grads[1].values())
+        torch._foreach_copy_([d for d, g in zip(dst, grads) if g is not None], [g for g in grads if g is not None])
+        for d, g in zip(dst, grads):
+            if g is None:
+                d.zero_()
+        if self.no_dir:
+            for g in self.grads:
+                g[DIR_W][:, 256:].zero_()
+        return self.grads
+
+    def clip_grads(self) -> Optional[torch.Tensor]:
+        """``nn.utils.clip_grad_norm_`` / ``clip_grad_value_`` over both networks together (:403-407), in place on
+        ``self.grads``.  Returns the total 2-norm before clipping ('norm'), None otherwise or when ``grad_clip_val`` is 0."""
+        if self.grad_clip_val <= 0:
+            return None
+        grads = list(self.grads[0].values()) + list(self.grads[1].values())
+        if self.grad_clip_type == "value":
+            torch._foreach_clamp_min_(grads, -self.grad_clip_val)
+            torch._foreach_clamp_max_(grads, self.grad_clip_val)
+            return None
+        # torch.nn.utils.clip_grad_norm_ (norm_type 2): the norm of the per-tensor norms, coefficient clamped to 1
+        total = torch.linalg.vector_norm(torch.stack([torch.linalg.vector_norm(g, 2.0) for g in grads]), 2.0)
+        coef = torch.clamp(self.grad_clip_val / (total + 1e-6), max=1.0)
+        torch._foreach_mul_(grads, coef)
+        return total
+
+    def regularize_patch(self, patch_rays: torch.Tensor, patch_len: int, reg_lambda_tv: float = 1.0, draws=None):
+        """The reference's patch regulariser iteration (``regularize_patch``, models/nerf_downX_model.py:596-618, called from
+        train.py when --reg_patch is on): render a (patch_len * downscale)^2 HR patch (rays in raster order), total-variation
+        loss of its coarse and fine colours (``tv_loss``) times ``reg_lambda_tv``, backward, its own Adam step.  Returns the
+        device tensor [tv_coarse, tv_fine] (before the lambda)."""
+        side = int(patch_len) * int(round(self.s2 ** 0.5))
+        out = self.forward(draws, rays=patch_rays)
+        loss_c = tv_loss(out["coarse_comp_rgbs"].view(side, side, -1))
+        loss_f = tv_loss(out["fine_comp_rgbs"].view(side, side, -1))
+        self.backward((loss_c + loss_f) * reg_lambda_tv)
+        self.all_reduce_grads()
+        self.optimizer_step()
+        self.out_patch = out
+        return torch.stack([loss_c.detach(), loss_f.detach()])
+
     def all_reduce_grads(self, group=None):
         """Data-parallel training (replaces DistributedDataParallel's bucketed gradient all-reduce,
         models/networks.py:84): every rank renders its own ray batch with ``grad_scale = 1 / world`` and ONE
@@ -234,16 +479,15 @@ class Trainer:
                 _ptr_array(list(self.params[n].values())), _ptr_array(list(self.grads[n].values())),
                 _ptr_array(list(self.exp_avg[n].values())), _ptr_array(list(self.exp_avg_sq[n].values())),
                 self.step, self.lr, self.beta1, self.beta2, self.eps, _stream()), "nsr_adam_step")
+        if self._leaves is not None:
+            # nsr_adam_step wrote the weights behind autograd's back: mark them modified, so that the backward of a forward
+            # made before this step fails the version check instead of mixing two sets of weights
+            torch.autograd.graph.increment_version(self._leaves[0] + self._leaves[1])
 
     def status(self, clear: bool = False) -> int:
         """Sticky numerics status word of the training step (``NSR_FLAG_*``, include/nsr_train.h): 0 = every iteration so
         far packed in-range weights and saw in-range inputs / activations and finite outputs.  Waits for the stream."""
-        if self._ws is None:
-            return 0
-        import ctypes
-        flags = ctypes.c_uint(0)
-        _lib.check(_lib.load().nsr_train_status(_p(self._ws), int(bool(clear)), ctypes.byref(flags), _stream()), "nsr_train_status")
-        return int(flags.value)
+        return self._workspace.status(clear)
 
     def optimize_parameters(self, draws=None):
         """One training iteration (:398-408); returns the device tensor [coarse_mse, fine_mse] (lambda-weighted).
@@ -268,6 +512,8 @@ class Trainer:
                     + (" or left the fp16 range of the split-fp16 forward; retry with precision='fp32'"
                        if self.precision != "fp32" else ""))
         self.all_reduce_grads()
+        if self.grad_clip_val > 0:
+            self.clip_grads()
         self.optimizer_step()
         return self.losses
 
