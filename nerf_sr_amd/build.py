@@ -67,6 +67,33 @@ def source_hash() -> str:
     return h.hexdigest()
 
 
+def _compile_units(units, objdir, defines=(), force=False, verbose=True):
+    """Compile (source, extra flags) units into ``objdir`` where the object is missing or older than the sources; returns
+    the object paths in order."""
+    hipcc = _hipcc()
+    os.makedirs(objdir, exist_ok=True)
+    common = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", *defines]
+    objs, jobs = [], []
+    newest = _newest_source_mtime()
+    for src, extra in units:
+        obj = os.path.join(objdir, os.path.basename(src).replace(".hip", ".o"))
+        srcp = os.path.join(CSRC, src)
+        if force or not os.path.exists(obj) or os.path.getmtime(obj) < max(newest, os.path.getmtime(srcp)):
+            jobs.append([hipcc, *common, *extra, "-c", srcp, "-o", obj])
+        objs.append(obj)
+    # the units are independent: compile them side by side (the three MFMA chain kernels take 30-40 s each)
+    from concurrent.futures import ThreadPoolExecutor
+
+    def _compile(cmd):
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+
+    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs) or 1, os.cpu_count() or 1))) as pool:
+        list(pool.map(_compile, jobs))
+    return objs
+
+
 def build(force: bool = False, verbose: bool = True, variant: str = "", defines=()) -> str:
     """Compile every HIP unit for gfx950 and link ``nerf_sr_amd/libnsr.so``; returns its path.
 
@@ -82,31 +109,39 @@ def build(force: bool = False, verbose: bool = True, variant: str = "", defines=
         return LIB
     hipcc = _hipcc()
     objdir = os.path.join(HERE, "build", variant) if variant else os.path.join(HERE, "build")
-    os.makedirs(objdir, exist_ok=True)
-    common = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", *defines]
-    objs, jobs = [], []
-    newest = _newest_source_mtime()
-    for src, extra in UNITS + [VARIANT_UNITS[d] for d in defines if d in VARIANT_UNITS]:
-        obj = os.path.join(objdir, os.path.basename(src).replace(".hip", ".o"))
-        srcp = os.path.join(CSRC, src)
-        if force or not os.path.exists(obj) or os.path.getmtime(obj) < newest:
-            jobs.append([hipcc, *common, *extra, "-c", srcp, "-o", obj])
-        objs.append(obj)
-    # the units are independent: compile them side by side (the three MFMA chain kernels take 30-40 s each)
-    from concurrent.futures import ThreadPoolExecutor
-
-    def _compile(cmd):
-        if verbose:
-            print(" ".join(cmd), flush=True)
-        subprocess.check_call(cmd)
-
-    with ThreadPoolExecutor(max_workers=max(1, min(len(jobs) or 1, os.cpu_count() or 1))) as pool:
-        list(pool.map(_compile, jobs))
+    objs = _compile_units(UNITS + [VARIANT_UNITS[d] for d in defines if d in VARIANT_UNITS], objdir, defines, force, verbose)
     cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", LIB]
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)
     return LIB
+
+
+# ---- test-hook library (tests/hooks.py): the product's own objects -- same sources, same flags, the very files libnsr.so is
+# linked from -- plus ONE extra unit that lives with the tests and exports C wrappers over the library-internal matrix
+# kernels (nsr::gemm, gemm_f16x3, wgrad_jobs_plan, wgrad_jobs_f16).  A second link, not a variant: no define, no #if in csrc/,
+# libnsr.so and its export list stay as they are.
+TEST_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks.hip")
+TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
+
+
+def hooks_stale() -> bool:
+    return not os.path.exists(TEST_HOOKS_LIB) or \
+        os.path.getmtime(TEST_HOOKS_LIB) < max(_newest_source_mtime(), os.path.getmtime(TEST_HOOKS_SRC))
+
+
+def build_test_hooks(force: bool = False, verbose: bool = True) -> str:
+    """Link ``<repo>/ab/libnsr_testhooks.so`` = product objects + tests/csrc/nsr_test_hooks.hip; returns its path."""
+    if not force and not hooks_stale():
+        return TEST_HOOKS_LIB
+    build(force=force, verbose=verbose)                      # libnsr.so first: the objects below are its objects
+    objs = _compile_units(UNITS + [(TEST_HOOKS_SRC, ["-ffp-contract=off", "-I" + CSRC])], os.path.join(HERE, "build"), (), False, verbose)
+    os.makedirs(AB_DIR, exist_ok=True)
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", TEST_HOOKS_LIB]
+    if verbose:
+        print(" ".join(cmd), flush=True)
+    subprocess.check_call(cmd)
+    return TEST_HOOKS_LIB
 
 
 # ---- ISA contract of the hand-written inline asm (tests/test_isa_contract.py; ADVICE r4: run it for every variant) ----------
@@ -190,3 +225,4 @@ if __name__ == "__main__":
         print(build(variant=sys.argv[i + 1], defines=[a for a in sys.argv[i + 2:] if a.startswith("-D")]))
     else:
         print(build(force="--force" in sys.argv))
+        print(build_test_hooks(force="--force" in sys.argv))
