@@ -28,7 +28,9 @@ UNITS = [
     ("nsr_gemm.hip", ["-ffp-contract=off"]),
     ("nsr_gemm_f16.hip", ["-ffp-contract=off"]),
     ("nsr_wgrad_f16.hip", ["-ffp-contract=off"]),
+    ("nsr_train_wgrad.hip", ["-ffp-contract=off"]),
     ("nsr_train.hip", ["-ffp-contract=off"]),
+    ("nsr_train_gemm.hip", ["-ffp-contract=off"]),
     ("nsr_train_chain.hip", ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     ("nsr_warp.hip", ["-ffp-contract=off"]),
     ("nsr_refine.hip", ["-ffp-contract=off"]),

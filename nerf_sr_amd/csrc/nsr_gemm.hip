@@ -14,6 +14,7 @@
 //                         lanes of a half read 32 consecutive floats, conflict free.
 // Both use the same k <-> (q, h, t) mapping, so the K permutation cancels in the product.
 #include "nsr_gemm.h"
+#include "../../include/nsr_train.h"
 #include "nsr_gemm_epilogue.h"
 
 namespace nsr {
@@ -179,6 +180,17 @@ NSR_INTERNAL int gemm(const GemmArgs& g, hipStream_t st) {
   if (!g.a_kmajor && g.b_kmajor) return launch<0, 1>(a, splits, st);
   if (g.a_kmajor && g.b_kmajor) return launch<1, 1>(a, splits, st);
   return NSR_ERR_UNSUPPORTED;
+}
+
+// GenericMLP's inference GEMM (include/nsr_train.h, nerf_sr_amd/ops.py)
+extern "C" int nsr_linear(const float* x, int64_t ldx, const float* w, int64_t ldw, const float* b, int act, float* y,
+                          int64_t ldy, float* y_t, int64_t ldyt, int64_t P, int K, int N, void* stream) {
+  if (P < 0 || K <= 0 || N <= 0 || act < 0 || act > 2) return NSR_ERR_INVALID_ARG;
+  if (P == 0) return NSR_OK;
+  GemmArgs g{};
+  g.A = x; g.lda = ldx; g.B = w; g.ldb = ldw; g.C = y; g.ldc = ldy; g.Ct = y_t; g.ldct = ldyt; g.bias = b;
+  g.M = P; g.N = N; g.K = K; g.n_valid = N; g.act = act; g.splits = 1;
+  return gemm(g, nsr_stream(stream));
 }
 
 }  // namespace nsr

@@ -11,6 +11,7 @@
 // (a K tile of 32 channels never straddles a tap because cin % 32 == 0), so a 3 x 3 convolution needs no col matrix.
 #include <type_traits>
 #include "nsr_gemm.h"
+#include "../../include/nsr_train.h"
 #include "nsr_gemm_epilogue.h"
 
 namespace nsr {
@@ -986,6 +987,25 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
   }
   if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
   return NSR_OK;
+}
+
+// GenericMLP's inference GEMM (include/nsr_train.h, nerf_sr_amd/ops.py)
+extern "C" int nsr_split_weights(const float* w, int64_t n, void* w_hi, void* w_lo, void* stream) {
+  return split_f16(w, n, static_cast<unsigned short*>(w_hi), static_cast<unsigned short*>(w_lo), nsr_stream(stream));
+}
+
+extern "C" int nsr_linear_f16x3(const float* x, int64_t ldx, const void* w_hi, const void* w_lo, int64_t ldw, const float* b, int act,
+                                float* y, int64_t ldy, int64_t P, int K, int N, void* stream) {
+  if (P < 0 || K <= 0 || N <= 0 || act < 0 || act > 2 || !w_hi || !w_lo) return NSR_ERR_INVALID_ARG;
+  if (P == 0) return NSR_OK;
+  GemmF16Args a{};
+  a.g.A = x; a.g.lda = ldx; a.g.C = y; a.g.ldc = ldy; a.g.bias = b;
+  a.g.M = P; a.g.N = N; a.g.K = K; a.g.n_valid = N; a.g.act = act; a.g.splits = 1;
+  a.g.acc_scale = kSplitInvScale;
+  a.Bh = static_cast<const unsigned short*>(w_hi);
+  a.Bl = static_cast<const unsigned short*>(w_lo);
+  a.ldbh = ldw;
+  return gemm_f16x3(a, nsr_stream(stream));
 }
 
 }  // namespace nsr

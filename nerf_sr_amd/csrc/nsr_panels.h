@@ -1,5 +1,5 @@
 // Geometry of the 2-byte training panels (nsr_f16x3_core.h "Training panels"), shared by the chain kernels that write them,
-// the weight-gradient kernel that reads them and the host code that carves them (nsr_train.hip).
+// the weight-gradient kernel that reads them and the host code that carves and schedules them (nsr_train.hip, nsr_train_wgrad.hip).
 #pragma once
 #include <stdint.h>
 #include <hip/hip_runtime.h>

@@ -19,7 +19,7 @@ from nerf_sr_amd import build as nsr_build
 NSR_OK, NSR_ERR_INVALID_ARG, NSR_ERR_UNSUPPORTED = 0, -1, -2
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
 MAX_WGRAD_JOBS = 16
-# the four tile shapes (M, N) of the fp16 weight-gradient kernel, and the order nsr_train.hip::chain_weight_grads issues a
+# the four tile shapes (M, N) of the fp16 weight-gradient kernel, and the order nsr_train_wgrad.hip::chain_weight_grads issues a
 # pass's twelve products in
 TILES = ((256, 256), (128, 256), (256, 64), (128, 64))
 STEP_JOBS = [(128, 256), (128, 64), (256, 256), (256, 256), (256, 256), (256, 256), (256, 256), (256, 64), (256, 256), (256, 256),

@@ -219,7 +219,7 @@ def test_gemm_forward_strided_coverage_is_complete():
     assert n == 144 and len({(i * 35) % n for i in range(n)}) == n
 
 
-# the step's dgrad products (nsr_train.hip lin_dgrad): (K, N, ldb at least)
+# the step's dgrad products (nsr_train_gemm.hip lin_dgrad): (K, N, ldb at least)
 DGRAD_SHAPES = ((32, 128, 0), (128, 256, 288), (288, 256, 0), (256, 256, 0), (256, 64, 0))
 
 
@@ -613,7 +613,7 @@ def test_wgrad_f16_single_product_exact(hk, M, N):
 
 @pytest.mark.parametrize("n_jobs", (2, 5, 12))
 def test_wgrad_f16_many_products_one_launch_exact(hk, n_jobs):
-    """the step's own product list (nsr_train.hip chain_weight_grads order, mixed tile shapes) as ONE launch: a workgroup
+    """the step's own product list (nsr_train_wgrad.hip chain_weight_grads order, mixed tile shapes) as ONE launch: a workgroup
     starts and ends in the middle of a product, slots are handed out per product; 300 workgroups for 128 point groups x 12
     products leave some without a whole group"""
     gen = torch.Generator().manual_seed(n_jobs)
