@@ -101,6 +101,10 @@ int nsr_pack_weights_async(const float* const* w, void* packed_dev, int precisio
  *                               is lost beyond 66,528).  The networks trained in tests/test_gpu_trained.py reach 165
  *                               (6 x below the limit); a diverged network trips it.  Re-run with NSR_FP32.
  *   NSR_FLAG_OUTPUT_NONFINITE   a network output (r, g, b, sigma) was inf / NaN
+ * One exception: the NSR_F16X3 launch of nsr_render_rays_composited / nsr_forward_rays* does not evaluate the colour branch
+ * (xyz_encoding_final, dir_encoding, rgb) of a window of 4 consecutive rays x 32 consecutive samples whose 128 raw
+ * densities are all <= 0 (relu density, raw == NULL: those colours have weight exactly 0).  For such a window the word
+ * reports the inputs, the trunk and the density only; a NaN density is not <= 0 and keeps its window whole.
  * nsr_weights_status copies the word to *flags_out (HOST), clears it on the device if `clear`, and WAITS for `stream`
  * (the second synchronising entry point).  The blob is therefore read-mostly, not read-only: `packed_dev` arguments
  * are const for the weight stream, the status word behind it is written by the kernels. */

@@ -124,20 +124,23 @@ def build(force: bool = False, verbose: bool = True, variant: str = "", defines=
 # kernels (nsr::gemm, gemm_f16x3, wgrad_jobs_plan, wgrad_jobs_f16).  A second link, not a variant: no define, no #if in csrc/,
 # libnsr.so and its export list stay as they are.
 TEST_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks.hip")
+# ... and the render launch with its skipped-window counter (tests/test_gpu_empty_skip.py)
+TEST_HOOKS_SRCS = [TEST_HOOKS_SRC, os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_render.hip")]
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 
 def hooks_stale() -> bool:
     return not os.path.exists(TEST_HOOKS_LIB) or \
-        os.path.getmtime(TEST_HOOKS_LIB) < max(_newest_source_mtime(), os.path.getmtime(TEST_HOOKS_SRC))
+        os.path.getmtime(TEST_HOOKS_LIB) < max(_newest_source_mtime(), *(os.path.getmtime(s) for s in TEST_HOOKS_SRCS))
 
 
 def build_test_hooks(force: bool = False, verbose: bool = True) -> str:
-    """Link ``<repo>/ab/libnsr_testhooks.so`` = product objects + tests/csrc/nsr_test_hooks.hip; returns its path."""
+    """Link ``<repo>/ab/libnsr_testhooks.so`` = product objects + tests/csrc/nsr_test_hooks*.hip; returns its path."""
     if not force and not hooks_stale():
         return TEST_HOOKS_LIB
     build(force=force, verbose=verbose)                      # libnsr.so first: the objects below are its objects
-    objs = _compile_units(UNITS + [(TEST_HOOKS_SRC, ["-ffp-contract=off", "-I" + CSRC])], os.path.join(HERE, "build"), (), False, verbose)
+    objs = _compile_units(UNITS + [(src, ["-ffp-contract=off", "-I" + CSRC]) for src in TEST_HOOKS_SRCS], os.path.join(HERE, "build"), (), False,
+                          verbose)
     os.makedirs(AB_DIR, exist_ok=True)
     cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", TEST_HOOKS_LIB]
     if verbose:

@@ -84,6 +84,7 @@ struct NsrCompOut {
   float* opacity;
   float* weights;
   int white;
+  unsigned* skipped = nullptr;   // tests only: counts the windows the split-fp16 render kernel ended after the density head
 };
 
 // Epilogue of a 128-point MLP tile whose points are whole rays (NS = 64: two rays, NS = 128: one ray): stage the tile's

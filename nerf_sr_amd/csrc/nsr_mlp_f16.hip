@@ -347,7 +347,9 @@ __device__ __forceinline__ void prefetch_next_chunk(Pre& nxt, int k, int g, cons
 // chunk's last DMA piece (k-step 13).  Vector-memory operations complete in issue order, so the next publish point --
 // which must see that DMA landed -- may leave those stores in flight (block_mma's YOUNGER); they have a whole further
 // chunk to reach HBM.  (Rounds 2-4 stored the sixteen raw fp32 accumulators of a block here.)
-template <bool RELU_OUT, bool TRAIN = false>   // relu on L2..L8 (true), none on xyz_encoding_final (L == 8: false)
+// PEND0 = false: nothing is pending on entry (the windowed render kernel runs the density head between L8 and
+// xyz_encoding_final: L8's last block was re-split in the density block's shadow, and that block has no re-split).
+template <bool RELU_OUT, bool TRAIN = false, bool PEND0 = true>   // relu on L2..L8 (true), none on xyz_encoding_final (L == 8: false)
 __device__ __forceinline__ void trunk_layer(int L, u32x4 (&bh)[16], u32x4 (&bl)[16], u32x4 (&oh)[16], u32x4 (&ol)[16],
                                             const u32x4* stash, Loader& ld, int h, Acc& pend, Pre& pre,
                                             const ChunkRef& after0, const ChunkRef& after1, float& amax, unsigned& sbits,
@@ -398,11 +400,11 @@ __device__ __forceinline__ void trunk_layer(int L, u32x4 (&bh)[16], u32x4 (&bl)[
     block_mma3<16, kBar, (TRAIN ? kTrainYoung : 0)>(
         cur, pre, a_addr, ld, c2, [&](int s, int part) -> u32x4 { return part ? bl[s] : bh[s]; },
         [&](int s, int g) {
-          if (nb == 0)
+          if (nb == 0) {
             // block 7 of the previous layer (always relu'd: the previous layer is L1..L7) -> k-steps 14, 15
             // of THIS layer's input, needed only at the end of this chunk
-            pending_gap<true>(s, g, pend, ptmp, bh[14], bl[14], bh[15], bl[15], amax);
-          else
+            if (PEND0) pending_gap<true>(s, g, pend, ptmp, bh[14], bl[14], bh[15], bl[15], amax);
+          } else
             pending_gap<RELU_OUT>(s, g, pend, ptmp, oh[2 * nb - 2], ol[2 * nb - 2], oh[2 * nb - 1], ol[2 * nb - 1], amax);
           if (TRAIN && s >= 8 && g == 2) {
             const char* blk = (nb == 0) ? panel_block(tr, L - 1, 7) : panel_block(tr, L, nb - 1);
@@ -461,16 +463,35 @@ extern "C" int nsr_dbg_timeline(void* host_dst, size_t bytes) {
 // and bit-identical, neither faster on this power-limited kernel (profiles/r4_persistent_ab.json: same
 // box, fine pass 61.8 ms one tile per workgroup / 61.9 persistent / 62.2 with the overlapped encoding).  They were removed
 // from the sources after commit 93a8826 and can be recovered from git.
+//
+// COMP (the render launches of nsr_render_rays_composited) tiles differently: one workgroup per group of 4 CONSECUTIVE
+// RAYS (grid = ceil(R / 4)), wave w owns ray 4 g + w and walks its NS / 32 windows of 32 consecutive samples in a loop; the
+// weight ring keeps streaming across windows (the last two dir_encoding blocks fetch the next window's L1 chunks), a
+// finished window's (r, g, b, sigma) stays in four registers, and after the last window every wave stages its own ray in the
+// by then idle ring and composites it.  The density head runs BEFORE xyz_encoding_final there (L8 -> sigma ->
+// xyz_encoding_final -> dir_encoding: the blocks are independent sums over the same operands, so every value is bit for
+// bit what the other order gives), which lets a window whose 128 samples all have raw density <= 0 stop after it: under
+// the relu density such a sample's alpha is exactly 0, its weight +0 and w * rgb = 0 for any finite rgb (composite_ray), so
+// xyz_encoding_final, dir_encoding and the colour head -- 200 of the window's 1,184 k-steps -- are dead work and rgb is set
+// to 0.  Consecutive rays are the sub-pixel rays of one LR pixel, so the four waves' depth windows are empty together far
+// more often than the 128 samples of whole rays (scripts/empty_tile_stats.py).  The skip is off under the softplus density
+// and when the raw network output is asked for; a NaN density never skips.
 template <int MODE, bool SIGMA_ONLY, int NS, bool COMP = false, bool TRAIN = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, const float* __restrict__ zv,
                  int64_t P, int N, int stride, float* __restrict__ out, NsrTail tail, NsrCompOut co = NsrCompOut{},
                  float* pan = nullptr, unsigned* sgn = nullptr) {
   // 3 x 41 KiB weight ring + per-wave stash of the encoded position (8 fragments x 64 lanes x 16 B = 8 KiB
-  // per wave) + the colour-head block (rgb weights and bias, 448 floats) + the compositor's staging area (640 floats):
-  // 163,072 B of the CU's 163,840
+  // per wave) + the colour-head block (rgb weights and bias, 448 floats) + 640 floats that were the compositor's staging
+  // area until the COMP kernels moved it into the idle ring (their vote word is the first of them): 163,072 B of the CU's
+  // 163,840
   constexpr int kStash0 = 3 * kSlotFloats, kAux0 = kStash0 + 4 * 8 * 256, kComp0 = kAux0 + hx::kAuxFloats;
   __shared__ __attribute__((aligned(16))) float ring[kComp0 + 640];
+  static_assert(!COMP || (MODE == 1 && !SIGMA_ONLY && !TRAIN && (NS == 64 || NS == 128)), "COMP: whole rays of 64 or 128 samples");
+  constexpr int kWindows = COMP ? NS / 32 : 1;     // COMP: depth windows of a ray group, walked in a loop
+  // COMP: the compositor stages in the idle ring after the last window; the first word of the old staging area is the
+  // workgroup's vote "some sample of this window is live"
+  unsigned* const vote = reinterpret_cast<unsigned*>(ring + kComp0);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int m = lane & 31, h = lane >> 5;
@@ -498,7 +519,8 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
 #pragma unroll
   for (int i = 0; i < 11; ++i) loader_issue(ld, i);
 
-  const int64_t n_tiles = (P + 127) / 128;
+  const int64_t n_rays = COMP ? P / (NS > 0 ? NS : 1) : 0;
+  const int64_t n_tiles = COMP ? (n_rays + 3) / 4 : (P + 127) / 128;
   // colour-head options of the packed network (nsr_common.h); TRAIN: word 1 of the step's status block, of which the kernel
   // honours the activation only (the step applies --gamma_correct itself, between this launch and the compositor)
   const unsigned opts = nsr_opts(tail) & (TRAIN ? kOptColorNone : ~0u);
@@ -515,9 +537,18 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     dma_drain();
     return;
   }
+  // COMP: the empty-window skip (see the header): relu density and no raw output
+  const bool skip_on = COMP && !(co.white & NSR_SIGMA_SOFTPLUS) && out == nullptr;
+  const int64_t my_ray = tile * 4 + wave;                              // COMP: this wave's ray; past the end: the last one, unused
+  const int64_t my_ray_c = my_ray < n_rays ? my_ray : n_rays - 1;
+  float res[kWindows][4];                                              // COMP: (r, g, b, sigma) of the finished windows (h == 0 lanes)
+  u32x4 bh[16], bl[16], oh[16], ol[16];
+#pragma unroll 1
+  for (int win = 0; win < kWindows; ++win) {
   NSR_TL(0);
-  const int64_t p = tile * 128 + wave * 32 + m;
-  const int64_t pc = p < P ? p : P - 1;
+  const int64_t p = COMP ? (my_ray < n_rays ? my_ray * NS + win * 32 + m : P) : tile * 128 + wave * 32 + m;
+  const int64_t pc = COMP ? my_ray_c * NS + win * 32 + m : (p < P ? p : P - 1);
+  if (COMP && threadIdx.x == 0) *vote = 0u;                            // published by the barrier below
   PanelRef tr{};
   if (TRAIN) {
     tr.base = reinterpret_cast<char*>(pan);
@@ -630,7 +661,6 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   for (int k = 0; k < kPF; ++k) prefetch_frag(l1pre, k, ld.slot_cur + ld.lane_off);
   prefetch_bias(l1pre, ld.slot_cur + 32 * 1024, h);
 
-  u32x4 bh[16], bl[16], oh[16], ol[16];
   Acc pend;
   Pre pre;
   unsigned sbits = 0u;     // TRAIN: sign bits of the pending blocks, two blocks per stored dword (nsr_f16x3_core.h)
@@ -707,6 +737,8 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   }
   if (SIGMA_ONLY) {   // xyz_encoding_final is not evaluated: L8 is followed by the density head, then nothing
     trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wave), first_ref(0, wave), amax, sbits);
+  } else if (COMP) {  // the density head comes next (SIGMA_ONLY's sequence), xyz_encoding_final after it
+    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wave), layer_ref(8, 0, wave), amax, sbits);
   } else {
 #ifdef NSR_ABL_TIMELINE
     trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wave), layer_ref(8, 1, wave), amax, sbits, tr, voff0, voff1, tk);
@@ -720,7 +752,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   NSR_TL(3);
   // ---- density head: sigma.weight as row 0 of one more 32-row block over h8 (= oh/ol: the input of
   // xyz_encoding_final, still intact).  The pending block is xyz_encoding_final's last one (-> bh, no
-  // activation), or L8's last one in a sigma_only launch (-> oh, relu).
+  // activation), or L8's last one in a sigma_only or COMP launch (-> oh, relu).
   float sigma;
   {
     Acc cur;
@@ -734,10 +766,10 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     constexpr bool kDensityMma = true;
 #endif
     block_mma3<16, kBar, (TRAIN ? kTrainYoung : 0), true, kDensityMma>(
-        cur, pre, ld.slot_cur + ld.lane_off, ld, SIGMA_ONLY ? first_ref(1, wave) : dir_ref(1, wave),
+        cur, pre, ld.slot_cur + ld.lane_off, ld, SIGMA_ONLY ? first_ref(1, wave) : (COMP ? layer_ref(8, 1, wave) : dir_ref(1, wave)),
         [&](int s, int part) -> u32x4 { return part ? ol[s] : oh[s]; },
         [&](int s, int g) {
-          if (SIGMA_ONLY)
+          if (SIGMA_ONLY || COMP)
             pending_gap<true>(s, g, pend, ptmp, oh[14], ol[14], oh[15], ol[15], amax);
           else
             pending_gap<false>(s, g, pend, ptmp, bh[14], bl[14], bh[15], bl[15], amax);
@@ -748,8 +780,9 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
           }
         },
         [&](int k, int g) {
-          // sigma_only: the tile ends here, the next chunk is L1 chunk 0 again (bias behind 32 weight pieces)
-          prefetch_next_chunk(nxt, k, g, ld, SIGMA_ONLY ? 32u * 1024u : next_bias, h);
+          // sigma_only: the tile ends here, the next chunk is L1 chunk 0 again (bias behind 32 weight pieces); COMP: the
+          // first block of xyz_encoding_final (the same)
+          prefetch_next_chunk(nxt, k, g, ld, (SIGMA_ONLY || COMP) ? 32u * 1024u : next_bias, h);
         });
     sigma = cur.m[0] * kWInvScale;           // row 0 of the block lives in register 0 of the h == 0 lanes
     pre = nxt;
@@ -764,9 +797,36 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     return;
   }
 
+  float rgb[3] = {0.0f, 0.0f, 0.0f};
+  // ---- COMP: is any sample of the workgroup's window live?  (!(sigma <= 0): a NaN density is live.)  If none is, the
+  // window ends here with rgb = 0: the two chunks already under way (xyz_encoding_final's first two blocks) are left to
+  // land and are discarded, and the ring is restarted on the next window's L1 chunks exactly as the kernel's prologue
+  // starts it.  The status word of such a window reports its inputs, its trunk and its density only.
+  bool colour = true;
+  if (COMP && skip_on) {
+    const bool live = h == 0 && p < P && !(sigma <= 0.0f);
+    if (__ballot(live) != 0ull && lane == 0) *vote = 1u;
+    __syncthreads();
+    colour = __builtin_amdgcn_readfirstlane(*vote) != 0u;
+    if (!colour) {
+      dma_drain();
+      __syncthreads();          // every wave's DMA has landed and nobody reads the ring
+      if (win + 1 < kWindows) {
+        loader_prepare_dma(ld, first_ref(0, wave), ld.slot_cur);
+#pragma unroll
+        for (int i = 0; i < 11; ++i) loader_issue(ld, i);
+        loader_prepare_dma(ld, first_ref(1, wave), ld.slot_next);
+#pragma unroll
+        for (int i = 0; i < 11; ++i) loader_issue(ld, i);
+      }
+      if (co.skipped && threadIdx.x == 0) atomicAdd(co.skipped, 1u);
+    }
+  }
+  if (colour) {
+  if (COMP) trunk_layer<false, false, false>(8, oh, ol, bh, bl, stash, ld, h, pend, pre, dir_ref(0, wave), dir_ref(1, wave), amax, sbits);
+
   NSR_TL(4);
   // ---- dir_encoding (cat([g, de]) -> 128, relu) fused with the rgb head (128 -> 3, sigmoid)
-  float rgb[3] = {0.0f, 0.0f, 0.0f};
   float2 w2[3];          // colour-head weights of the pair consumed in the next k-step (rgb_gap)
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
@@ -777,13 +837,17 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     Pre nxt;
     // in flight behind the previous block's DMA: the density block's 2 stores | nothing | a dir block's 2 + sign word
     const unsigned a_seq = ld.slot_cur + ld.lane_off;
-    const ChunkRef c2 = nb < 2 ? dir_ref(nb + 2, wave) : first_ref(nb - 2, wave);   // (blocks 2 and 3 fetch nothing)
+    // (blocks 2 and 3 fetch nothing, except COMP: the next window's L1 chunks; dead traffic after the last window)
+    const ChunkRef c2 = nb < 2 ? dir_ref(nb + 2, wave) : first_ref(nb - 2, wave);
+    Resplit ptmp;
     auto b_of = [&](int s, int part) -> u32x4 {
       return (s < 16) ? (part ? bl[s & 15] : bh[s & 15]) : (part ? del[s & 1] : deh[s & 1]);
     };
     auto hook = [&](int s, int g) {
       // the pending dir block is consumed in k-steps 6..13, one pair per k-step, one colour channel per gap
       if (nb > 0) rgb_gap<kConvStep0>(s, g, pend, aux + hx::kAuxRgbW + 32 * (nb - 1), h, rgb, w2);
+      // COMP: xyz_encoding_final's last block (no activation) -> k-steps 14, 15 of this block's own input
+      if (COMP && nb == 0) pending_gap<false>(s, g, pend, ptmp, bh[14], bl[14], bh[15], bl[15], amax);
       if (TRAIN && nb > 0 && s < 8 && g == 1) relu_hi_step(s, pend, dh0, dh1);
       if (TRAIN && nb > 0 && s >= 8 && s < 16 && g == 2) {
         const char* blk = panel_block(tr, 9, nb - 1);
@@ -799,7 +863,8 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     };
     // nothing is fetched behind the last two blocks: the tile's stream ends with them
     if (nb >= 2) {
-      if (!TRAIN) block_mma3<18, kBar, 0, false>(cur, pre, a_seq, ld, c2, b_of, hook, next);
+      if (COMP) block_mma3<18, kBar>(cur, pre, a_seq, ld, c2, b_of, hook, next);
+      else if (!TRAIN) block_mma3<18, kBar, 0, false>(cur, pre, a_seq, ld, c2, b_of, hook, next);
       else block_mma3<18, kBar, kTrainYoung, false>(cur, pre, a_seq, ld, c2, b_of, hook, next);
     } else if (!TRAIN || nb == 1) block_mma3<18, kBar>(cur, pre, a_seq, ld, c2, b_of, hook, next);
     else if (nb == 0) block_mma3<18, kBar, 2>(cur, pre, a_seq, ld, c2, b_of, hook, next);
@@ -840,15 +905,38 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
 #pragma unroll
     for (int k = 0; k < 3; ++k) rgb[k] = nsr_gamma(rgb[k]);
   }
+  }   // colour
   if (amax >= 65520.0f) flags |= NSR_FLAG_ACTIVATION_RANGE;
   if (!(nsr_finite(rgb[0]) && nsr_finite(rgb[1]) && nsr_finite(rgb[2]) && nsr_finite(sigma))) flags |= NSR_FLAG_OUTPUT_NONFINITE;
   if (p < P) nsr_raise(tail, flags);
   if (out && h == 0 && p < P) reinterpret_cast<float4*>(out)[p] = make_float4(rgb[0], rgb[1], rgb[2], sigma);
   NSR_TL(6);
-  // the compositor's staging area is its own: at least L1's two publish barriers lie between two uses, and the weight
-  // ring keeps streaming underneath
-  if (COMP) composite_tile<(COMP ? NS : 64), true>(ring + kComp0, h == 0, wave, m, lane, make_float4(rgb[0], rgb[1], rgb[2], sigma),
-                                                  zv[pc], P / NS, co, tile);
+  if (COMP) {
+#pragma unroll
+    for (int w = 0; w < kWindows; ++w)
+      if (win == w) {
+        res[w][0] = rgb[0];
+        res[w][1] = rgb[1];
+        res[w][2] = rgb[2];
+        res[w][3] = sigma;
+      }
+  }
+  }   // window
+  // COMP: the ring is idle after the drain and the barrier (the last window's dead L1 prefetch included): every wave
+  // stages its own ray in it, sample by sample as the two-call route's (R, N, 4) tensor holds them, and composites it
+  if (COMP) {
+    dma_drain();
+    __syncthreads();
+    float* mine = ring + 4 * (NS > 0 ? NS : 64) * wave;
+    if (h == 0) {
+#pragma unroll
+      for (int w = 0; w < kWindows; ++w) reinterpret_cast<float4*>(mine)[32 * w + m] = make_float4(res[w][0], res[w][1], res[w][2], res[w][3]);
+    }
+    __syncthreads();
+    if (my_ray < n_rays)
+      composite_ray<(COMP ? NS / 64 : 1)>(mine, 4, mine + 3, 4, zv + my_ray * NS, NS, co.white, lane, my_ray, co.comp_rgb, co.depth,
+                                          co.opacity, co.weights);
+  }
 #ifdef NSR_ABL_TIMELINE
   NSR_TL(7);
   if (lane == 0 && tile < kTlGroups) {
@@ -892,7 +980,7 @@ extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const
                                                        void* stream) {
   const NsrTail tail{tail_w};
   const int64_t P = R * N;
-  const dim3 grid((unsigned)((P + 127) / 128)), block(256);
+  const dim3 grid((unsigned)((R + 3) / 4)), block(256);     // one workgroup per group of 4 consecutive rays
   const float* pk = static_cast<const float*>(packed);
   if (N == 64)
     hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 64, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
