@@ -5,6 +5,7 @@ is trained with Trainer.optimize_parameters on random LR-pixel batches of the te
 the reference's train.py (set_input -> optimize_parameters) without its datasets / options / visualiser.
 
     python examples/train_toy.py [--iters 300] [--batch 512]
+    python examples/train_toy.py --arch 6,192,1+3      # a non-default network (--D --W --skips): the layer-by-layer pair
 """
 import argparse
 import os
@@ -15,15 +16,18 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nerf_sr_amd import cameras, ops, train  # noqa: E402
-from nerf_sr_amd.weights import make_state_dict  # noqa: E402
+from nerf_sr_amd.weights import make_state_dict, make_state_dict_arch  # noqa: E402
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--batch", type=int, default=512, help="LR pixels per step (x4 sub-rays)")
+    ap.add_argument("--arch", default="", help="D,W,skips of a non-default network, skips joined by '+' ('6,192,1+3'; '4,128,' = none)")
     a = ap.parse_args()
     W, H, s = 504, 378, 2
+    if a.arch:
+        return main_arch(a, W, H, s)
     teacher_c = ops.VanillaMLP(precision="f16x3").load_state_dict(make_state_dict(99))
     teacher_f = ops.VanillaMLP(precision="f16x3").load_state_dict(make_state_dict(100))
     frames = []
@@ -33,6 +37,32 @@ def main():
         frames.append((rays, ops.sr_mean(out["fine_comp_rgbs"].clone(), rays.shape[0], s * s)))
     student = train.Trainer(make_state_dict(7, field="plain"), make_state_dict(8, field="plain"), randomized=True, noise_std=1.0,
                             lr=5e-4, ray_chunk=4 * a.batch)
+    t0 = time.time()
+    for it in range(a.iters):
+        rays, target = frames[it % len(frames)]
+        sel = torch.randint(0, rays.shape[0], (a.batch,), device="cuda")
+        student.set_input(rays[sel], target[sel])
+        losses = student.optimize_parameters()
+        if it % 50 == 0 or it == a.iters - 1:
+            lc, lf = losses.tolist()
+            print(f"iter {it:4d}  coarse mse {lc:.5f}  fine mse {lf:.5f}  ({(it + 1) / (time.time() - t0):.1f} it/s)")
+
+
+def main_arch(a, W, H, s):
+    """The same loop for ``--arch D,W,skips``: teacher and student are networks of that architecture; the teacher's frames are
+    its deterministic train-mode forward, the student trains through ``Trainer(..., arch=)``."""
+    D, Wd, skips = a.arch.split(",")
+    arch = {"D": int(D), "W": int(Wd), "skips": tuple(int(x) for x in skips.split("+") if x)}
+    teacher = [{k: torch.from_numpy(v).cuda() for k, v in make_state_dict_arch(seed, **arch).items()} for seed in (99, 100)]
+    frames = []
+    for t in (0.1, 0.5, 0.9):
+        rays = ops.subpixel_rays(cameras.spiral_pose(t), (W, H), cameras.llff_focal(W), s, True)
+        with torch.no_grad():
+            out = train.forward_rays_train(teacher[0], teacher[1], rays.view(-1, 8), None, precision="f16x3_gemm", arch=arch,
+                                           ray_chunk=16384)
+        frames.append((rays, out["fine_comp_rgbs"].view(rays.shape[0], s * s, 3).mean(1)))
+    student = train.Trainer(make_state_dict_arch(7, **arch), make_state_dict_arch(8, **arch), randomized=True, noise_std=1.0,
+                            lr=5e-4, ray_chunk=4 * a.batch, precision="f16x3_gemm", arch=arch)
     t0 = time.time()
     for it in range(a.iters):
         rays, target = frames[it % len(frames)]

@@ -180,6 +180,63 @@ int nsr_train_status(void* workspace, int clear, unsigned* flags_out, void* stre
 int nsr_adam_step(float* const* w, const float* const* g, float* const* m, float* const* v, int step, float lr,
                   float beta1, float beta2, float eps, void* stream);
 
+/* ---- Training a network of any architecture the reference's flags describe (--D --W --skips --deg_pos --deg_dir --no_dir;
+ * models/networks.py:124-169, models/nerf_model.py:53-57).  The entry points above are laid out for the default network
+ * (8 x 256, skip at layer 4, degrees 10 / 4); the ones below take a descriptor and run layer by layer on the same GEMM
+ * kernels (csrc/nsr_train_arch.hip).  The default network is a valid descriptor here too: {8, 256, 1u << 4, 10, 4, 0}.
+ *
+ * State tensors: 2 D + 8, in the order of the reference module's state_dict() (nerf_sr_amd.weights.arch_spec):
+ *   xyz_encoding_{i+1}.0.weight (W, fan_in) / .bias (W) for i = 0 .. D-1, fan_in = 3 + 6 deg_pos for layer 0,
+ *   W + 3 + 6 deg_pos for a skip layer (input cat([pe, h])), W otherwise; xyz_encoding_final (W, W) / (W);
+ *   dir_encoding.0 (W / 2, W + 3 + 6 deg_dir) / (W / 2) -- (W / 2, W) under no_dir --; sigma (1, W) / (1); rgb.0 (3, W / 2) / (3)
+ *   (dim_rgb is 3: the compositor renders three colours).
+ * Limits: 1 <= D <= 16, even W with 2 <= W <= 512, 0 <= deg_pos, deg_dir <= 16 (what nsr_posenc accepts).  A descriptor
+ * beyond them (D > 16, W > 512, a degree > 16) is NSR_ERR_UNSUPPORTED; a malformed one (D < 1, W < 2 or odd, a negative
+ * degree, a skip bit at 0 or at >= D, no_dir other than 0 / 1, a NULL descriptor) NSR_ERR_INVALID_ARG. */
+typedef struct nsr_arch {
+  int D, W;
+  unsigned skips;      /* bit i (1 <= i < D): layer i sees cat([pe, h]) */
+  int deg_pos, deg_dir;
+  int no_dir;
+} nsr_arch;
+#define NSR_ARCH_MAX_D 16
+#define NSR_ARCH_MAX_W 512
+#define NSR_ARCH_MAX_DEG 16
+/* 2 D + 8, or the error code (< 0) of the descriptor */
+int nsr_arch_n_tensors(const nsr_arch* arch);
+/* elements of state tensor t; 0 on an invalid descriptor or index */
+int64_t nsr_arch_tensor_numel(const nsr_arch* arch, int t);
+/* Sizes of the workspace and of the saved state of the pair below; they depend on their arguments only.  0 on invalid
+ * arguments: a descriptor, precision or sample counts the pair rejects, ray_chunk <= 0 (workspace), R <= 0 or a chunking that
+ * breaks the 32-point rule (saved state; the workspace size is a function of ray_chunk alone and does not know R).  Per sample point the saved state keeps, in
+ * floats, n_x (Kx + Wp) + (D - n_x) Wp + (Wp + Dp) + Hp + 6 with Kx = r32(3 + 6 deg_pos), Wp = r32(W), Hp = r32(W / 2),
+ * Dp = r32(3 + 6 deg_dir) (0 under no_dir), r32 = rounded up to 32, n_x = max(1, number of skips): every trunk layer's
+ * output, the encoded position once per skip layer (in front of that layer's input, so cat([pe, h]) is a column range),
+ * the colour branch's input [final | dir pe], its hidden layer, (rgb, sigma), the noisy sigma and z. */
+size_t nsr_train_arch_workspace_bytes(const nsr_arch* arch, int precision, int64_t ray_chunk, int n_coarse, int n_importance);
+size_t nsr_train_arch_saved_bytes(const nsr_arch* arch, int precision, int64_t R, int n_coarse, int n_importance, int64_t ray_chunk);
+/* nsr_train_forward / nsr_train_backward for the network `arch` describes: the same arguments with the same meaning
+ * (outputs, draws, render_flags with NSR_TRAIN_STOP_GRAD, lindisp, ray strides, ray_chunk, the 32-point rule; all eight
+ * upstream gradients, NULL = zero; coarse weights detached for the fine pass; everything checked before anything is
+ * enqueued), weight and gradient arrays of nsr_arch_n_tensors DEVICE pointers.  precision: NSR_FP32 or NSR_F16X3_GEMM
+ * (forward products split-fp16, every gradient on the fp32 MFMA); the chain precisions are NSR_ERR_UNSUPPORTED.  The saved
+ * header records the descriptor: a backward with another descriptor, a buffer no forward wrote or a damaged header is
+ * NSR_ERR_INVALID_ARG, a buffer shorter than its header says NSR_ERR_WORKSPACE.  The weights must be the forward call's.
+ * Weight matrices must be 16-byte aligned (a trunk layer whose shape needs no padding is the GEMMs' operand where the caller
+ * holds it): NSR_ERR_INVALID_ARG otherwise, like every other check before anything is enqueued.
+ * Weight gradients are reduced in a fixed order (no atomics): two identical calls give identical bits. */
+int nsr_train_arch_forward(const nsr_arch* arch, const float* const* w_coarse, const float* const* w_fine, const float* rays,
+                           int ray_stride, int64_t R, int n_coarse, int n_importance, int render_flags, int lindisp,
+                           const float* u_coarse, const float* u_fine, const float* noise_coarse, const float* noise_fine,
+                           float noise_std, int precision, int64_t ray_chunk, float* const* outs, void* workspace,
+                           size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream);
+int nsr_train_arch_backward(const nsr_arch* arch, const float* const* w_coarse, const float* const* w_fine,
+                            const float* const* g_outs, float* const* g_coarse, float* const* g_fine, void* workspace,
+                            size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream);
+/* nsr_adam_step over n tensors of numel[i] elements each (HOST array), the same arithmetic; 1 <= n <= 2 NSR_ARCH_MAX_D + 8. */
+int nsr_adam_step_n(int n, const int64_t* numel, float* const* w, const float* const* g, float* const* m, float* const* v,
+                    int step, float lr, float beta1, float beta2, float eps, void* stream);
+
 /* One nn.Linear (+ activation) on the training GEMM, exposed for testing the kernel on its own:
  *   y (P, N) = act(x (P, K) · w (N, K)^T + b),  act: 0 none, 1 relu, 2 sigmoid;  y_t (N, P) optional transpose.
  * K % 32 == 0, ldx % 4 == 0, ldw % 4 == 0, 16-byte aligned pointers (the training step pads its operands). */

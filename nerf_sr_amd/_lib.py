@@ -28,6 +28,12 @@ NSR_F16X3_BWD3, NSR_F16X3_BWD2, NSR_F16X3_BWD1, NSR_F16X3_BWDM = 19, 20, 21, 22 
 TRAIN_PRECISIONS = {"fp32": NSR_FP32, "f16x3": NSR_F16X3, "f16x3_gemm": NSR_F16X3_GEMM,
                     "f16x3_bwd3": NSR_F16X3_BWD3, "f16x3_bwd2": NSR_F16X3_BWD2, "f16x3_bwd1": NSR_F16X3_BWD1, "f16x3_bwdm": NSR_F16X3_BWDM}
 
+
+class NsrArch(ctypes.Structure):
+    """``struct nsr_arch`` (include/nsr_train.h): the architecture flags of a VanillaMLP."""
+    _fields_ = [("D", c_int), ("W", c_int), ("skips", c_uint), ("deg_pos", c_int), ("deg_dir", c_int), ("no_dir", c_int)]
+
+
 # symbol -> (restype, argtypes); must list every function of include/*.h
 SIGNATURES = {
     "nsr_version": (c_int, []),
@@ -84,6 +90,17 @@ SIGNATURES = {
     "nsr_train_status": (c_int, [c_void_p, c_int, POINTER(c_uint), c_void_p]),
     "nsr_adam_step": (c_int, [POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), c_int,
                               c_float, c_float, c_float, c_float, c_void_p]),
+    "nsr_arch_n_tensors": (c_int, [POINTER(NsrArch)]),
+    "nsr_arch_tensor_numel": (c_int64, [POINTER(NsrArch), c_int]),
+    "nsr_train_arch_workspace_bytes": (c_size_t, [POINTER(NsrArch), c_int, c_int64, c_int, c_int]),
+    "nsr_train_arch_saved_bytes": (c_size_t, [POINTER(NsrArch), c_int, c_int64, c_int, c_int, c_int64]),
+    "nsr_train_arch_forward": (c_int, [POINTER(NsrArch), POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int, c_int64, c_int, c_int,
+                                       c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64,
+                                       POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "nsr_train_arch_backward": (c_int, [POINTER(NsrArch), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                        POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "nsr_adam_step_n": (c_int, [c_int, POINTER(c_int64), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                c_int, c_float, c_float, c_float, c_float, c_void_p]),
     # ---- include/nsr_warp.h
     "nsr_depth_warp": (c_int, [c_void_p, c_int, c_int, c_double, POINTER(c_float), POINTER(c_double), c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p]),

@@ -282,33 +282,17 @@ struct AdamPtrs {
   float* m[NSR_N_STATE_TENSORS];
   float* v[NSR_N_STATE_TENSORS];
 };
-// torch/optim/adam.py (_single_tensor_adam) operation order, fp32
+// one launch over the 24 tensors of the default network (adam_update: nsr_train_work.h)
 __global__ void __launch_bounds__(256) adam_kernel(AdamPtrs a, float beta1, float beta2, float eps, float step_size,
                                                    float bc2_sqrt) {
   const int t = blockIdx.y;
   const int64_t n = tensor_numel(t);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float g = a.g[t][i];
-    const float m = __fadd_rn(__fmul_rn(a.m[t][i], beta1), __fmul_rn(g, 1.0f - beta1));
-    const float v = __fadd_rn(__fmul_rn(a.v[t][i], beta2), __fmul_rn(__fmul_rn(g, g), 1.0f - beta2));   // addcmul: (g*g)*value
-    a.m[t][i] = m;
-    a.v[t][i] = v;
-    const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), bc2_sqrt), eps);
-    a.w[t][i] = __fsub_rn(a.w[t][i], __fmul_rn(step_size, __fdiv_rn(m, denom)));
+    adam_update(a.g[t], a.m[t], a.v[t], a.w[t], i, beta1, beta2, eps, step_size, bc2_sqrt);
   }
 }
 
 // ---- host side: carving the workspace ---------------------------------------------------------------------------------
-struct Carver {   // hands out consecutive 256-byte granules of `base` (null: only counts them)
-  float* base;
-  int64_t off = 0;
-  float* take(int64_t n, bool on = true) {
-    if (!on) return nullptr;
-    float* p = base ? base + off : nullptr;
-    off += align64(n);
-    return p;
-  }
-};
 // the kept state of a pass over P sample points (nsr_train_work.h): THE list of its buffers, for the workspace and for a
 // pass region of the saved state alike
 Kept carve_kept(Carver& a, int64_t P, bool gemm_path, bool chain_path) {
@@ -389,8 +373,9 @@ template <bool COMPACT, bool FULL> CompositeBwdFn composite_bwd_for(int K) {   /
 }
 // compact: the chain path's output layout.  g_opacity / g_weights (nsr_train_backward only): non-null selects the FULL
 // instantiation
-int composite_bwd(hipStream_t st, const Work& k, const float* z, const float* g_comp, int64_t R, int N, int white, bool compact,
-                  const float* g_depth, const float* g_opacity, const float* g_weights) {
+}  // namespace
+int nsr::composite_bwd(hipStream_t st, const Work& k, const float* z, const float* g_comp, int64_t R, int N, int white, bool compact,
+                       const float* g_depth, const float* g_opacity, const float* g_weights) {
   const int K = (N + 63) / 64;
   const bool full = g_opacity || g_weights;
   const CompositeBwdFn fn = compact ? (full ? composite_bwd_for<true, true>(K) : composite_bwd_for<true, false>(K))
@@ -406,10 +391,10 @@ int composite_bwd(hipStream_t st, const Work& k, const float* z, const float* g_
 // ---- the opening the three drivers share -------------------------------------------------------------------------------
 // the shape rules: sample counts and precision (NSR_ERR_UNSUPPORTED), R and the chunk multiples of s2
 // (NSR_ERR_INVALID_ARG), a multiple of 32 points per pass in both networks (NSR_ERR_UNSUPPORTED).  ray_chunk <= 0 or > R
-// becomes R.
-int check_shape(int64_t R, int s2, int n_coarse, int n_importance, int precision, int64_t& ray_chunk) {
+// becomes R.  gemm_only: the layer-by-layer precisions alone (nsr_train_arch.hip)
+int nsr::check_shape(int64_t R, int s2, int n_coarse, int n_importance, int precision, int64_t& ray_chunk, bool gemm_only) {
   if (n_coarse < 2 || n_importance < 1 || n_coarse + n_importance > 256) return NSR_ERR_UNSUPPORTED;
-  if (!train_precision_ok(precision)) return NSR_ERR_UNSUPPORTED;
+  if (!train_precision_ok(precision) || (gemm_only && chain_selected(precision))) return NSR_ERR_UNSUPPORTED;
   if (R % s2 != 0) return NSR_ERR_INVALID_ARG;
   if (ray_chunk <= 0 || ray_chunk > R) ray_chunk = R;
   if (ray_chunk % s2 != 0) return NSR_ERR_INVALID_ARG;
@@ -423,33 +408,28 @@ int check_shape(int64_t R, int s2, int n_coarse, int n_importance, int precision
   return NSR_OK;
 }
 // the option word (include/nsr_train.h): the renderer's two bits + the colour head's two + stop_grad
+namespace {
 constexpr int kTrainOpts = NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS | NSR_TRAIN_GAMMA_CORRECT | NSR_TRAIN_COLOR_NONE | NSR_TRAIN_STOP_GRAD;
-int check_flags(int flags) {
+}  // namespace
+int nsr::check_flags(int flags) {
   if ((flags & ~kTrainOpts) != 0) return NSR_ERR_INVALID_ARG;
   // pow(x, 1 / 2.2) of an unbounded head: NaN for every negative value
   if ((flags & NSR_TRAIN_GAMMA_CORRECT) && (flags & NSR_TRAIN_COLOR_NONE)) return NSR_ERR_UNSUPPORTED;
   return NSR_OK;
 }
 
-struct Need {   // the pointers a driver requires of its caller
-  std::initializer_list<const void*> always;          // whatever R is
-  std::initializer_list<const float* const*> state;   // arrays of NSR_N_STATE_TENSORS tensors, every one of them set
-  float* const* outs;                                 // not null: its two colour outputs [0], [4], when there are rays
-  std::initializer_list<const void*> with_rays;       // when there are rays
-  std::initializer_list<const void*> aligned;         // on 256 bytes
-};
 // Everything that is checked before a call enqueues, in the ONE order that decides which status a call with two mistakes
 // returns.  c: shape and options of the call (c->chunk is resolved; s2 = 1 without a loss), or null for the backward, whose
 // shape comes out of the saved header afterwards.  NSR_OK with c->R == 0 means: nothing to do, the rest was not looked at.
-int check_args(const Need& need, Run* c, int s2) {
+int nsr::check_args(const Need& need, Run* c, int s2) {
   for (const void* p : need.always)
     if (!p) return NSR_ERR_INVALID_ARG;
   if (c) {
     if (c->R < 0 || s2 <= 0 || !nsr_ray_stride_ok(c->ray_stride)) return NSR_ERR_INVALID_ARG;
-    NSR_TRY(check_shape(c->R, s2, c->nc, c->ni, c->precision, c->chunk));
+    NSR_TRY(check_shape(c->R, s2, c->nc, c->ni, c->precision, c->chunk, need.gemm_only));
   }
   for (const float* const* tensors : need.state)
-    for (int i = 0; i < NSR_N_STATE_TENSORS; ++i)
+    for (int i = 0; i < need.n_state; ++i)
       if (!tensors[i]) return NSR_ERR_INVALID_ARG;
   if (c && c->R == 0) return NSR_OK;
   if (need.outs && (!need.outs[0] || !need.outs[4])) return NSR_ERR_INVALID_ARG;
@@ -459,6 +439,7 @@ int check_args(const Need& need, Run* c, int s2) {
     if ((reinterpret_cast<uintptr_t>(p) & 255) != 0) return NSR_ERR_INVALID_ARG;
   return c ? check_flags(c->flags) : NSR_OK;
 }
+namespace {
 // the workspace of a checked call: large enough for its path, then carved
 int open_work(Run& c, void* workspace, size_t workspace_bytes, Work& k) {
   if (workspace_bytes < nsr_train_workspace_bytes_for(c.precision, c.chunk, c.nc, c.ni)) return NSR_ERR_WORKSPACE;
@@ -490,27 +471,29 @@ int prepare_call(hipStream_t st, const Work& k, const float* const* w_coarse, co
 }
 
 // ---- the passes of a call ----------------------------------------------------------------------------------------------
-struct Pass {
-  int net, N;               // 0 = coarse, 1 = fine; its samples per ray
-  int64_t P, r0, rc, ci;    // sample points; first ray and rays of the chunk; index of the chunk
-  int acc;                  // gradients: the first chunk overwrites them, later chunks accumulate
-};
-// chunk by chunk, coarse then fine
-template <class F> int for_each_pass(const Run& c, F&& body) {
-  for (int64_t r0 = 0, ci = 0; r0 < c.R; r0 += c.chunk, ++ci) {
-    const int64_t rc = (c.R - r0 < c.chunk) ? c.R - r0 : c.chunk;
-    for (int net = 0; net < 2; ++net) {
-      const int N = net ? c.nc + c.ni : c.nc;
-      NSR_TRY(body(Pass{net, N, rc * N, r0, rc, ci, r0 > 0}));
-    }
+}  // namespace
+// the two halves of a pass's forward that do not depend on the network (nsr_train_arch.hip runs them around its own):
+// stratified samples (coarse) or inverse-CDF samples from the detached coarse weights w_c over z_c (fine) into z ...
+int nsr::pass_sample(const Run& c, const Pass& q, const float* rays, const float* u, const float* z_c, const float* w_c, float* z,
+                     void* stream) {
+  const float* rays_c = rays + q.r0 * c.ray_stride;
+  if (q.net == 0) return nsr_sample_along_rays(rays_c, c.ray_stride, q.rc, c.nc, c.lindisp, rows_of(u, q, c.nc), z, nullptr, stream);
+  return nsr_resample_along_rays(rays_c, c.ray_stride, z_c, w_c, q.rc, c.nc, c.ni, rows_of(u, q, c.ni), z, nullptr, stream);
+}
+// ... and, from the raw densities (sigma_raw, one every sigma_stride floats) and the (P, 4) colours the network left: density
+// noise into sig, --gamma_correct, compositing
+int nsr::pass_finish(hipStream_t st, const Run& c, const Pass& q, const float* sigma_raw, int sigma_stride, const float* noise,
+                     float* rgb4, float* sig, const float* z, float* comp, float* depth, float* opac, float* wts, void* stream) {
+  hipLaunchKernelGGL(sigma_noise_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, st, sigma_raw, sigma_stride,
+                     c.noise_std > 0.0f ? rows_of(noise, q, q.N) : nullptr, c.noise_std, q.P, sig);
+  NSR_CHECK_LAUNCH();
+  if (c.flags & NSR_TRAIN_GAMMA_CORRECT) {   // render_rays: out_rgbs = pow(out_rgbs, 1 / 2.2) per sample, in training too (nerf_downX_model.py:271-276)
+    hipLaunchKernelGGL(gamma_points_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, st, rgb4, q.P);
+    NSR_CHECK_LAUNCH();
   }
-  return NSR_OK;
+  return nsr_composite(rgb4, 4, sig, 1, z, q.rc, q.N, c.flags & (NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS), comp, depth, opac, wts, stream);
 }
-// the pass's rows of a per-ray array of the whole call (`width` values per ray); null: `fallback`
-template <class T, class U = T> T* rows_of(T* p, const Pass& q, int64_t width, U* fallback = nullptr) {
-  return p ? p + q.r0 * width : fallback;
-}
-
+namespace {
 // forward half of pass q: stratified samples (coarse) or inverse-CDF samples from the detached coarse weights w_c over z_c
 // (fine) into z, the network (what its backward reads stays in k.kept), density noise, --gamma_correct, compositing.
 // rays / u / noise: the call's whole arrays; w_c / comp / depth / opac / wts: this pass's rows (all but comp may be null)
@@ -519,26 +502,15 @@ int pass_forward(hipStream_t st, const Work& k, const Run& c, const Pass& q, con
                  float* opac, float* wts, void* stream) {
   const Kept& s = k.kept;
   const float* rays_c = rays + q.r0 * c.ray_stride;
-  if (q.net == 0) {
-    NSR_TRY(nsr_sample_along_rays(rays_c, c.ray_stride, q.rc, c.nc, c.lindisp, rows_of(u, q, c.nc), z, nullptr, stream));
-  } else {
-    NSR_TRY(nsr_resample_along_rays(rays_c, c.ray_stride, z_c, w_c, q.rc, c.nc, c.ni, rows_of(u, q, c.ni), z, nullptr, stream));
-  }
+  NSR_TRY(pass_sample(c, q, rays, u, z_c, w_c, z, stream));
   if (c.chain) {   // the chain path encodes inside its forward kernel
     NSR_TRY(nsr_f16x3_train_forward(k.stream_f[q.net], rays_c, c.ray_stride, z, q.rc, q.N, s.rgb, s.zpan, s.sgn, k.status, stream));
   } else {
     NSR_TRY(net_forward(st, rays_c, c.ray_stride, z, q.N, w, k.pack[q.net], s, q.P, gemm_precision(c.precision),
                         (c.flags & NSR_TRAIN_COLOR_NONE) != 0));
   }
-  hipLaunchKernelGGL(sigma_noise_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, st,
-                     c.chain ? s.rgb + 3 : s.gs + kSigmaCol, c.chain ? 4 : kGs, c.noise_std > 0.0f ? rows_of(noise, q, q.N) : nullptr,
-                     c.noise_std, q.P, s.sig);
-  NSR_CHECK_LAUNCH();
-  if (c.flags & NSR_TRAIN_GAMMA_CORRECT) {   // render_rays: out_rgbs = pow(out_rgbs, 1 / 2.2) per sample, in training too (nerf_downX_model.py:271-276)
-    hipLaunchKernelGGL(gamma_points_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, st, s.rgb, q.P);
-    NSR_CHECK_LAUNCH();
-  }
-  return nsr_composite(s.rgb, 4, s.sig, 1, z, q.rc, q.N, c.flags & (NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS), comp, depth, opac, wts, stream);
+  return pass_finish(st, c, q, c.chain ? s.rgb + 3 : s.gs + kSigmaCol, c.chain ? 4 : kGs, noise, s.rgb, s.sig, z, comp, depth, opac,
+                     wts, stream);
 }
 
 // backward half of the same pass, from the upstream gradients of its outputs (this pass's rows; g_comp required, the others

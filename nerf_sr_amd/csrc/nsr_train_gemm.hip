@@ -127,8 +127,11 @@ __global__ void __launch_bounds__(256) reduce_place_kernel(float* __restrict__ d
   float* d = dst + (int64_t)i * dst_ld + dc0 + j;
   *d = (accumulate ? *d : 0.0f) + (float)(s * (double)scale);   // scale: a power of two (pre-scaled operands)
 }
-int place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* src, int src_ld, int rows, int cols,
-          int col0, int transpose) {
+}  // namespace
+
+// ---- host wrappers over the kernels above, shared with nsr_train_arch.hip (declared in nsr_train_work.h)
+int nsr::place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* src, int src_ld, int rows, int cols,
+               int col0, int transpose) {
   const int n = rows * cols;
   hipLaunchKernelGGL(place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, dst_ld, r0, c0, src, src_ld, rows, cols,
                      col0, transpose);
@@ -136,25 +139,37 @@ int place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* s
   return NSR_OK;
 }
 
-// y (P, N) = act(x (P, K) w (N, K)^T + b); `split` (entry e of the pack's split block) selects the split-fp16 product
-int lin_fwd(hipStream_t st, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
-            float* y, int64_t ldy, int64_t P, int N, int n_valid, const unsigned short* split = nullptr, int e = 0) {
+// y (P, N) = act(x (P, K) w (N, K)^T + b); hi / lo (the weights' split-fp16 halves, row stride ldh) select the split-fp16 product
+int nsr::lin_fwd_at(hipStream_t st, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
+                    float* y, int64_t ldy, int64_t P, int N, int n_valid, const unsigned short* hi, const unsigned short* lo,
+                    int ldh) {
   GemmArgs g{};
   g.A = x; g.lda = ldx; g.B = w; g.ldb = ldw; g.C = y; g.ldc = ldy; g.bias = b;
   g.M = P; g.N = N; g.K = K; g.n_valid = n_valid; g.act = act; g.splits = 1;
-  if (!split) return gemm(g, st);
+  if (!hi) return gemm(g, st);
   GemmF16Args a{};
   a.g = g;
   a.g.acc_scale = kSplitInvScale;
-  a.Bh = split + split_offset(e);
-  a.Bl = a.Bh + (int64_t)kSplitRows[e] * kSplitK[e];
-  a.ldbh = kSplitK[e];
+  a.Bh = hi;
+  a.Bl = lo;
+  a.ldbh = ldh;
   return gemm_f16x3(a, st);
 }
+namespace {
+// the default network: `split` (entry e of the pack's split block) selects the split-fp16 product
+int lin_fwd(hipStream_t st, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
+            float* y, int64_t ldy, int64_t P, int N, int n_valid, const unsigned short* split = nullptr, int e = 0) {
+  const unsigned short* hi = split ? split + split_offset(e) : nullptr;
+  return lin_fwd_at(st, x, ldx, K, w, ldw, b, act, y, ldy, P, N, n_valid, hi, hi ? hi + (int64_t)kSplitRows[e] * kSplitK[e] : nullptr,
+                    kSplitK[e]);
+}
+}  // namespace
 // dx (P, N) = (dy (P, K) w[:, 0 : N]) * [mask > 0], w (K, ldw) in the nn.Linear layout (mask may be null);
 // bias_grad (N) (+)= column sums of dx = the bias gradient of the layer that produced the masked activation
-int lin_dgrad(hipStream_t st, const Work& k, const float* dy, int64_t lddy, int K, const float* w, int ldw,
-              const float* mask, int64_t ldm, float* dx, int64_t lddx, int64_t P, int N, float* bias_grad, int acc) {
+// n_bias (0: N): how many of the N columns the bias has (a padded layer's trailing columns are exact zeros)
+int nsr::lin_dgrad(hipStream_t st, const Work& k, const float* dy, int64_t lddy, int K, const float* w, int ldw,
+                   const float* mask, int64_t ldm, float* dx, int64_t lddx, int64_t P, int N, float* bias_grad, int acc,
+                   int n_bias) {
   GemmArgs g{};
   g.A = dy; g.lda = lddy; g.B = w; g.ldb = ldw; g.b_kmajor = 1; g.C = dx; g.ldc = lddx;
   g.mask = mask; g.ldm = ldm; g.M = P; g.N = N; g.K = K; g.n_valid = N; g.act = kActNone; g.splits = 1;
@@ -166,29 +181,31 @@ int lin_dgrad(hipStream_t st, const Work& k, const float* dy, int64_t lddy, int 
   hipLaunchKernelGGL(tilesum_partial_kernel, dim3((N + 63) / 64, slices), dim3(256), 0, st, k.col_tiles, (P + 127) / 128, N,
                      N, part);
   NSR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sum_finish_kernel, dim3((N + 3) / 4), dim3(256), 0, st, part, slices, N, N, bias_grad, acc);
+  const int nb = n_bias > 0 ? n_bias : N;
+  hipLaunchKernelGGL(sum_finish_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, part, slices, N, nb, bias_grad, acc);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
 // partial[z] (M x N) = sum over the z-th slice of the points of dy[p][0..M) x[p][0..N)^T
-int lin_wgrad(hipStream_t st, const float* dy, int64_t lddy, int M, const float* x, int64_t ldx, int N, int64_t P,
-              float* partial, int splits) {
+// (slice z at partial + z * stride)
+int nsr::lin_wgrad(hipStream_t st, const float* dy, int64_t lddy, int M, const float* x, int64_t ldx, int N, int64_t P,
+                   float* partial, int splits, int64_t stride) {
   GemmArgs g{};
   g.A = dy; g.lda = lddy; g.a_kmajor = 1; g.B = x; g.ldb = ldx; g.b_kmajor = 1; g.C = partial; g.ldc = N;
-  g.M = M; g.N = N; g.K = P; g.n_valid = N; g.act = kActNone; g.splits = splits; g.split_stride = kPartialFloats;
+  g.M = M; g.N = N; g.K = P; g.n_valid = N; g.act = kActNone; g.splits = splits; g.split_stride = stride;
   return gemm(g, st);
 }
-int reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows, int cols, const float* partial, int splits,
-                 int p_ld, int pr0, int pc0, int accumulate, float scale = 1.0f) {
+int nsr::reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows, int cols, const float* partial, int splits,
+                      int p_ld, int pr0, int pc0, int accumulate, float scale, int64_t stride) {
   const int n = rows * cols;
   hipLaunchKernelGGL(reduce_place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, dst_ld, dc0, rows, cols, partial,
-                     splits, kPartialFloats, p_ld, pr0, pc0, accumulate, scale);
+                     splits, stride, p_ld, pr0, pc0, accumulate, scale);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
 // `scratch`: >= kSumBlocks * 4 doubles (the split-K partial buffer is free between two weight gradients)
-int colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, float* dst, int accumulate,
-           float* scratch) {
+int nsr::colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, float* dst, int accumulate,
+                float* scratch) {
   if (cols > 4) return NSR_ERR_INVALID_ARG;
   double* part = reinterpret_cast<double*>(scratch);
   hipLaunchKernelGGL(colsum_few_kernel, dim3(kSumBlocks), dim3(256), 0, st, src, ld, P, col0, cols, part);
@@ -197,7 +214,6 @@ int colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, in
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
-}  // namespace
 
 int nsr::prepare_weights(hipStream_t st, const float* const* w, const WeightPack& q, int precision) {
   // zero the whole pack first (padding rows / columns), it is one contiguous block starting at w1p

@@ -319,8 +319,9 @@ class GenericMLP:
     GEMM (``nsr_linear``, include/nsr_train.h) over zero-padded operands -- K and N rounded up to multiples of 32 with
     zero weight columns / rows, whose products are exact zeros -- writing straight into the next layer's input buffer, so
     ``cat([input_xyz, h])`` of a skip layer and ``cat([final, dir])`` are column ranges of one buffer, never copies of
-    activations.  Same interface as ``VanillaMLP`` (``forward(x, sigma_only)``, ``state_dict``, ``check``); inference only
-    (the training step is built for the default architecture)."""
+    activations.  Same interface as ``VanillaMLP`` (``forward(x, sigma_only)``, ``state_dict``, ``check``).  Training such a
+    network is ``train.Trainer(..., arch=)`` / ``train.forward_rays_train(..., arch=)``: the same layout, layer by layer, with the
+    backward products (``nsr_train_arch_forward`` / ``nsr_train_arch_backward``); its ``state_dicts()`` load here."""
 
     POINT_CHUNK = 262144          # rows per pass (the reference's point_chunk, options/base_options.py:70): bounds the buffers
 

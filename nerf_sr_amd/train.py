@@ -20,6 +20,7 @@ over ``nsr_train_forward`` / ``nsr_train_backward`` -- the same kernels, split a
 """
 from __future__ import annotations
 
+import ctypes
 from ctypes import c_void_p
 from typing import Dict, Optional
 
@@ -29,7 +30,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .ops import _f32, _p, _ray_stride, _stream
-from .weights import STATE_DICT_SPEC, check_state_dict, pad_no_dir, DIR_W
+from .weights import STATE_DICT_SPEC, check_state_dict, pad_no_dir, DIR_W, arch_of, arch_spec
 
 OUT_KEYS = ("coarse_comp_rgbs", "coarse_depth", "coarse_opacity", "coarse_weights",
             "fine_comp_rgbs", "fine_depth", "fine_opacity", "fine_weights")
@@ -60,6 +61,17 @@ def _to_dev(sd, device, no_dir: bool = False) -> Dict[str, torch.Tensor]:
         v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
         v = v.to(device=device, dtype=torch.float32)
         out[k] = (pad_no_dir(v) if (no_dir and k == DIR_W) else v).contiguous().clone()
+    return out
+
+
+def _to_dev_arch(sd, device, arch: dict) -> Dict[str, torch.Tensor]:
+    from .weights import check_state_dict_arch
+    check_state_dict_arch(sd, **arch)
+    out = {}
+    for k in arch_spec(**arch):
+        v = sd[k]
+        v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
+        out[k] = v.to(device=device, dtype=torch.float32).contiguous().clone()
     return out
 
 
@@ -132,16 +144,86 @@ def _weights24(params, name: str):
     return [t if t.is_contiguous() else t.contiguous() for t in ts]
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# non-default architectures (--D --W --skips --deg_pos --deg_dir --no_dir): struct nsr_arch of include/nsr_train.h
+# ---------------------------------------------------------------------------------------------------------------------
+ARCH_PRECISIONS = ("fp32", "f16x3_gemm")      # what the layer-by-layer training pair runs; 'f16x3' maps to 'f16x3_gemm'
+_ARCH_WARNED = set()
+
+
+def normalize_arch(arch) -> dict:
+    """``arch`` as the dict ``weights.arch_spec`` takes: a dict with any of D, W, skips, deg_pos, deg_dir, no_dir (absent
+    ones = the reference's defaults), or an options object carrying the reference's flags.  Validates (ValueError)."""
+    a = {**arch_of(None), **arch} if isinstance(arch, dict) else arch_of(arch)
+    a["skips"] = tuple(sorted(set(int(s) for s in a["skips"])))
+    if int(a.get("dim_rgb", 3)) != 3:
+        raise ValueError("arch: dim_rgb must be 3 (the compositor renders three colours)")
+    arch_spec(**a)      # D >= 1, even W, degrees >= 0, skips inside 1 .. D - 1
+    return a
+
+
+def _arch_struct(a: dict) -> "_lib.NsrArch":
+    skips = 0
+    for i in a["skips"]:
+        skips |= 1 << i
+    return _lib.NsrArch(a["D"], a["W"], skips, a["deg_pos"], a["deg_dir"], int(bool(a["no_dir"])))
+
+
+def arch_precision(arch: dict, precision: str) -> str:
+    """The precision the layer-by-layer pair runs for ``precision``: 'fp32' and 'f16x3_gemm' as they are; 'f16x3' (the
+    chain kernels, laid out for the default network) maps to 'f16x3_gemm' -- the same split-fp16 forward products, gradients
+    on the fp32 MFMA -- with one RuntimeWarning per architecture and process; the other chain names raise ValueError."""
+    if precision in ARCH_PRECISIONS:
+        return precision
+    if precision != "f16x3":
+        raise ValueError(f"precision={precision!r} with arch=...: a non-default architecture trains layer by layer under "
+                         f"{list(ARCH_PRECISIONS)} ('f16x3' maps to 'f16x3_gemm'); the chain kernels are the default network's")
+    key = (arch["D"], arch["W"], tuple(arch["skips"]), arch["deg_pos"], arch["deg_dir"], bool(arch["no_dir"]))
+    if key not in _ARCH_WARNED:
+        _ARCH_WARNED.add(key)
+        import warnings
+        warnings.warn(f"training architecture D={arch['D']} W={arch['W']} skips={list(arch['skips'])} degrees "
+                      f"{arch['deg_pos']}/{arch['deg_dir']}: precision 'f16x3' names the chain kernels of the default 8 x 256 "
+                      "network; running 'f16x3_gemm' (layer by layer, forward products split-fp16, gradients fp32)",
+                      RuntimeWarning, stacklevel=3)
+    return "f16x3_gemm"
+
+
+def _weights_arch(params, name: str, arch: dict):
+    """A network's 2 D + 8 tensors in state_dict order for ``arch`` (an nn.Module such as the reference's own ``netCoarse``
+    built with those flags, a dict keyed like ``weights.arch_spec``, or a sequence); shapes checked."""
+    spec = arch_spec(**arch)
+    if isinstance(params, torch.nn.Module):
+        ts = list(params.parameters())
+    elif isinstance(params, dict):
+        missing = [k for k in spec if k not in params]
+        if missing:
+            raise ValueError(f"{name}: missing keys {missing}")
+        ts = [params[k] for k in spec]
+    else:
+        ts = list(params)
+    if len(ts) != len(spec):
+        raise ValueError(f"{name}: expected {len(spec)} tensors for this architecture, got {len(ts)}")
+    for t, (k, shape) in zip(ts, spec.items()):
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name}: {k} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    for t, k in zip(ts, spec):
+        _f32(t, f"{name}.{k}")
+    return [t if t.is_contiguous() else t.contiguous() for t in ts]
+
+
 class _TrainRun:
     """The arguments of one forward_rays_train call that are not tensors."""
 
-    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace):
+    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace, arch=None):
         self.nc, self.ni, self.flags, self.lindisp = nc, ni, flags, lindisp
         self.noise_std, self.prec, self.chunk, self.workspace = noise_std, prec, chunk, workspace
+        self.arch = arch          # None: the default network's pair; else struct nsr_arch (nsr_train_arch_forward / _backward)
 
 
 class _ForwardRaysTrain(torch.autograd.Function):
-    """Outputs: the eight OUT_KEYS tensors.  Inputs: the run, rays, the four draws, then the 48 weight tensors."""
+    """Outputs: the eight OUT_KEYS tensors.  Inputs: the run, rays, the four draws, then both networks' weight tensors (48;
+    2 (2 D + 8) with an architecture)."""
 
     @staticmethod
     def forward(ctx, run, rays, u_c, u_f, n_c, n_f, *weights):
@@ -150,17 +232,22 @@ class _ForwardRaysTrain(torch.autograd.Function):
         dev = rays.device
         outs = [torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, nc, device=dev),
                 torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, nc + ni, device=dev)]
-        nbytes = lib.nsr_train_saved_bytes(run.prec, R, nc, ni, run.chunk)
+        arch = () if run.arch is None else (ctypes.byref(run.arch),)
+        what = "nsr_train_saved_bytes" if run.arch is None else "nsr_train_arch_saved_bytes"
+        nbytes = getattr(lib, what)(*arch, run.prec, R, nc, ni, run.chunk)
         if nbytes == 0:
-            raise _lib.NsrError(f"nsr_train_saved_bytes: no saved state for R={R}, samples {nc} + {ni}, ray_chunk {run.chunk} "
+            raise _lib.NsrError(f"{what}: no saved state for R={R}, samples {nc} + {ni}, ray_chunk {run.chunk} "
                                 "(every ray chunk must hold a multiple of 32 sample points in both networks)")
         saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ctx.ws_need = lib.nsr_train_workspace_bytes_for(run.prec, run.chunk if 0 < run.chunk < R else R, nc, ni)
+        ws_bytes = lib.nsr_train_workspace_bytes_for if run.arch is None else lib.nsr_train_arch_workspace_bytes
+        ctx.ws_need = ws_bytes(*arch, run.prec, run.chunk if 0 < run.chunk < R else R, nc, ni)
         ws = run.workspace.get(ctx.ws_need, dev)
-        _lib.check(lib.nsr_train_forward(
-            _ptr_array(weights[:24]), _ptr_array(weights[24:]), _p(rays), _ray_stride(rays), R, nc, ni, run.flags, run.lindisp,
+        nt = len(weights) // 2
+        fwd, what = (lib.nsr_train_forward, "nsr_train_forward") if run.arch is None else (lib.nsr_train_arch_forward, "nsr_train_arch_forward")
+        _lib.check(fwd(
+            *arch, _ptr_array(weights[:nt]), _ptr_array(weights[nt:]), _p(rays), _ray_stride(rays), R, nc, ni, run.flags, run.lindisp,
             _p(u_c), _p(u_f), _p(n_c), _p(n_f), run.noise_std, run.prec, run.chunk, _ptr_array(outs),
-            _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()), "nsr_train_forward")
+            _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()), what)
         ctx.save_for_backward(*weights)      # an in-place update of a weight before the backward fails autograd's version check
         ctx.run, ctx.state = run, saved
         ctx.set_materialize_grads(False)     # an output the loss does not use arrives as None: a NULL upstream gradient
@@ -177,10 +264,13 @@ class _ForwardRaysTrain(torch.autograd.Function):
         g_outs = [None if g is None else g.to(torch.float32).contiguous() for g in g_outs]
         grads = [torch.empty_like(w) for w in weights]
         ws = ctx.run.workspace.get(ctx.ws_need, saved.device)
-        _lib.check(lib.nsr_train_backward(
-            _ptr_array(weights[:24]), _ptr_array(weights[24:]), (c_void_p * 8)(*[_p(g) for g in g_outs]),
-            _ptr_array(grads[:24]), _ptr_array(grads[24:]), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
-            "nsr_train_backward")
+        run, nt = ctx.run, len(weights) // 2
+        arch = () if run.arch is None else (ctypes.byref(run.arch),)
+        bwd, what = (lib.nsr_train_backward, "nsr_train_backward") if run.arch is None else (lib.nsr_train_arch_backward, "nsr_train_arch_backward")
+        _lib.check(bwd(
+            *arch, _ptr_array(weights[:nt]), _ptr_array(weights[nt:]), (c_void_p * 8)(*[_p(g) for g in g_outs]),
+            _ptr_array(grads[:nt]), _ptr_array(grads[nt:]), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
+            what)
         ctx.state = None
         return (None,) * 6 + tuple(grads)
 
@@ -189,7 +279,7 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
                        N_coarse: int = 64, N_importance: int = 64, white_bkgd: bool = False, lindisp: bool = False,
                        noise_std: float = 0.0, gamma_correct: bool = False, sigma_activation: str = "relu",
                        color_activation: str = "sigmoid", stop_grad: bool = False, precision: str = "f16x3",
-                       ray_chunk: int = 0, workspace: Optional[TrainWorkspace] = None) -> Dict[str, torch.Tensor]:
+                       ray_chunk: int = 0, workspace: Optional[TrainWorkspace] = None, arch=None) -> Dict[str, torch.Tensor]:
     """Train-mode ``forward_rays`` (``models/nerf_downX_model.py:280-313``) that autograd differentiates with respect to the
     24 + 24 weight tensors of ``params_c`` / ``params_f`` (the reference's ``netCoarse`` / ``netFine`` modules, their
     parameter lists, or state-dict-like dicts such as ``Trainer.params``).  Returns the eight ``OUT_KEYS`` outputs; any loss
@@ -198,16 +288,31 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     ``draws``: ``u_coarse`` (R, Nc), ``u_fine`` (R, Ni), ``noise_coarse`` (R, Nc), ``noise_fine`` (R, Nc + Ni) on the device,
     or None for the deterministic branch of that stage (``Trainer.draw`` makes them in the reference's order).  ``ray_chunk``:
     rays per pass (0 = all).  Every call keeps its own saved state (5.4 KB per sample point under 'f16x3', include/nsr_train.h)
-    until its backward; ``workspace`` (shared scratch + the sticky status block) defaults to one per device."""
+    until its backward; ``workspace`` (shared scratch + the sticky status block) defaults to one per device.
+
+    ``arch``: the architecture flags of both networks (a dict with any of D, W, skips, deg_pos, deg_dir, no_dir, or an options
+    object carrying ``--D --W --skips --deg_pos --deg_dir --no_dir``): the layer-by-layer pair ``nsr_train_arch_forward`` /
+    ``nsr_train_arch_backward`` over the 2 D + 8 tensors of each network, e.g. the reference's own ``netCoarse`` /
+    ``netFine`` built with those flags.  ``precision``: 'fp32' or 'f16x3_gemm' ('f16x3' maps to 'f16x3_gemm' with one
+    RuntimeWarning per architecture; the chain names raise ValueError).  None = the default network, as before."""
     if rays.requires_grad:
         raise ValueError("forward_rays_train: rays must not require grad (there is no gradient with respect to rays)")
+    if arch is not None:      # everything about the architecture is checked before a device is touched
+        arch = normalize_arch(arch)
+        if sigma_activation not in ("relu", "softplus") or color_activation not in ("sigmoid", "none"):
+            raise ValueError("sigma_activation: 'relu' or 'softplus'; color_activation: 'sigmoid' or 'none'")
+        if gamma_correct and color_activation == "none":
+            raise ValueError("gamma_correct with color_activation='none': pow(rgb, 1 / 2.2) of an unbounded head is NaN for every negative value")
+        precision = arch_precision(arch, precision)
+        wc, wf = _weights_arch(params_c, "params_c", arch), _weights_arch(params_f, "params_f", arch)
     rays = _f32(rays, "rays")
     _ray_stride(rays)
     if precision not in _lib.TRAIN_PRECISIONS:
         raise ValueError(f"precision must be one of {sorted(_lib.TRAIN_PRECISIONS)}")
     if sigma_activation not in ("relu", "softplus") or color_activation not in ("sigmoid", "none"):
         raise ValueError("sigma_activation: 'relu' or 'softplus'; color_activation: 'sigmoid' or 'none'")
-    wc, wf = _weights24(params_c, "params_c"), _weights24(params_f, "params_f")
+    if arch is None:
+        wc, wf = _weights24(params_c, "params_c"), _weights24(params_f, "params_f")
     for t in wc + wf:
         if t.device != rays.device:
             raise ValueError("the weights must live on the rays' device")
@@ -220,7 +325,7 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     if workspace is None:
         workspace = _DEFAULT_WS.setdefault(rays.device, TrainWorkspace())
     run = _TrainRun(int(N_coarse), int(N_importance), flags, int(bool(lindisp)), float(noise_std),
-                    _lib.TRAIN_PRECISIONS[precision], int(ray_chunk), workspace)
+                    _lib.TRAIN_PRECISIONS[precision], int(ray_chunk), workspace, None if arch is None else _arch_struct(arch))
     outs = _ForwardRaysTrain.apply(run, rays, *d, *wc, *wf)
     return dict(zip(OUT_KEYS, outs))
 
@@ -244,7 +349,15 @@ class Trainer:
                  use_var_loss: bool = False, lambda_coarse_var: float = 0.01, lambda_fine_var: float = 0.01,
                  use_depth_var_loss: bool = False, lambda_coarse_depth_var: float = 0.01, lambda_fine_depth_var: float = 0.01,
                  no_dir: bool = False, sigma_activation: str = "relu", color_activation: str = "sigmoid", stop_grad: bool = False,
-                 grad_clip_val: float = 0.0, grad_clip_type: str = "norm"):
+                 grad_clip_val: float = 0.0, grad_clip_type: str = "norm", arch=None):
+        # arch: the architecture flags of both networks (see forward_rays_train); None = the default network and the fused step.
+        # With an architecture the iteration is forward -> losses in torch -> backward -> Adam over the 2 D + 8 tensors
+        # (nsr_train_arch_forward / _backward, nsr_adam_step_n), --no_dir runs natively as the narrow dir_encoding
+        self.arch = None if arch is None else normalize_arch(arch)
+        if self.arch is not None:
+            precision = arch_precision(self.arch, precision)
+            if bool(no_dir) and not self.arch["no_dir"]:
+                self.arch["no_dir"] = True
         # --grad_clip_val / --grad_clip_type (models/nerf_downX_model.py:403-407): both networks' gradients together, between
         # the backward and the optimiser step; 0 = off
         if grad_clip_type not in ("norm", "value"):
@@ -271,8 +384,11 @@ class Trainer:
         # --no_dir (models/networks.py:160-169): the networks are trained as the full layout with 27 zero columns in
         # dir_encoding's weight (weights.pad_no_dir) whose gradients are dropped every step, so Adam never moves them
         # (m = v = 0 -> update 0): the function, its gradients and the trajectory are the narrow network's
-        self.no_dir = bool(no_dir)
-        self.params = [_to_dev(sd_coarse, self.device, self.no_dir), _to_dev(sd_fine, self.device, self.no_dir)]
+        self.no_dir = bool(no_dir) if self.arch is None else bool(self.arch["no_dir"])
+        if self.arch is None:
+            self.params = [_to_dev(sd_coarse, self.device, self.no_dir), _to_dev(sd_fine, self.device, self.no_dir)]
+        else:
+            self.params = [_to_dev_arch(sd_coarse, self.device, self.arch), _to_dev_arch(sd_fine, self.device, self.arch)]
         flat = [_flat_like(p) for p in self.params]
         self.flat_grads, self.grads = [f for f, _ in flat], [v for _, v in flat]
         self.exp_avg = [_flat_like(p)[1] for p in self.params]
@@ -332,6 +448,8 @@ class Trainer:
         """forward + comp_low_res_output + calculate_losses + backward (:316-396): fills ``self.out``,
         ``self.losses`` (device float[2], UNscaled: this rank's lambda-weighted MSEs) and ``self.grads`` (already
         scaled by 1 / world for the data-parallel SUM, see ``grad_scale``)."""
+        if self.arch is not None:
+            return self._loss_and_grads_arch(draws)
         from .dist import _world
         gs = float(self.grad_scale) if self.grad_scale is not None else 1.0 / _world(self.group)[1]
         rays = self.data_rays
@@ -389,6 +507,41 @@ class Trainer:
         self.out = o
         return self.losses, self.grads
 
+    def _loss_and_grads_arch(self, draws=None):
+        """``loss_and_grads`` of a non-default architecture: the autograd pair with the reference's losses written in torch
+        (comp_low_res_output + calculate_losses, models/nerf_downX_model.py:326-378): s^2 means, the two lambda-weighted
+        MSEs, the variance terms when they are on."""
+        rays = self.data_rays
+        R = rays.shape[0]
+        out = self.forward(draws)
+        n_lr = R // self.s2
+        lr_c = out["coarse_comp_rgbs"].view(n_lr, self.s2, 3).mean(1)
+        lr_f = out["fine_comp_rgbs"].view(n_lr, self.s2, 3).mean(1)
+        mse = torch.nn.functional.mse_loss
+        loss_c, loss_f = mse(lr_c, self.data_rgbs) * self.lambda_coarse, mse(lr_f, self.data_rgbs) * self.lambda_fine
+        total = loss_c + loss_f
+        self.var_losses = torch.zeros(4, dtype=torch.float32, device=self.device)
+        if any(self.lambda_var):
+            var_of = lambda t: torch.sum(torch.var(t.reshape(n_lr, self.s2, -1), dim=1))
+            terms = [None] * 4
+            if any(self.lambda_var[:2]):
+                terms[0], terms[1] = var_of(out["coarse_comp_rgbs"]), var_of(out["fine_comp_rgbs"])
+            if any(self.lambda_var[2:]):
+                # self.far of the reference (:284): the far bound of the first ray of the last ray chunk
+                chunk = min(self.ray_chunk, R) if self.ray_chunk > 0 else R
+                far = rays[((R - 1) // chunk) * chunk, 7]
+                terms[2], terms[3] = var_of(out["coarse_depth"] / far), var_of(out["fine_depth"] / far)
+            for i, (lam, t) in enumerate(zip(self.lambda_var, terms)):
+                if lam and t is not None:
+                    total = total + lam * t
+                    self.var_losses[i] = (lam * t).detach()
+        self.losses = torch.stack([loss_c.detach(), loss_f.detach()])
+        self.backward(total)
+        o = {k: v.detach() for k, v in out.items()}
+        o["lr_coarse"], o["lr_fine"] = lr_c.detach(), lr_f.detach()
+        self.out = o
+        return self.losses, self.grads
+
     # -- autograd protocol: forward() -> any loss in torch -> backward(loss) -> [clip_grads()] -> optimizer_step() ---------
     def _weight_leaves(self):
         """Per network 24 tensors that alias ``self.params`` and require grad (autograd leaves; they share the storage and the
@@ -411,7 +564,7 @@ class Trainer:
                                   white_bkgd=self.white_bkgd, lindisp=self.lindisp, noise_std=self.noise_std,
                                   gamma_correct=self.gamma_correct, sigma_activation=self.sigma_activation,
                                   color_activation=self.color_activation, stop_grad=self.stop_grad, precision=self.precision,
-                                  ray_chunk=self.ray_chunk, workspace=self._workspace)
+                                  ray_chunk=self.ray_chunk, workspace=self._workspace, arch=self.arch)
 
     def backward(self, loss: torch.Tensor):
         """d(loss)/d(weights) of the forwards behind ``loss`` into ``self.grads`` / ``self.flat_grads`` (OVERWRITTEN; scaled by
@@ -427,7 +580,7 @@ class Trainer:
         for d, g in zip(dst, grads):
             if g is None:
                 d.zero_()
-        if self.no_dir:
+        if self.no_dir and self.arch is None:
             for g in self.grads:
                 g[DIR_W][:, 256:].zero_()
         return self.grads
@@ -475,6 +628,14 @@ class Trainer:
         """torch.optim.Adam.step over both networks (:201-204, :408)."""
         self.step += 1
         for n in range(2):
+            if self.arch is not None:
+                ps = list(self.params[n].values())
+                numel = (ctypes.c_int64 * len(ps))(*[p.numel() for p in ps])
+                _lib.check(_lib.load().nsr_adam_step_n(
+                    len(ps), numel, _ptr_array(ps), _ptr_array(list(self.grads[n].values())),
+                    _ptr_array(list(self.exp_avg[n].values())), _ptr_array(list(self.exp_avg_sq[n].values())),
+                    self.step, self.lr, self.beta1, self.beta2, self.eps, _stream()), "nsr_adam_step_n")
+                continue
             _lib.check(_lib.load().nsr_adam_step(
                 _ptr_array(list(self.params[n].values())), _ptr_array(list(self.grads[n].values())),
                 _ptr_array(list(self.exp_avg[n].values())), _ptr_array(list(self.exp_avg_sq[n].values())),
@@ -537,4 +698,6 @@ class Trainer:
         return self.lr
 
     def state_dicts(self):
+        if self.arch is not None:
+            return [{k: v.clone() for k, v in p.items()} for p in self.params]
         return [{k: (v[:, :256] if (self.no_dir and k == DIR_W) else v).clone() for k, v in p.items()} for p in self.params]
