@@ -57,6 +57,40 @@ int nsr_refine_pack_weights_noref(const float* const* tensors, void* packed, int
 int nsr_refine_forward_noref(const void* packed, int precision, const float* x_synth, int B, int H, int W, float* out,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- training (MaxPoolingModel in .train(), models/refine_model.py:84-175): fp32 forward / backward pair over the
+ * RAW (unfolded) tensors, with the reference patches (--not_use_ref is not trainable here).  BatchNorm2d normalises with
+ * the batch statistics of the call (biased variance, eps 1e-5); the encoder runs on the B synthesised and on the B R
+ * reference patches with the same weights, each call on ITS OWN statistics, its weight gradients are the sum over both.
+ * Parameters (NSR_REFINE_N_PARAMS = 72): per layer weight, bias and, with a BatchNorm, its weight, bias -- the order
+ * above without the running statistics.  `running`: HOST array of the 34 running_mean / running_var DEVICE pointers in
+ * layer order, updated in place with `momentum` (running_var from the UNBIASED variance; the encoder's twice per
+ * forward: synthesised call, then reference call), or NULL to leave them alone.
+ * The 17 convolution biases in front of a BatchNorm are cancelled by its mean subtraction: their gradients are DEFINED
+ * as exact zeros and not computed (the reference's fp32 autograd leaves ~1e-7 of rounding noise there).
+ * Shapes: H, W multiples of 8 (NSR_ERR_UNSUPPORTED otherwise), B >= 1, 1 <= R <= 255, B H W / 64 >= 2 (a BatchNorm needs
+ * two values per channel; NSR_ERR_INVALID_ARG).  `img_chunk`: images whose im2col matrix is live at once (<= 0: the
+ * library picks, at most 1 GiB); it bounds the workspace, never the batch statistics, and the outputs do not depend on
+ * it bit for bit (the weight gradients' summation order does).
+ * `saved` (256-byte aligned) carries the run from the forward to its backward: a header (magic, B, R, H, W, img_chunk),
+ * the inputs, at most the pre-activation and the output of every layer, the per-layer mean / 1 / std and the winner
+ * indices of the four maxima: (787 R + 2398) H W floats + 232 H W bytes per patch set -- 143 MB for R = 8 at 64 x 64.
+ * The backward does not modify it: a second backward gives the same bits.  A buffer no forward wrote is
+ * NSR_ERR_INVALID_ARG, one shorter than its header says NSR_ERR_WORKSPACE.  The backward reads the header back (it waits
+ * for the stream); everything is validated before anything is enqueued.  Every reduction runs in a fixed order without
+ * float atomics: identical calls give identical bits.  No gradient with respect to the images; no status word
+ * (non-finite values travel as in torch). */
+#define NSR_REFINE_N_PARAMS 72
+size_t nsr_refine_train_workspace_bytes(int B, int R, int H, int W, int img_chunk);
+size_t nsr_refine_train_saved_bytes(int B, int R, int H, int W);
+/* tensors: the NSR_REFINE_N_TENSORS of nsr_refine_pack_weights, raw; x_synth (B, 3, H, W), x_candi (B, R, 3, H, W),
+ * out (B, 3, H, W) */
+int nsr_refine_train_forward(const float* const* tensors, float* const* running, float momentum, const float* x_synth,
+                             const float* x_candi, int B, int R, int H, int W, int img_chunk, float* out, void* workspace,
+                             size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream);
+/* g_out (B, 3, H, W) = dL/d out; grads: HOST array of NSR_REFINE_N_PARAMS DEVICE pointers, OVERWRITTEN */
+int nsr_refine_train_backward(const float* const* tensors, const float* g_out, float* const* grads, void* workspace,
+                              size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream);
+
 /* ---- patch tiler / stitcher around the network (the 'test' path of data/llff_refine_dataset.py:303-340 and
  * models/refine_model.py:205-216): an SR image is cut into `patch` x `patch` tiles on a grid (x outer, y inner, starts
  * clamped to size - patch); each tile gets `n_ref` reference patches whose top-left corners are the first `n_ref`

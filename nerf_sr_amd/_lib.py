@@ -114,6 +114,12 @@ SIGNATURES = {
     "nsr_refine_packed_bytes_noref": (c_size_t, [c_int]),
     "nsr_refine_pack_weights_noref": (c_int, [POINTER(c_void_p), c_void_p, c_int, c_void_p]),
     "nsr_refine_forward_noref": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nsr_refine_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "nsr_refine_train_saved_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "nsr_refine_train_forward": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                         c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "nsr_refine_train_backward": (c_int, [POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_size_t,
+                                          c_void_p]),
     "nsr_refine_tile": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "nsr_refine_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                   c_void_p, c_void_p]),

@@ -35,6 +35,7 @@ UNITS = [
     ("nsr_train_chain.hip", ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     ("nsr_warp.hip", ["-ffp-contract=off"]),
     ("nsr_refine.hip", ["-ffp-contract=off"]),
+    ("nsr_refine_train.hip", ["-ffp-contract=off"]),
     ("nsr_image.hip", ["-ffp-contract=off"]),
     ("nsr_api.hip", []),
 ]

@@ -4,15 +4,22 @@
 ``x_synth`` (B, 3, H, W) and ``list_x_candi`` (B, R, 3, H, W) in [-1, 1] -> refined patch (B, 3, H, W) (tanh).
 Weights enter as the reference's ``state_dict`` (``load_state_dict``; the int64 ``num_batches_tracked`` entries are
 ignored).  All arithmetic runs in libnsr.so; there is no CPU path.
+
+Training (fp32, with reference patches): ``forward_train`` is the train-mode network as a ``torch.autograd.Function``
+over the 72 parameter tensors, ``RefineTrainer`` mirrors ``RefineModel``'s protocol (models/refine_model.py:84-175:
+L1 / MSE loss, Adam) on top of it.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
+import ctypes
 from ctypes import c_void_p
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 import torch
+
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .ops import _f32, _p, _stream
@@ -51,6 +58,11 @@ def _spec(not_use_ref: bool = False) -> "OrderedDict[str, tuple]":
 REFINE_SPEC = _spec()
 REFINE_SPEC_NOREF = _spec(True)
 assert len(REFINE_SPEC) == 106 and len(REFINE_SPEC_NOREF) == 106
+#: the 72 trainable tensors (per layer: conv weight, bias, then the BatchNorm's weight, bias) and the 34 running-statistics
+#: tensors (state, not parameters), both in state_dict order
+TRAIN_PARAM_KEYS = [k for k in REFINE_SPEC if "running_" not in k]
+RUNNING_KEYS = [k for k in REFINE_SPEC if "running_" in k]
+assert len(TRAIN_PARAM_KEYS) == 72 and len(RUNNING_KEYS) == 34
 
 
 def make_refine_state_dict(seed: int, not_use_ref: bool = False) -> Dict[str, np.ndarray]:
@@ -220,3 +232,198 @@ def refine_image(net: MaxPoolingModel, sr_img: torch.Tensor, ref_img: torch.Tens
     sr, ref = gather_patches(sr_img, ref_img, starts, refs, patch_len)
     pred = torch.cat([net(sr[i:i + batch], ref[i:i + batch]) for i in range(0, sr.shape[0], batch)], 0)
     return stitch_patches(pred, starts, (sr_img.shape[2], sr_img.shape[1]))
+
+
+# ------------------------------------------------------------------------------------------------------- training
+_TRAIN_WS: Dict[torch.device, torch.Tensor] = {}     # scratch of the train-mode pair, one per device (grows, never shrinks)
+
+
+def _train_workspace(need: int, dev) -> torch.Tensor:
+    ws = _TRAIN_WS.get(dev)
+    if ws is None or ws.numel() < need:
+        _TRAIN_WS[dev] = ws = None                   # free the old one first
+        _TRAIN_WS[dev] = ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _ptr_array(tensors):
+    return (c_void_p * len(tensors))(*[c_void_p(t.data_ptr()) for t in tensors])
+
+
+class _TrainRun:
+    """The arguments of one forward_train call that are not differentiable tensors."""
+
+    def __init__(self, running, momentum, img_chunk):
+        self.running, self.momentum, self.img_chunk = running, momentum, img_chunk
+
+    def tensors106(self, params):
+        by_name = dict(zip(TRAIN_PARAM_KEYS, params))
+        by_name.update(zip(RUNNING_KEYS, self.running))
+        return _ptr_array([by_name[k] for k in REFINE_SPEC])
+
+
+class _ForwardTrain(torch.autograd.Function):
+    """Output: the refined patches (B, 3, H, W).  Inputs: the run, the two image tensors, the 72 parameter tensors."""
+
+    @staticmethod
+    def forward(ctx, run, x, c, *params):
+        lib = _lib.load()
+        B, _, H, W = x.shape
+        R = c.shape[1]
+        nbytes = lib.nsr_refine_train_saved_bytes(B, R, H, W)
+        if nbytes == 0:
+            raise ValueError(f"forward_train: no train-mode network for B={B}, R={R}, {H} x {W}: H and W must be multiples of 8, "
+                             "1 <= R <= 255 and B * H * W / 64 >= 2 (a BatchNorm needs two values per channel)")
+        ctx.ws_need = lib.nsr_refine_train_workspace_bytes(B, R, H, W, run.img_chunk)
+        ws = _train_workspace(ctx.ws_need, x.device)
+        saved = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        out = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
+        _lib.check(lib.nsr_refine_train_forward(run.tensors106(params), _ptr_array(run.running), run.momentum, _p(x), _p(c), B, R, H, W,
+                                                run.img_chunk, _p(out), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
+                   "nsr_refine_train_forward")
+        ctx.save_for_backward(*params)       # an in-place update of a weight before the backward fails autograd's version check
+        ctx.run, ctx.state = run, saved
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        params, saved = ctx.saved_tensors, ctx.state
+        if saved is None:
+            raise RuntimeError("forward_train: the saved state of this forward was released by its first backward")
+        grads = [torch.empty_like(p) for p in params]
+        ws = _train_workspace(ctx.ws_need, saved.device)
+        g_out = g_out.to(torch.float32).contiguous()
+        _lib.check(_lib.load().nsr_refine_train_backward(ctx.run.tensors106(params), _p(g_out), _ptr_array(grads), _p(ws), ws.numel(),
+                                                         _p(saved), saved.numel(), _stream()), "nsr_refine_train_backward")
+        ctx.state = None
+        return (None, None, None) + tuple(grads)
+
+
+def forward_train(params, running, x_synth: torch.Tensor, list_x_candi: torch.Tensor, momentum: float = 0.1,
+                  img_chunk: Optional[int] = None) -> torch.Tensor:
+    """``MaxPoolingModel.forward`` in train mode (networks.py:964-990 under ``.train()``): BatchNorm normalises with the batch
+    statistics of each call (the encoder's two calls each with their own), fp32.  ``params``: name -> CUDA fp32 leaf for the 72
+    ``TRAIN_PARAM_KEYS``; ``running``: name -> tensor for the 34 ``RUNNING_KEYS``, updated IN PLACE (momentum; the encoder's
+    twice).  Returns ``y`` (B, 3, H, W); any loss written in torch over it back-propagates through ``nsr_refine_train_backward``
+    into the 72 parameters (once: the backward is not differentiable).  The 17 convolution biases in front of a BatchNorm get
+    exact-zero gradients (include/nsr_refine.h).  There is no gradient with respect to the images (None).
+    ``img_chunk``: images whose im2col matrix is live at once (None: the library picks)."""
+    missing = [k for k in TRAIN_PARAM_KEYS if k not in params] + [k for k in RUNNING_KEYS if k not in running]
+    if missing:
+        raise KeyError(f"forward_train: missing {missing[:3]}{'...' if len(missing) > 3 else ''}")
+    x, c = _f32(x_synth.detach(), "x_synth"), _f32(list_x_candi.detach(), "list_x_candi")
+    if x.ndim != 4 or x.shape[1] != 3 or c.ndim != 5 or c.shape[0] != x.shape[0] or tuple(c.shape[2:]) != tuple(x.shape[1:]):
+        raise ValueError("expected x_synth (B, 3, H, W) and list_x_candi (B, R, 3, H, W)")
+    ps, rs = [params[k] for k in TRAIN_PARAM_KEYS], [running[k] for k in RUNNING_KEYS]
+    for k, t in list(zip(TRAIN_PARAM_KEYS, ps)) + list(zip(RUNNING_KEYS, rs)):
+        if not isinstance(t, torch.Tensor) or t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous() \
+                or tuple(t.shape) != tuple(REFINE_SPEC[k]):
+            raise ValueError(f"forward_train: {k} must be a contiguous float32 tensor of shape {REFINE_SPEC[k]} on {x.device}")
+    run = _TrainRun(rs, float(momentum), 0 if img_chunk is None else int(img_chunk))
+    return _ForwardTrain.apply(run, x, c, *ps)
+
+
+class RefineTrainer:
+    """``RefineModel``'s training protocol (models/refine_model.py:84-175) for the ``MaxPoolingModel`` with reference patches,
+    fp32: ``set_input`` -> ``forward`` -> ``calculate_losses`` -> ``backward`` -> ``optimizer_step`` (``optimize_parameters``
+    does the four), Adam(lr, betas=(beta1, 0.999)) over the 72 parameters.  ``sd``: the reference's ``state_dict`` (tensors or
+    arrays).  Losses other than L1 / MSE are not built in: compose them in torch over ``forward_train``."""
+
+    def __init__(self, sd, lr: float = 5e-4, beta1: float = 0.9, refine_with_l1: bool = True, refine_with_mse: bool = False,
+                 lambda_refine_l1: float = 1.0, lambda_refine_mse: float = 10.0, device="cuda", *, refine_with_vgg: bool = False,
+                 refine_with_grad: bool = False, refine_as_gan: bool = False, precision: str = "fp32", not_use_ref: bool = False,
+                 momentum: float = 0.1, img_chunk: Optional[int] = None, beta2: float = 0.999, eps: float = 1e-8):
+        # every option is checked before a device is touched
+        for name, on in (("refine_with_vgg", refine_with_vgg), ("refine_with_grad", refine_with_grad), ("refine_as_gan", refine_as_gan)):
+            if on:
+                raise NotImplementedError(f"RefineTrainer: {name} is not built in; compose that loss in torch over "
+                                          "nerf_sr_amd.refine.forward_train, which back-propagates any torch loss")
+        if precision != "fp32":
+            raise ValueError(f"RefineTrainer: precision must be 'fp32' (got {precision!r}): the refinement network trains in fp32 only")
+        if not_use_ref:
+            raise NotImplementedError("RefineTrainer: --not_use_ref training is not supported (inference is: MaxPoolingModel(not_use_ref=True))")
+        if not (refine_with_l1 or refine_with_mse):
+            raise ValueError("RefineTrainer: no loss selected (refine_with_l1 / refine_with_mse)")
+        missing = [k for k in REFINE_SPEC if k not in sd]
+        if missing:
+            raise KeyError(f"state_dict lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
+        self.device = torch.device(device)
+        self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
+        self.refine_with_l1, self.refine_with_mse = bool(refine_with_l1), bool(refine_with_mse)
+        self.lambda_refine_l1, self.lambda_refine_mse = float(lambda_refine_l1), float(lambda_refine_mse)
+        self.momentum, self.img_chunk = float(momentum), img_chunk
+        dev = OrderedDict()
+        for k, shape in REFINE_SPEC.items():
+            v = sd[k]
+            v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
+            if tuple(v.shape) != tuple(shape):
+                raise ValueError(f"{k}: expected shape {shape}, got {tuple(v.shape)}")
+            dev[k] = v.to(device=self.device, dtype=torch.float32).contiguous().clone()
+        self.params = OrderedDict((k, dev[k].requires_grad_(True)) for k in TRAIN_PARAM_KEYS)
+        self.running = OrderedDict((k, dev[k]) for k in RUNNING_KEYS)
+        self.exp_avg = OrderedDict((k, torch.zeros_like(v)) for k, v in self.params.items())
+        self.exp_avg_sq = OrderedDict((k, torch.zeros_like(v)) for k, v in self.params.items())
+        self.step = 0
+        self.pred = None
+
+    def set_input(self, input):
+        for name in ("sr_patch", "ref_patches", "gt_patch"):
+            setattr(self, f"data_{name}", input[name].to(device=self.device, dtype=torch.float32).contiguous())
+
+    def forward(self):
+        self.pred = forward_train(self.params, self.running, self.data_sr_patch, self.data_ref_patches, self.momentum, self.img_chunk)
+        return self.pred
+
+    def calculate_losses(self):
+        """refine_model.py:151-168: lambda-weighted L1 / MSE (reduction 'mean'), their sum, PSNR of the input and the output."""
+        zero = torch.zeros((), device=self.device)
+        self.loss_l1 = torch.nn.functional.l1_loss(self.pred, self.data_gt_patch) * self.lambda_refine_l1 if self.refine_with_l1 else zero
+        self.loss_mse = torch.nn.functional.mse_loss(self.pred, self.data_gt_patch) * self.lambda_refine_mse if self.refine_with_mse else zero
+        self.loss_tot = self.loss_mse + self.loss_l1
+        with torch.no_grad():
+            psnr = lambda a, b: -10.0 * torch.log10(torch.mean((a - b) ** 2))
+            self.loss_psnr_input = psnr(self.data_sr_patch, self.data_gt_patch)
+            self.loss_psnr_refine = psnr(self.pred, self.data_gt_patch)
+
+    def backward(self):
+        self.calculate_losses()
+        for p in self.params.values():
+            p.grad = None
+        self.loss_tot.backward()
+
+    def optimizer_step(self):
+        """torch.optim.Adam.step over the 72 parameters: nsr_adam_step_n, at most 40 tensors per call."""
+        self.step += 1
+        keys = [k for k in TRAIN_PARAM_KEYS if self.params[k].grad is not None]
+        for i in range(0, len(keys), 40):
+            g = keys[i:i + 40]
+            numel = (ctypes.c_int64 * len(g))(*[self.params[k].numel() for k in g])
+            _lib.check(_lib.load().nsr_adam_step_n(
+                len(g), numel, _ptr_array([self.params[k] for k in g]), _ptr_array([self.params[k].grad for k in g]),
+                _ptr_array([self.exp_avg[k] for k in g]), _ptr_array([self.exp_avg_sq[k] for k in g]),
+                self.step, self.lr, self.beta1, self.beta2, self.eps, _stream()), "nsr_adam_step_n")
+        # the weights were written behind autograd's back: the backward of a forward made before this step must fail the
+        # version check instead of mixing two sets of weights
+        torch.autograd.graph.increment_version(list(self.params.values()))
+
+    def optimize_parameters(self):
+        self.forward()
+        self.backward()
+        self.optimizer_step()
+        return self.loss_tot.detach()
+
+    def update_learning_rate(self, epoch: int, lr_policy: str = "exp", **kw) -> float:
+        """The reference's per-epoch schedules, the arithmetic of ``train.Trainer.update_learning_rate``."""
+        from .train import Trainer
+        return Trainer.update_learning_rate(self, epoch, lr_policy, **kw)
+
+    def state_dict(self):
+        sd = OrderedDict()
+        for k in REFINE_SPEC:
+            sd[k] = (self.params[k] if k in self.params else self.running[k]).detach().clone()
+        return sd
+
+    def eval_model(self, precision: str = "f16x3") -> MaxPoolingModel:
+        """The eval-mode network (BatchNorm folded on the running statistics) of the current state."""
+        return MaxPoolingModel(precision=precision, device=self.device).load_state_dict(self.state_dict())
