@@ -136,9 +136,11 @@ int nsr_train_loss_and_grads_var(const float* const* w_coarse, const float* cons
  * anything is enqueued.  It ORs the same NSR_FLAG_* bits into the workspace's sticky status block (nsr_train_status).
  * What the backward needs stays in the caller's `saved` buffer (>= nsr_train_saved_bytes, 256-byte aligned; one per forward
  * call that is still to be differentiated -- the workspace is scratch and may be shared by any number of them): a header with
- * the run's parameters, the backward weight streams of both networks (NSR_F16X3*), and per ray chunk and network the (rgb,
- * sigma) of every sample point, its depth z, and the forward activations -- the chain kernels' 2-byte panels and sign words
- * (NSR_F16X3*) or the per-layer fp32 matrices (NSR_FP32, NSR_F16X3_GEMM).  At the bench's training batch (2,048 rays,
+ * the run's parameters and the network's descriptor (nsr_arch below; the default network's here), the backward weight streams of
+ * both networks (NSR_F16X3*), and per ray chunk and network the (rgb, sigma) of every sample point, its depth z, and the forward
+ * activations -- the chain kernels' 2-byte panels and sign words (NSR_F16X3*) or the per-layer fp32 matrices (NSR_FP32,
+ * NSR_F16X3_GEMM).  The format is one for nsr_train_forward and nsr_train_arch_forward; it is opaque and belongs to the
+ * library build that wrote it.  At the bench's training batch (2,048 rays,
  * 64 + 64 samples = 393,216 sample points, one chunk): 2.13 GB under NSR_F16X3 (5.4 KB per sample point; the two weight streams
  * are 6 MB of it), 3.99 GB under NSR_FP32 (10.1 KB per point).
  * nsr_train_saved_bytes: 0 on invalid arguments (R <= 0 included); depends on its arguments only.
@@ -150,8 +152,8 @@ int nsr_train_loss_and_grads_var(const float* const* w_coarse, const float* cons
  * internally the result is bit-identical to nsr_train_loss_and_grads.  R, the sample counts, render_flags, precision and
  * ray_chunk are read back from `saved` (the call waits for the stream to read the header: at the bench's batch the GPU idles
  * ~30 us in front of the backward, and the call cannot be captured into a graph): a buffer that no forward call
- * wrote is NSR_ERR_INVALID_ARG, one smaller than its header says NSR_ERR_WORKSPACE; the workspace must be large enough for
- * that run (nsr_train_workspace_bytes_for).  The weights must be the forward call's (the GEMM path re-reads them).  `saved`
+ * wrote -- or one that nsr_train_arch_forward wrote for another network than the default -- is NSR_ERR_INVALID_ARG, one smaller
+ * than its header says NSR_ERR_WORKSPACE; the workspace must be large enough for that run (nsr_train_workspace_bytes_for).  The weights must be the forward call's (the GEMM path re-reads them).  `saved`
  * is not modified: a second backward of the same forward is allowed and gives the same gradients. */
 size_t nsr_train_saved_bytes(int precision, int64_t R, int n_coarse, int n_importance, int64_t ray_chunk);
 int nsr_train_forward(const float* const* w_coarse, const float* const* w_fine, const float* rays, int ray_stride, int64_t R,
@@ -181,9 +183,10 @@ int nsr_adam_step(float* const* w, const float* const* g, float* const* m, float
                   float beta1, float beta2, float eps, void* stream);
 
 /* ---- Training a network of any architecture the reference's flags describe (--D --W --skips --deg_pos --deg_dir --no_dir;
- * models/networks.py:124-169, models/nerf_model.py:53-57).  The entry points above are laid out for the default network
- * (8 x 256, skip at layer 4, degrees 10 / 4); the ones below take a descriptor and run layer by layer on the same GEMM
- * kernels (csrc/nsr_train_arch.hip).  The default network is a valid descriptor here too: {8, 256, 1u << 4, 10, 4, 0}.
+ * models/networks.py:124-169, models/nerf_model.py:53-57).  The entry points above run the default network (8 x 256, skip at
+ * layer 4, degrees 10 / 4); the ones below take a descriptor.  There is ONE layer-by-layer network (csrc/nsr_train_gemm.hip), a
+ * function of the descriptor: under NSR_FP32 / NSR_F16X3_GEMM the entry points above are the ones below with the descriptor
+ * {8, 256, 1u << 4, 10, 4, 0}, bit for bit (the chain precisions exist for that network only, through the entry points above).
  *
  * State tensors: 2 D + 8, in the order of the reference module's state_dict() (nerf_sr_amd.weights.arch_spec):
  *   xyz_encoding_{i+1}.0.weight (W, fan_in) / .bias (W) for i = 0 .. D-1, fan_in = 3 + 6 deg_pos for layer 0,
@@ -223,7 +226,8 @@ size_t nsr_train_arch_saved_bytes(const nsr_arch* arch, int precision, int64_t R
  * header records the descriptor: a backward with another descriptor, a buffer no forward wrote or a damaged header is
  * NSR_ERR_INVALID_ARG, a buffer shorter than its header says NSR_ERR_WORKSPACE.  The weights must be the forward call's.
  * Weight matrices must be 16-byte aligned (a trunk layer whose shape needs no padding is the GEMMs' operand where the caller
- * holds it): NSR_ERR_INVALID_ARG otherwise, like every other check before anything is enqueued.
+ * holds it): NSR_ERR_INVALID_ARG otherwise, before anything is enqueued.  The same holds for nsr_train_loss_and_grads[_var],
+ * nsr_train_forward and nsr_train_backward under NSR_FP32 / NSR_F16X3_GEMM.
  * Weight gradients are reduced in a fixed order (no atomics): two identical calls give identical bits. */
 int nsr_train_arch_forward(const nsr_arch* arch, const float* const* w_coarse, const float* const* w_fine, const float* rays,
                            int ray_stride, int64_t R, int n_coarse, int n_importance, int render_flags, int lindisp,

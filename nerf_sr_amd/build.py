@@ -31,7 +31,6 @@ UNITS = [
     ("nsr_train_wgrad.hip", ["-ffp-contract=off"]),
     ("nsr_train.hip", ["-ffp-contract=off"]),
     ("nsr_train_gemm.hip", ["-ffp-contract=off"]),
-    ("nsr_train_arch.hip", ["-ffp-contract=off"]),
     ("nsr_train_chain.hip", ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     ("nsr_warp.hip", ["-ffp-contract=off"]),
     ("nsr_refine.hip", ["-ffp-contract=off"]),

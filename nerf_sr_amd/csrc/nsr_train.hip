@@ -12,12 +12,15 @@
 // open_work) and the loop (for_each_pass).
 //
 // The network itself has two implementations, selected by the precision argument:
-//   CHAIN path (NSR_F16X3 and its _BWD* variants; the default): the network is a per-point chain.  Its forward pass is the
-//   inference kernel (nsr_mlp_f16.hip, TRAIN) that additionally keeps every layer's activation as the fp16 operand it makes
-//   anyway; the input gradients are one launch of the backward chain (nsr_train_chain.hip), which keeps its fp16 operands
-//   likewise.  Both write 2-byte "panels" in 1 KiB units (nsr_f16x3_core.h) that the weight gradients are computed from
-//   (nsr_train_wgrad.hip, chain_weight_grads).
-//   GEMM path (NSR_FP32, NSR_F16X3_GEMM): layer by layer on the GEMM kernels, nsr_train_gemm.hip.
+//   CHAIN path (NSR_F16X3 and its _BWD* variants; the default network only): the network is a per-point chain.  Its forward
+//   pass is the inference kernel (nsr_mlp_f16.hip, TRAIN) that additionally keeps every layer's activation as the fp16 operand
+//   it makes anyway; the input gradients are one launch of the backward chain (nsr_train_chain.hip), which keeps its fp16
+//   operands likewise.  Both write 2-byte "panels" in 1 KiB units (nsr_f16x3_core.h) that the weight gradients are computed
+//   from (nsr_train_wgrad.hip, chain_weight_grads).
+//   LAYER-BY-LAYER network (NSR_FP32, NSR_F16X3_GEMM): nsr_train_gemm.hip, a function of an architecture descriptor.
+// and two families of entry points over the SAME drivers: nsr_train_* run the default network (the descriptor
+// {8, 256, skips {4}, 10, 4, 0} on the layer-by-layer precisions), nsr_train_arch_* the network of the caller's descriptor
+// (layer-by-layer precisions only).  One saved-state header and layout serves both; it records the descriptor.
 // Per-ray stages (sampling, compositing, resampling) are the inference kernels (nsr_rays.hip / nsr_render.hip); the
 // compositing backward is a one-wave-per-ray kernel like its forward.  The kernels both paths use, and Adam, are here.
 #include <initializer_list>
@@ -160,22 +163,21 @@ __device__ __forceinline__ float colour_head_bwd(float g, float y, int head) {
 // are y = s^(1/2.2), s = sigmoid(pre), and dy/d(pre) = s^(1/2.2 - 1) s (1 - s) / 2.2 = y (1 - y^2.2) / 2.2.
 // `white`: the training entry points' option word (include/nsr_train.h).  NSR_SIGMA_SOFTPLUS: density log(1 + exp(sigma - 1)),
 // whose slope sigmoid(sigma - 1) replaces [sigma > 0]; NSR_TRAIN_COLOR_NONE: no colour activation, slope 1.
-// Outputs in the GEMM path's training layout: d_rgb (P, 32) columns 0..2 (3..31 zeroed); d_sigma into column 256 of
-// g1 (P, 288) (257..287 zeroed).  COMPACT (chain path): one float4 per point, d4[p] = (d_rgb_pre 0..2, d_sigma) -- 16 bytes
-// instead of 256 written per point, and one 16-byte read per point for the backward chain instead of two strided ones.
+// Output: one float4 per point, d4[p] = (d_rgb_pre 0..2, d_sigma).  gmax (may be null): the backward chain's ten gmax words,
+// cleared here.  bias_part (may be null): per ray, the sums of the four values over its points.
 // FULL (nsr_train_backward: upstream gradients of every output): gw_k also takes + g_opacity (opacity = sum_k w_k) and
 // + g_weights[k]; either pointer may be null.  The fused step's instantiations (FULL = false) do not contain the two terms.
-template <int K, bool COMPACT, bool FULL>
+template <int K, bool FULL>
 __global__ void __launch_bounds__(256) composite_bwd_kernel(const float* __restrict__ rgb4, const float* __restrict__ sigma,
                                                             const float* __restrict__ z, const float* __restrict__ g_comp,
                                                             int64_t R, int N, int white,
-                                                            float* __restrict__ d_rgb, float* __restrict__ g1,
+                                                            float* __restrict__ d4, unsigned* __restrict__ gmax,
                                                             const float* __restrict__ g_depth, float* __restrict__ bias_part,
                                                             const float* __restrict__ g_opacity, const float* __restrict__ g_weights) {
   const int lane = threadIdx.x & 63;
-  // COMPACT (chain path): `g1` carries the backward chain's ten gmax words, cleared here -- the kernel that runs right in front
-  // of the chain -- instead of by a memset launch of their own (round 6)
-  if (COMPACT && g1 && blockIdx.x == 0 && threadIdx.x < 10) reinterpret_cast<unsigned*>(g1)[threadIdx.x] = 0u;
+  // the chain path's gmax words are cleared here -- the kernel that runs right in front of the chain -- instead of by a memset
+  // launch of their own (round 6)
+  if (gmax && blockIdx.x == 0 && threadIdx.x < 10) gmax[threadIdx.x] = 0u;
   const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (r >= R) return;
   const int64_t base = r * N;
@@ -241,7 +243,7 @@ __global__ void __launch_bounds__(256) composite_bwd_kernel(const float* __restr
   const double lane_incl = wave_scan_add_d(acc, lane);
   const double total = __shfl(lane_incl, 63, 64);
   const double lane_excl = lane_incl - acc;
-  float bs0 = 0.0f, bs1 = 0.0f, bs2 = 0.0f, bs3 = 0.0f;     // COMPACT: this ray's sums of the four values = its share of the
+  float bs0 = 0.0f, bs1 = 0.0f, bs2 = 0.0f, bs3 = 0.0f;     // this ray's sums of the four values = its share of the
                                                             // colour head's and the density head's bias gradients
 #pragma unroll
   for (int i = 0; i < K; ++i) {
@@ -256,87 +258,72 @@ __global__ void __launch_bounds__(256) composite_bwd_kernel(const float* __restr
     const float dr0 = colour_head_bwd(gc0 * w[i], c0[i], head);
     const float dr1 = colour_head_bwd(gc1 * w[i], c1[i], head);
     const float dr2 = colour_head_bwd(gc2 * w[i], c2[i], head);
-    if (COMPACT) {
-      reinterpret_cast<float4*>(d_rgb)[p] = make_float4(dr0, dr1, dr2, d_sigma);
-      bs0 += dr0; bs1 += dr1; bs2 += dr2; bs3 += d_sigma;
-      continue;
-    }
-    float4* dr = reinterpret_cast<float4*>(d_rgb + p * kRgbPad);
-    dr[0] = make_float4(dr0, dr1, dr2, 0.0f);
-#pragma unroll
-    for (int j = 1; j < 8; ++j) dr[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    float* gp = g1 + p * kGs + kSigmaCol;
-    gp[0] = d_sigma;
-#pragma unroll
-    for (int j = 1; j < 32; ++j) gp[j] = 0.0f;
+    reinterpret_cast<float4*>(d4)[p] = make_float4(dr0, dr1, dr2, d_sigma);
+    bs0 += dr0; bs1 += dr1; bs2 += dr2; bs3 += d_sigma;
   }
-  if (COMPACT && bias_part) {      // one float4 per ray; finish_jobs_kernel (kind 2) sums the rays in double
+  if (bias_part) {      // one float4 per ray; finish_jobs_kernel (kind 2) sums the rays in double
     bs0 = wave_sum(bs0); bs1 = wave_sum(bs1); bs2 = wave_sum(bs2); bs3 = wave_sum(bs3);
     if (lane == 0) reinterpret_cast<float4*>(bias_part)[r] = make_float4(bs0, bs1, bs2, bs3);
   }
 }
 
-struct AdamPtrs {
-  float* w[NSR_N_STATE_TENSORS];
-  const float* g[NSR_N_STATE_TENSORS];
-  float* m[NSR_N_STATE_TENSORS];
-  float* v[NSR_N_STATE_TENSORS];
+// torch.optim.Adam over n tensors in one launch (adam_update: nsr_train_work.h)
+struct AdamN {
+  float* w[kMaxT];
+  const float* g[kMaxT];
+  float* m[kMaxT];
+  float* v[kMaxT];
+  int64_t n[kMaxT];
 };
-// one launch over the 24 tensors of the default network (adam_update: nsr_train_work.h)
-__global__ void __launch_bounds__(256) adam_kernel(AdamPtrs a, float beta1, float beta2, float eps, float step_size,
-                                                   float bc2_sqrt) {
+__global__ void __launch_bounds__(256) adam_n_kernel(AdamN a, float beta1, float beta2, float eps, float step_size, float bc2_sqrt) {
   const int t = blockIdx.y;
-  const int64_t n = tensor_numel(t);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+  const int64_t n = a.n[t];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     adam_update(a.g[t], a.m[t], a.v[t], a.w[t], i, beta1, beta2, eps, step_size, bc2_sqrt);
-  }
 }
 
 // ---- host side: carving the workspace ---------------------------------------------------------------------------------
 // the kept state of a pass over P sample points (nsr_train_work.h): THE list of its buffers, for the workspace and for a
 // pass region of the saved state alike
-Kept carve_kept(Carver& a, int64_t P, bool gemm_path, bool chain_path) {
-  Kept q;
-  q.x5 = a.take(P * kX5, gemm_path);
-  for (int L = 0; L <= 8; ++L) q.h[L] = (L == 0 || L == 4) ? nullptr : a.take(P * kW, gemm_path);   // h4 lives in x5[:, 64:]
-  q.gs = a.take(P * kGs, gemm_path);
-  q.cc = a.take(P * kDirOut, gemm_path);
+// net: the layer-by-layer network whose activations are kept (null: none); chain_path: the chain kernels' panels
+Kept carve_kept(Carver& a, int64_t P, const Shape* net, bool chain_path) {
+  Kept q{};
+  if (net) carve_net_kept(a, *net, P, q);
   q.rgb = a.take(P * 4);   q.sig = a.take(P);   q.z = a.take(P);
   q.zpan = reinterpret_cast<char*>(a.take(nsr_f16x3_train_panel_bytes(P) / 4, chain_path));
   q.sgn = reinterpret_cast<unsigned*>(a.take(nsr_f16x3_train_sign_words(P), chain_path));
   return q;
 }
 
-// both paths: every buffer (nsr_train_workspace_bytes: sufficient whatever runs); else the layer-by-layer GEMM path only, or
-// the chain path only (no per-layer activation / gradient matrices: 11 KB per sample point less)
-int64_t work_floats(int64_t chunk, int nc, int ni, bool gemm_path, bool chain_path, Work* w, float* base) {
+// net (+ split: its split-fp16 weight halves) and / or the chain path: the buffers of what may run.  Both
+// (nsr_train_workspace_bytes): sufficient whatever runs; the chain path alone holds no per-layer activation / gradient
+// matrices (11 KB per sample point less)
+int64_t work_floats(int64_t chunk, int nc, int ni, const Shape* net, bool split, bool chain_path, Work* w, float* base) {
   const int64_t nf = nc + ni, P = chunk * nf;
   Carver a{base};
   Work tmp;
   Work& k = w ? *w : tmp;
   k.status = reinterpret_cast<unsigned*>(a.take(16));      // offset 0 whatever the path: nsr_train_status reads it blind
-  k.kept = carve_kept(a, P, gemm_path, chain_path);
-  k.g0 = a.take(P * kGs, gemm_path);   k.g1 = a.take(P * kGs, gemm_path);
-  k.drgb = a.take(P * kRgbPad, gemm_path);
-  k.d4 = a.take(P * 4, chain_path);
-  k.bias_part = a.take(chunk * 4, chain_path);
-  k.col_tiles = a.take((P / 128 + 1) * kW + 2 * 64 * kW + 64);   // per-tile column sums + 64 slices of doubles
+  k.kept = carve_kept(a, P, net, chain_path);
+  k.d4 = a.take(P * 4);
+  if (net) {
+    const Shape& S = *net;
+    k.g0 = a.take(P * (S.Wp + 32));   k.g1 = a.take(P * (S.Wp + 32));
+    k.drgb = a.take(P * 32);
+    k.col_tiles = a.take((P / 128 + 1) * S.Wp + 2 * 64 * S.Wp + 64);   // per-tile column sums + 64 slices of doubles
+    k.partial = a.take(kMaxSplits * S.part_stride);                    // also scratch of the small bias sums
+    for (int n = 0; n < 2; ++n) k.pack[n] = carve_pack(a, S, split);
+  }
   k.z_c = a.take(chunk * nc);   k.w_c = a.take(chunk * nc);
-  k.comp = a.take(chunk * 3);   k.g_comp = a.take(chunk * 3);
+  k.g_comp = a.take(chunk * 3);
   k.scratch_out = a.take(chunk * (nf + 8));
-  k.partial = a.take(kMaxSplits * kPartialFloats);         // also scratch of the small bias sums
-  // chain path: every second pass of a network waits for one launch; sized by the split-K factor of the larger pass
-  const int64_t sp_max = n_splits(P);
-  k.slots = a.take(kChainSlots * sp_max * 256 * 256, chain_path);
   k.block_sums = reinterpret_cast<double*>(a.take(2 * 3 * (chunk / 256 + 2)));
   k.carry = reinterpret_cast<double*>(a.take(16));
   k.g_depth = a.take(chunk);
-  for (int n = 0; n < 2; ++n) {
-    WeightPack& q = k.pack[n];
-    q.w1p = a.take(256 * 64);   q.w5p = a.take(256 * 320);   q.w9p = a.take(288 * 256);   q.wdirp = a.take(128 * 288);
-    q.wrgbp = a.take(32 * 128);   q.b9p = a.take(320);   q.brgbp = a.take(64);
-    q.split = reinterpret_cast<unsigned short*>(a.take((kSplitHalves + 1) / 2));
-  }
+  // chain path: every second pass of a network waits for one launch; sized by the split-K factor of the larger pass
+  const int64_t sp_max = n_splits(P);
+  k.bias_part = a.take(chunk * 4, chain_path);
+  k.slots = a.take(kChainSlots * sp_max * 256 * 256, chain_path);
   k.dpan = reinterpret_cast<char*>(a.take(nsr_f16x3_train_panel_bytes(P) / 4, chain_path));
   k.row_part = a.take(kChainRowSlots * sp_max * 256, chain_path);
   k.gmax = reinterpret_cast<unsigned*>(a.take(64, chain_path));
@@ -359,40 +346,36 @@ int chain_bwd_terms(int precision) {
   return precision == NSR_F16X3_BWD3 ? 3 : (precision == NSR_F16X3_BWD2 ? 2 : (precision == NSR_F16X3_BWD1 ? 1 : (precision == NSR_F16X3_BWDM ? 12 : kDefaultBwdTerms)));
 }
 bool train_precision_ok(int precision) { return precision == NSR_FP32 || chain_selected(precision) || precision == NSR_F16X3_GEMM; }
-int gemm_precision(int precision) { return precision == NSR_F16X3_GEMM ? NSR_F16X3 : precision; }   // what the GEMM path's helpers expect
+bool split_selected(int precision) { return precision == NSR_F16X3_GEMM; }   // split-fp16 forward products of the layer-by-layer network
 
-using CompositeBwdFn = decltype(&composite_bwd_kernel<1, false, false>);
-template <bool COMPACT, bool FULL> CompositeBwdFn composite_bwd_for(int K) {   // K: samples per lane
+using CompositeBwdFn = decltype(&composite_bwd_kernel<1, false>);
+template <bool FULL> CompositeBwdFn composite_bwd_for(int K) {   // K: samples per lane
   switch (K) {
-    case 1: return composite_bwd_kernel<1, COMPACT, FULL>;
-    case 2: return composite_bwd_kernel<2, COMPACT, FULL>;
-    case 3: return composite_bwd_kernel<3, COMPACT, FULL>;
-    case 4: return composite_bwd_kernel<4, COMPACT, FULL>;
+    case 1: return composite_bwd_kernel<1, FULL>;
+    case 2: return composite_bwd_kernel<2, FULL>;
+    case 3: return composite_bwd_kernel<3, FULL>;
+    case 4: return composite_bwd_kernel<4, FULL>;
     default: return nullptr;
   }
 }
-// compact: the chain path's output layout.  g_opacity / g_weights (nsr_train_backward only): non-null selects the FULL
-// instantiation
-}  // namespace
-int nsr::composite_bwd(hipStream_t st, const Work& k, const float* z, const float* g_comp, int64_t R, int N, int white, bool compact,
-                       const float* g_depth, const float* g_opacity, const float* g_weights) {
+// (P, 4) rows into d4 from the pass's rgb / sig / z; gmax, bias_part: the chain path's, else null.  g_opacity / g_weights
+// (the backward entry points only): non-null selects the FULL instantiation
+int composite_bwd(hipStream_t st, const float* rgb, const float* sig, const float* z, const float* g_comp, int64_t R, int N, int white,
+                  float* d4, unsigned* gmax, float* bias_part, const float* g_depth, const float* g_opacity, const float* g_weights) {
   const int K = (N + 63) / 64;
-  const bool full = g_opacity || g_weights;
-  const CompositeBwdFn fn = compact ? (full ? composite_bwd_for<true, true>(K) : composite_bwd_for<true, false>(K))
-                                    : (full ? composite_bwd_for<false, true>(K) : composite_bwd_for<false, false>(K));
+  const CompositeBwdFn fn = (g_opacity || g_weights) ? composite_bwd_for<true>(K) : composite_bwd_for<false>(K);
   if (!fn) return NSR_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(fn, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, k.kept.rgb, k.kept.sig, z, g_comp, R, N, white,
-                     compact ? k.d4 : k.drgb, compact ? reinterpret_cast<float*>(k.gmax) : k.g1, g_depth,
-                     compact ? k.bias_part : nullptr, g_opacity, g_weights);
+  hipLaunchKernelGGL(fn, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, rgb, sig, z, g_comp, R, N, white, d4, gmax, g_depth,
+                     bias_part, g_opacity, g_weights);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
 
-// ---- the opening the three drivers share -------------------------------------------------------------------------------
+// ---- the opening the drivers share ---------------------------------------------------------------------------------------
 // the shape rules: sample counts and precision (NSR_ERR_UNSUPPORTED), R and the chunk multiples of s2
 // (NSR_ERR_INVALID_ARG), a multiple of 32 points per pass in both networks (NSR_ERR_UNSUPPORTED).  ray_chunk <= 0 or > R
-// becomes R.  gemm_only: the layer-by-layer precisions alone (nsr_train_arch.hip)
-int nsr::check_shape(int64_t R, int s2, int n_coarse, int n_importance, int precision, int64_t& ray_chunk, bool gemm_only) {
+// becomes R.  gemm_only: the layer-by-layer precisions alone (nsr_train_arch_*)
+int check_shape(int64_t R, int s2, int n_coarse, int n_importance, int precision, int64_t& ray_chunk, bool gemm_only) {
   if (n_coarse < 2 || n_importance < 1 || n_coarse + n_importance > 256) return NSR_ERR_UNSUPPORTED;
   if (!train_precision_ok(precision) || (gemm_only && chain_selected(precision))) return NSR_ERR_UNSUPPORTED;
   if (R % s2 != 0) return NSR_ERR_INVALID_ARG;
@@ -408,20 +391,19 @@ int nsr::check_shape(int64_t R, int s2, int n_coarse, int n_importance, int prec
   return NSR_OK;
 }
 // the option word (include/nsr_train.h): the renderer's two bits + the colour head's two + stop_grad
-namespace {
 constexpr int kTrainOpts = NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS | NSR_TRAIN_GAMMA_CORRECT | NSR_TRAIN_COLOR_NONE | NSR_TRAIN_STOP_GRAD;
-}  // namespace
-int nsr::check_flags(int flags) {
+int check_flags(int flags) {
   if ((flags & ~kTrainOpts) != 0) return NSR_ERR_INVALID_ARG;
   // pow(x, 1 / 2.2) of an unbounded head: NaN for every negative value
   if ((flags & NSR_TRAIN_GAMMA_CORRECT) && (flags & NSR_TRAIN_COLOR_NONE)) return NSR_ERR_UNSUPPORTED;
   return NSR_OK;
 }
 
+
 // Everything that is checked before a call enqueues, in the ONE order that decides which status a call with two mistakes
 // returns.  c: shape and options of the call (c->chunk is resolved; s2 = 1 without a loss), or null for the backward, whose
 // shape comes out of the saved header afterwards.  NSR_OK with c->R == 0 means: nothing to do, the rest was not looked at.
-int nsr::check_args(const Need& need, Run* c, int s2) {
+int check_args(const Need& need, Run* c, int s2) {
   for (const void* p : need.always)
     if (!p) return NSR_ERR_INVALID_ARG;
   if (c) {
@@ -439,12 +421,21 @@ int nsr::check_args(const Need& need, Run* c, int s2) {
     if ((reinterpret_cast<uintptr_t>(p) & 255) != 0) return NSR_ERR_INVALID_ARG;
   return c ? check_flags(c->flags) : NSR_OK;
 }
-namespace {
-// the workspace of a checked call: large enough for its path, then carved
-int open_work(Run& c, void* workspace, size_t workspace_bytes, Work& k) {
-  if (workspace_bytes < nsr_train_workspace_bytes_for(c.precision, c.chunk, c.nc, c.ni)) return NSR_ERR_WORKSPACE;
+// the workspace of a checked call: which implementation runs (c.net: the descriptor's shapes, already made), the weights
+// usable where they lie, large enough, then carved.  The nsr_train_* family always sizes the split halves
+// (nsr_train_workspace_bytes_for: one size for both layer-by-layer precisions), nsr_train_arch_* sizes by precision
+int open_work(Run& c, const float* const* w_coarse, const float* const* w_fine, bool by_precision, void* workspace,
+              size_t workspace_bytes, Work& k) {
   c.chain = chain_selected(c.precision);
-  work_floats(c.chunk, c.nc, c.ni, !c.chain, c.chain, &k, static_cast<float*>(workspace));
+  const Shape* net = c.chain ? nullptr : &c.net;
+  if (net) {
+    NSR_TRY(check_alignment(*net, w_coarse));
+    NSR_TRY(check_alignment(*net, w_fine));
+  }
+  const bool split = !by_precision || split_selected(c.precision);
+  if (workspace_bytes < (size_t)work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, nullptr, nullptr) * sizeof(float))
+    return NSR_ERR_WORKSPACE;
+  work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, &k, static_cast<float*>(workspace));
   return NSR_OK;
 }
 
@@ -463,28 +454,26 @@ int prepare_call(hipStream_t st, const Work& k, const float* const* w_coarse, co
                                 chain_bwd_terms(c.precision), k.carry, 8, k.status + 1,
                                 (c.flags & NSR_TRAIN_COLOR_NONE) ? kOptColorNone : 0u, stream));
   } else {
-    NSR_TRY(prepare_weights(st, w_coarse, k.pack[0], gemm_precision(c.precision)));
-    NSR_TRY(prepare_weights(st, w_fine, k.pack[1], gemm_precision(c.precision)));
+    NSR_TRY(prepare_weights(st, c.net, w_coarse, k.pack[0], split_selected(c.precision)));
+    NSR_TRY(prepare_weights(st, c.net, w_fine, k.pack[1], split_selected(c.precision)));
     if (hipMemsetAsync(k.carry, 0, 8 * sizeof(double), st) != hipSuccess) return NSR_ERR_LAUNCH;
   }
   return NSR_OK;
 }
 
 // ---- the passes of a call ----------------------------------------------------------------------------------------------
-}  // namespace
-// the two halves of a pass's forward that do not depend on the network (nsr_train_arch.hip runs them around its own):
-// stratified samples (coarse) or inverse-CDF samples from the detached coarse weights w_c over z_c (fine) into z ...
-int nsr::pass_sample(const Run& c, const Pass& q, const float* rays, const float* u, const float* z_c, const float* w_c, float* z,
+// stratified samples (coarse) or inverse-CDF samples from the detached coarse weights w_c over z_c (fine) into z
+int pass_sample(const Run& c, const Pass& q, const float* rays, const float* u, const float* z_c, const float* w_c, float* z,
                      void* stream) {
   const float* rays_c = rays + q.r0 * c.ray_stride;
   if (q.net == 0) return nsr_sample_along_rays(rays_c, c.ray_stride, q.rc, c.nc, c.lindisp, rows_of(u, q, c.nc), z, nullptr, stream);
   return nsr_resample_along_rays(rays_c, c.ray_stride, z_c, w_c, q.rc, c.nc, c.ni, rows_of(u, q, c.ni), z, nullptr, stream);
 }
-// ... and, from the raw densities (sigma_raw, one every sigma_stride floats) and the (P, 4) colours the network left: density
-// noise into sig, --gamma_correct, compositing
-int nsr::pass_finish(hipStream_t st, const Run& c, const Pass& q, const float* sigma_raw, int sigma_stride, const float* noise,
-                     float* rgb4, float* sig, const float* z, float* comp, float* depth, float* opac, float* wts, void* stream) {
-  hipLaunchKernelGGL(sigma_noise_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, st, sigma_raw, sigma_stride,
+// from the raw densities in column 3 of the (P, 4) colours the network left: density noise into sig, --gamma_correct,
+// compositing
+int pass_finish(hipStream_t st, const Run& c, const Pass& q, const float* noise, float* rgb4, float* sig, const float* z, float* comp,
+                float* depth, float* opac, float* wts, void* stream) {
+  hipLaunchKernelGGL(sigma_noise_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, st, rgb4 + 3, 4,
                      c.noise_std > 0.0f ? rows_of(noise, q, q.N) : nullptr, c.noise_std, q.P, sig);
   NSR_CHECK_LAUNCH();
   if (c.flags & NSR_TRAIN_GAMMA_CORRECT) {   // render_rays: out_rgbs = pow(out_rgbs, 1 / 2.2) per sample, in training too (nerf_downX_model.py:271-276)
@@ -493,9 +482,8 @@ int nsr::pass_finish(hipStream_t st, const Run& c, const Pass& q, const float* s
   }
   return nsr_composite(rgb4, 4, sig, 1, z, q.rc, q.N, c.flags & (NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS), comp, depth, opac, wts, stream);
 }
-namespace {
-// forward half of pass q: stratified samples (coarse) or inverse-CDF samples from the detached coarse weights w_c over z_c
-// (fine) into z, the network (what its backward reads stays in k.kept), density noise, --gamma_correct, compositing.
+// forward half of pass q: sampling into z, the network (what its backward reads stays in k.kept), density noise,
+// --gamma_correct, compositing.
 // rays / u / noise: the call's whole arrays; w_c / comp / depth / opac / wts: this pass's rows (all but comp may be null)
 int pass_forward(hipStream_t st, const Work& k, const Run& c, const Pass& q, const float* const* w, const float* rays,
                  const float* u, const float* noise, const float* z_c, const float* w_c, float* z, float* comp, float* depth,
@@ -506,53 +494,54 @@ int pass_forward(hipStream_t st, const Work& k, const Run& c, const Pass& q, con
   if (c.chain) {   // the chain path encodes inside its forward kernel
     NSR_TRY(nsr_f16x3_train_forward(k.stream_f[q.net], rays_c, c.ray_stride, z, q.rc, q.N, s.rgb, s.zpan, s.sgn, k.status, stream));
   } else {
-    NSR_TRY(net_forward(st, rays_c, c.ray_stride, z, q.N, w, k.pack[q.net], s, q.P, gemm_precision(c.precision),
+    NSR_TRY(net_forward(st, c.net, rays_c, c.ray_stride, z, q.N, w, k.pack[q.net], s, q.P, split_selected(c.precision),
                         (c.flags & NSR_TRAIN_COLOR_NONE) != 0));
   }
-  return pass_finish(st, c, q, c.chain ? s.rgb + 3 : s.gs + kSigmaCol, c.chain ? 4 : kGs, noise, s.rgb, s.sig, z, comp, depth, opac,
-                     wts, stream);
+  return pass_finish(st, c, q, noise, s.rgb, s.sig, z, comp, depth, opac, wts, stream);
 }
 
 // backward half of the same pass, from the upstream gradients of its outputs (this pass's rows; g_comp required, the others
-// may be null): compositing backward, then the chain kernels or the layer-by-layer GEMMs.  g: the network's 24 gradient
+// may be null): compositing backward, then the chain kernels or the layer-by-layer network.  g: the network's gradient
 // tensors, overwritten or accumulated (q.acc)
 int pass_backward(hipStream_t st, const Work& k, const Run& c, const Pass& q, const float* const* w, const float* z,
                   const float* g_comp, const float* g_depth, const float* g_opacity, const float* g_weights, float* const* g,
                   void* stream) {
-  NSR_TRY(composite_bwd(st, k, z, g_comp, q.rc, q.N, c.flags, c.chain, g_depth, g_opacity, g_weights));
+  NSR_TRY(composite_bwd(st, k.kept.rgb, k.kept.sig, z, g_comp, q.rc, q.N, c.flags, k.d4, c.chain ? k.gmax : nullptr,
+                        c.chain ? k.bias_part : nullptr, g_depth, g_opacity, g_weights));
   if (c.chain) {
     NSR_TRY(nsr_chain_bwd(k.stream_b[q.net], k.kept.sgn, k.dpan, k.d4, 4, k.d4 + 3, 4, q.P, k.gmax, k.pscale,
                           chain_bwd_terms(c.precision), 1, stream));
     return chain_weight_grads(st, k, q.P, q.rc, g, q.acc);
   }
-  return net_backward(st, w, k.pack[q.net], k, q.P, g, q.acc, (c.flags & NSR_TRAIN_STOP_GRAD) != 0);
+  return net_backward(st, c.net, w, k.pack[q.net], k, q.P, g, q.acc, (c.flags & NSR_TRAIN_STOP_GRAD) != 0);
 }
 
-// ---- saved state of nsr_train_forward (include/nsr_train.h) ----------------------------------------------------------
+// ---- saved state of a forward call (include/nsr_train.h) --------------------------------------------------------------
 // [header: 256 bytes][chain path: backward weight streams of both networks][chunk 0: coarse pass, fine pass][chunk 1: ...]
 // A pass region holds the pass's Kept: what pass_backward reads besides the weights.  Every region is sized for a full chunk.
-constexpr uint64_t kSavedMagic = 0x31564153525343ull;   // "CSRSAV1": format of this header and layout
+constexpr uint64_t kSavedMagic = 0x32564153525343ull;   // "CSRSAV2": format of this header and layout
 constexpr int64_t kSavedHeaderFloats = 64;
 struct SavedHeader {
   uint64_t magic, floats;   // floats: the layout's total, checked against the arguments read back
   int64_t R, chunk;
   int nc, ni, flags, precision;
+  nsr_arch arch;            // the network the forward ran (the default descriptor under a chain precision)
 };
-static_assert(sizeof(SavedHeader) <= kSavedHeaderFloats * 4, "header");
+static_assert(sizeof(SavedHeader) <= kSavedHeaderFloats * 4 && sizeof(SavedHeader) % 4 == 0, "header");
 struct SavedLayout {
   int64_t stream, pass_c, pass_f, n_chunks, total;   // floats
 };
-int64_t kept_floats(int64_t P, bool chain) {
+int64_t kept_floats(int64_t P, const Shape* net, bool chain) {
   Carver a{nullptr};
-  carve_kept(a, P, !chain, chain);
+  carve_kept(a, P, net, chain);
   return a.off;
 }
-SavedLayout saved_layout(int precision, int64_t R, int nc, int ni, int64_t chunk) {
+SavedLayout saved_layout(const Shape& net, int precision, int64_t R, int nc, int ni, int64_t chunk) {
   const bool chain = chain_selected(precision);
   SavedLayout L;
   L.stream = chain ? align64((int64_t)(nsr_chain_bwd_packed_bytes() / 4)) : 0;
-  L.pass_c = kept_floats(chunk * nc, chain);
-  L.pass_f = kept_floats(chunk * (nc + ni), chain);
+  L.pass_c = kept_floats(chunk * nc, chain ? nullptr : &net, chain);
+  L.pass_f = kept_floats(chunk * (nc + ni), chain ? nullptr : &net, chain);
   L.n_chunks = (R + chunk - 1) / chunk;
   L.total = kSavedHeaderFloats + 2 * L.stream + L.n_chunks * (L.pass_c + L.pass_f);
   return L;
@@ -560,26 +549,142 @@ SavedLayout saved_layout(int precision, int64_t R, int nc, int ni, int64_t chunk
 float* saved_stream(float* base, const SavedLayout& L, int net) { return base + kSavedHeaderFloats + net * L.stream; }
 Kept saved_kept(float* base, const SavedLayout& L, const Run& c, const Pass& q) {
   Carver a{base + kSavedHeaderFloats + 2 * L.stream + q.ci * (L.pass_c + L.pass_f) + (q.net ? L.pass_c : 0)};
-  return carve_kept(a, c.chunk * q.N, !c.chain, c.chain);
+  return carve_kept(a, c.chunk * q.N, c.chain ? nullptr : &c.net, c.chain);
 }
-// the header is written on the stream (the call enqueues, it does not wait) and read back by nsr_train_backward
+// the header is written on the stream (the call enqueues, it does not wait) and read back by the backward call
 __global__ void saved_header_kernel(SavedHeader h, unsigned* __restrict__ dst) {
   const unsigned* src = reinterpret_cast<const unsigned*>(&h);
   const int i = threadIdx.x;
   if (i < (int)(sizeof(SavedHeader) / 4)) dst[i] = src[i];
 }
+bool same_arch(const nsr_arch& a, const nsr_arch& b) {
+  return a.D == b.D && a.W == b.W && a.skips == b.skips && a.deg_pos == b.deg_pos && a.deg_dir == b.deg_dir && a.no_dir == b.no_dir;
+}
+bool sizes_ok(int64_t ray_chunk, int nc, int ni) { return ray_chunk > 0 && nc >= 2 && ni >= 1 && nc + ni <= 256; }
+
+// ---- the forward / backward pair: nsr_train_* with the default descriptor and every precision, nsr_train_arch_* with the
+// caller's descriptor and the layer-by-layer precisions only (by_arch) -------------------------------------------------------
+size_t saved_bytes_of(const nsr_arch* arch, bool by_arch, int precision, int64_t R, int nc, int ni, int64_t ray_chunk) {
+  Shape S;
+  if (make_shape(arch, S) != NSR_OK) return 0;
+  if (R <= 0 || check_shape(R, 1, nc, ni, precision, ray_chunk, by_arch) != NSR_OK) return 0;
+  return (size_t)saved_layout(S, precision, R, nc, ni, ray_chunk).total * sizeof(float);
+}
+
+int train_forward(const nsr_arch* arch, bool by_arch, const float* const* w_coarse, const float* const* w_fine, const float* rays,
+                  int ray_stride, int64_t R, int n_coarse, int n_importance, int render_flags, int lindisp, const float* u_coarse,
+                  const float* u_fine, const float* noise_coarse, const float* noise_fine, float noise_std, int precision,
+                  int64_t ray_chunk, float* const* outs, void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes,
+                  void* stream) {
+  Run c{};
+  NSR_TRY(make_shape(arch, c.net));
+  c.R = R; c.chunk = ray_chunk; c.nc = n_coarse; c.ni = n_importance; c.flags = render_flags; c.precision = precision;
+  c.lindisp = lindisp; c.ray_stride = ray_stride; c.noise_std = noise_std;
+  NSR_TRY(check_args({{w_coarse, w_fine, outs}, {w_coarse, w_fine}, outs, {rays, workspace, saved}, {workspace, saved},
+                      c.net.n_tensors(), by_arch}, &c, 1));
+  if (R == 0) return NSR_OK;
+  Work k;
+  NSR_TRY(open_work(c, w_coarse, w_fine, by_arch, workspace, workspace_bytes, k));
+  const SavedLayout L = saved_layout(c.net, precision, R, n_coarse, n_importance, c.chunk);
+  if (saved_bytes < (size_t)L.total * sizeof(float)) return NSR_ERR_WORKSPACE;
+  hipStream_t st = nsr_stream(stream);
+  float* sv = static_cast<float*>(saved);
+  if (c.chain)   // the backward weight streams are packed into the saved state: the backward call uses them as they are
+    for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
+  const SavedHeader h{kSavedMagic, (uint64_t)L.total, R, c.chunk, n_coarse, n_importance, render_flags, precision, c.net.arch};
+  hipLaunchKernelGGL(saved_header_kernel, dim3(1), dim3(64), 0, st, h, reinterpret_cast<unsigned*>(sv));
+  NSR_CHECK_LAUNCH();
+  NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream));
+  const float* z_c = nullptr;   // the coarse pass's samples of the chunk at hand
+  return for_each_pass(c, [&](const Pass& q) -> int {
+    k.kept = saved_kept(sv, L, c, q);
+    if (q.net == 0) z_c = k.kept.z;
+    float* const* o = outs + 4 * q.net;
+    return pass_forward(st, k, c, q, q.net ? w_fine : w_coarse, rays, q.net ? u_fine : u_coarse,
+                        q.net ? noise_fine : noise_coarse, z_c, rows_of(outs[3], q, c.nc, k.w_c), k.kept.z, o[0] + q.r0 * 3,
+                        rows_of(o[1], q, 1), rows_of(o[2], q, 1), rows_of(o[3], q, q.N, q.net ? nullptr : k.w_c), stream);
+  });
+}
+
+int train_backward(const nsr_arch* arch, bool by_arch, const float* const* w_coarse, const float* const* w_fine,
+                   const float* const* g_outs, float* const* g_coarse, float* const* g_fine, void* workspace, size_t workspace_bytes,
+                   const void* saved, size_t saved_bytes, void* stream) {
+  Run c{};   // no sampling in this half: lindisp, ray_stride and noise_std stay unused
+  NSR_TRY(make_shape(arch, c.net));
+  NSR_TRY(check_args({{w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, saved}, {w_coarse, w_fine, g_coarse, g_fine},
+                      nullptr, {}, {workspace, saved}, c.net.n_tensors(), by_arch}, nullptr, 1));
+  if (saved_bytes < (size_t)kSavedHeaderFloats * sizeof(float)) return NSR_ERR_WORKSPACE;
+  // the run's parameters, read back from the header the forward call wrote (waits for the stream)
+  hipStream_t st = nsr_stream(stream);
+  SavedHeader h{};
+  if (hipMemcpyAsync(&h, saved, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) return NSR_ERR_LAUNCH;
+  if (hipStreamSynchronize(st) != hipSuccess) return NSR_ERR_LAUNCH;
+  if (h.magic != kSavedMagic) return NSR_ERR_INVALID_ARG;
+  if (h.floats > saved_bytes / sizeof(float)) return NSR_ERR_WORKSPACE;   // the header says the state is larger than the buffer
+  if (!same_arch(h.arch, c.net.arch)) return NSR_ERR_INVALID_ARG;         // the forward ran another network
+  // bounds before anything loops over them (a damaged header may hold anything): every ray and every chunk takes at least
+  // 64 floats of the layout, so neither count can exceed what the buffer holds
+  if (h.R <= 0 || h.chunk <= 0 || h.chunk > h.R || (uint64_t)h.R > h.floats / 64 ||
+      (uint64_t)((h.R + h.chunk - 1) / h.chunk) > h.floats / 64)
+    return NSR_ERR_INVALID_ARG;
+  c.R = h.R; c.chunk = h.chunk; c.nc = h.nc; c.ni = h.ni; c.flags = h.flags; c.precision = h.precision;
+  if (check_shape(c.R, 1, c.nc, c.ni, c.precision, c.chunk, by_arch) != NSR_OK || c.chunk != h.chunk || check_flags(c.flags) != NSR_OK)
+    return NSR_ERR_INVALID_ARG;
+  const SavedLayout L = saved_layout(c.net, c.precision, c.R, c.nc, c.ni, c.chunk);
+  if ((uint64_t)L.total != h.floats) return NSR_ERR_INVALID_ARG;
+  Work k;
+  NSR_TRY(open_work(c, w_coarse, w_fine, by_arch, workspace, workspace_bytes, k));
+  float* sv = const_cast<float*>(static_cast<const float*>(saved));   // read only
+  if (c.chain) {
+    for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
+  } else {   // the padded weight copies the backward products read (no split halves: every gradient runs on the fp32 MFMA)
+    NSR_TRY(prepare_weights(st, c.net, w_coarse, k.pack[0], false));
+    NSR_TRY(prepare_weights(st, c.net, w_fine, k.pack[1], false));
+  }
+  // the fused step's order of passes: the first chunk overwrites the gradients, later chunks accumulate
+  return for_each_pass(c, [&](const Pass& q) -> int {
+    k.kept = saved_kept(sv, L, c, q);
+    const float* const* go = g_outs + 4 * q.net;
+    if (!go[0] && hipMemsetAsync(k.g_comp, 0, (size_t)q.rc * 3 * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
+    return pass_backward(st, k, c, q, q.net ? w_fine : w_coarse, k.kept.z, rows_of(go[0], q, 3, k.g_comp), rows_of(go[1], q, 1),
+                         rows_of(go[2], q, 1), rows_of(go[3], q, q.N), q.net ? g_fine : g_coarse, stream);
+  });
+}
 
 }  // namespace
 
 extern "C" size_t nsr_train_workspace_bytes_for(int precision, int64_t ray_chunk, int n_coarse, int n_importance) {
-  if (ray_chunk <= 0 || n_coarse < 2 || n_importance < 1 || n_coarse + n_importance > 256 || !train_precision_ok(precision)) return 0;
+  Shape S;
+  if (!sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) || make_shape(&kDefaultArch, S) != NSR_OK) return 0;
   const bool chain = chain_selected(precision);
-  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, !chain, chain, nullptr, nullptr) * sizeof(float);
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, chain ? nullptr : &S, true, chain, nullptr, nullptr) * sizeof(float);
 }
 
 extern "C" size_t nsr_train_workspace_bytes(int64_t ray_chunk, int n_coarse, int n_importance) {
-  if (ray_chunk <= 0 || n_coarse < 2 || n_importance < 1 || n_coarse + n_importance > 256) return 0;
-  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, true, true, nullptr, nullptr) * sizeof(float);
+  Shape S;
+  if (!sizes_ok(ray_chunk, n_coarse, n_importance) || make_shape(&kDefaultArch, S) != NSR_OK) return 0;
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, true, true, nullptr, nullptr) * sizeof(float);
+}
+
+extern "C" size_t nsr_train_arch_workspace_bytes(const nsr_arch* arch, int precision, int64_t ray_chunk, int n_coarse,
+                                                 int n_importance) {
+  Shape S;
+  if (make_shape(arch, S) != NSR_OK || !sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) ||
+      chain_selected(precision))
+    return 0;
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, split_selected(precision), false, nullptr, nullptr) * sizeof(float);
+}
+
+extern "C" int nsr_arch_n_tensors(const nsr_arch* arch) {
+  Shape S;
+  const int rc = make_shape(arch, S);
+  return rc != NSR_OK ? rc : S.n_tensors();
+}
+
+extern "C" int64_t nsr_arch_tensor_numel(const nsr_arch* arch, int t) {
+  Shape S;
+  if (make_shape(arch, S) != NSR_OK) return 0;
+  return tensor_numel_of(S, t);
 }
 
 extern "C" int nsr_train_loss_and_grads_var(const float* const* w_coarse, const float* const* w_fine, float* const* g_coarse,
@@ -599,11 +704,12 @@ extern "C" int nsr_train_loss_and_grads_var(const float* const* w_coarse, const 
   Run c{};
   c.R = R; c.chunk = ray_chunk; c.nc = n_coarse; c.ni = n_importance; c.flags = white_bkgd; c.precision = precision;
   c.lindisp = lindisp; c.ray_stride = ray_stride; c.noise_std = noise_std;
+  NSR_TRY(make_shape(&kDefaultArch, c.net));
   NSR_TRY(check_args({{w_coarse, w_fine, g_coarse, g_fine, outs}, {w_coarse, w_fine, g_coarse, g_fine}, outs,
                       {rays, target_lr, lr_coarse, lr_fine, losses, workspace}, {workspace}}, &c, s2));
   if (R == 0) return NSR_OK;
   Work k;
-  NSR_TRY(open_work(c, workspace, workspace_bytes, k));
+  NSR_TRY(open_work(c, w_coarse, w_fine, false, workspace, workspace_bytes, k));
   hipStream_t st = nsr_stream(stream);
   const double mse_scale = 1.0 / (3.0 * (double)(R / s2));
   NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream));
@@ -651,8 +757,11 @@ extern "C" int nsr_train_loss_and_grads(const float* const* w_coarse, const floa
 }
 
 extern "C" size_t nsr_train_saved_bytes(int precision, int64_t R, int n_coarse, int n_importance, int64_t ray_chunk) {
-  if (R <= 0 || check_shape(R, 1, n_coarse, n_importance, precision, ray_chunk) != NSR_OK) return 0;
-  return (size_t)saved_layout(precision, R, n_coarse, n_importance, ray_chunk).total * sizeof(float);
+  return saved_bytes_of(&kDefaultArch, false, precision, R, n_coarse, n_importance, ray_chunk);
+}
+extern "C" size_t nsr_train_arch_saved_bytes(const nsr_arch* arch, int precision, int64_t R, int n_coarse, int n_importance,
+                                             int64_t ray_chunk) {
+  return saved_bytes_of(arch, true, precision, R, n_coarse, n_importance, ray_chunk);
 }
 
 extern "C" int nsr_train_forward(const float* const* w_coarse, const float* const* w_fine, const float* rays, int ray_stride,
@@ -660,75 +769,31 @@ extern "C" int nsr_train_forward(const float* const* w_coarse, const float* cons
                                  const float* u_coarse, const float* u_fine, const float* noise_coarse, const float* noise_fine,
                                  float noise_std, int precision, int64_t ray_chunk, float* const* outs, void* workspace,
                                  size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream) {
-  Run c{};
-  c.R = R; c.chunk = ray_chunk; c.nc = n_coarse; c.ni = n_importance; c.flags = render_flags; c.precision = precision;
-  c.lindisp = lindisp; c.ray_stride = ray_stride; c.noise_std = noise_std;
-  NSR_TRY(check_args({{w_coarse, w_fine, outs}, {w_coarse, w_fine}, outs, {rays, workspace, saved}, {workspace, saved}}, &c, 1));
-  if (R == 0) return NSR_OK;
-  Work k;
-  NSR_TRY(open_work(c, workspace, workspace_bytes, k));
-  const SavedLayout L = saved_layout(precision, R, n_coarse, n_importance, c.chunk);
-  if (saved_bytes < (size_t)L.total * sizeof(float)) return NSR_ERR_WORKSPACE;
-  hipStream_t st = nsr_stream(stream);
-  float* sv = static_cast<float*>(saved);
-  if (c.chain)   // the backward weight streams are packed into the saved state: the backward call uses them as they are
-    for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
-  const SavedHeader h{kSavedMagic, (uint64_t)L.total, R, c.chunk, n_coarse, n_importance, render_flags, precision};
-  hipLaunchKernelGGL(saved_header_kernel, dim3(1), dim3(64), 0, st, h, reinterpret_cast<unsigned*>(sv));
-  NSR_CHECK_LAUNCH();
-  NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream));
-  const float* z_c = nullptr;   // the coarse pass's samples of the chunk at hand
-  return for_each_pass(c, [&](const Pass& q) -> int {
-    k.kept = saved_kept(sv, L, c, q);
-    if (q.net == 0) z_c = k.kept.z;
-    float* const* o = outs + 4 * q.net;
-    return pass_forward(st, k, c, q, q.net ? w_fine : w_coarse, rays, q.net ? u_fine : u_coarse,
-                        q.net ? noise_fine : noise_coarse, z_c, rows_of(outs[3], q, c.nc, k.w_c), k.kept.z, o[0] + q.r0 * 3,
-                        rows_of(o[1], q, 1), rows_of(o[2], q, 1), rows_of(o[3], q, q.N, q.net ? nullptr : k.w_c), stream);
-  });
+  return train_forward(&kDefaultArch, false, w_coarse, w_fine, rays, ray_stride, R, n_coarse, n_importance, render_flags, lindisp,
+                       u_coarse, u_fine, noise_coarse, noise_fine, noise_std, precision, ray_chunk, outs, workspace, workspace_bytes,
+                       saved, saved_bytes, stream);
+}
+extern "C" int nsr_train_arch_forward(const nsr_arch* arch, const float* const* w_coarse, const float* const* w_fine,
+                                      const float* rays, int ray_stride, int64_t R, int n_coarse, int n_importance, int render_flags,
+                                      int lindisp, const float* u_coarse, const float* u_fine, const float* noise_coarse,
+                                      const float* noise_fine, float noise_std, int precision, int64_t ray_chunk, float* const* outs,
+                                      void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream) {
+  return train_forward(arch, true, w_coarse, w_fine, rays, ray_stride, R, n_coarse, n_importance, render_flags, lindisp, u_coarse,
+                       u_fine, noise_coarse, noise_fine, noise_std, precision, ray_chunk, outs, workspace, workspace_bytes, saved,
+                       saved_bytes, stream);
 }
 
 extern "C" int nsr_train_backward(const float* const* w_coarse, const float* const* w_fine, const float* const* g_outs,
                                   float* const* g_coarse, float* const* g_fine, void* workspace, size_t workspace_bytes,
                                   const void* saved, size_t saved_bytes, void* stream) {
-  NSR_TRY(check_args({{w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, saved}, {w_coarse, w_fine, g_coarse, g_fine},
-                      nullptr, {}, {workspace, saved}}, nullptr, 1));
-  if (saved_bytes < (size_t)kSavedHeaderFloats * sizeof(float)) return NSR_ERR_WORKSPACE;
-  // the run's parameters, read back from the header the forward call wrote (waits for the stream)
-  hipStream_t st = nsr_stream(stream);
-  SavedHeader h{};
-  if (hipMemcpyAsync(&h, saved, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess) return NSR_ERR_LAUNCH;
-  if (hipStreamSynchronize(st) != hipSuccess) return NSR_ERR_LAUNCH;
-  if (h.magic != kSavedMagic) return NSR_ERR_INVALID_ARG;
-  if (h.floats > saved_bytes / sizeof(float)) return NSR_ERR_WORKSPACE;   // the header says the state is larger than the buffer
-  // bounds before anything loops over them (a damaged header may hold anything): every ray and every chunk takes at least
-  // 64 floats of the layout, so neither count can exceed what the buffer holds
-  if (h.R <= 0 || h.chunk <= 0 || h.chunk > h.R || (uint64_t)h.R > h.floats / 64 ||
-      (uint64_t)((h.R + h.chunk - 1) / h.chunk) > h.floats / 64)
-    return NSR_ERR_INVALID_ARG;
-  Run c{};   // no sampling in this half: lindisp, ray_stride and noise_std stay unused
-  c.R = h.R; c.chunk = h.chunk; c.nc = h.nc; c.ni = h.ni; c.flags = h.flags; c.precision = h.precision;
-  if (check_shape(c.R, 1, c.nc, c.ni, c.precision, c.chunk) != NSR_OK || c.chunk != h.chunk || check_flags(c.flags) != NSR_OK)
-    return NSR_ERR_INVALID_ARG;
-  const SavedLayout L = saved_layout(c.precision, c.R, c.nc, c.ni, c.chunk);
-  if ((uint64_t)L.total != h.floats) return NSR_ERR_INVALID_ARG;
-  Work k;
-  NSR_TRY(open_work(c, workspace, workspace_bytes, k));
-  float* sv = const_cast<float*>(static_cast<const float*>(saved));   // read only
-  if (c.chain) {
-    for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
-  } else {   // the padded weight copies the layer-by-layer backward reads (deterministic: the forward call's own)
-    NSR_TRY(prepare_weights(st, w_coarse, k.pack[0], gemm_precision(c.precision)));
-    NSR_TRY(prepare_weights(st, w_fine, k.pack[1], gemm_precision(c.precision)));
-  }
-  // the fused step's order of passes: the first chunk overwrites the gradients, later chunks accumulate
-  return for_each_pass(c, [&](const Pass& q) -> int {
-    k.kept = saved_kept(sv, L, c, q);
-    const float* const* go = g_outs + 4 * q.net;
-    if (!go[0] && hipMemsetAsync(k.g_comp, 0, (size_t)q.rc * 3 * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
-    return pass_backward(st, k, c, q, q.net ? w_fine : w_coarse, k.kept.z, rows_of(go[0], q, 3, k.g_comp), rows_of(go[1], q, 1),
-                         rows_of(go[2], q, 1), rows_of(go[3], q, q.N), q.net ? g_fine : g_coarse, stream);
-  });
+  return train_backward(&kDefaultArch, false, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved,
+                        saved_bytes, stream);
+}
+extern "C" int nsr_train_arch_backward(const nsr_arch* arch, const float* const* w_coarse, const float* const* w_fine,
+                                       const float* const* g_outs, float* const* g_coarse, float* const* g_fine, void* workspace,
+                                       size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream) {
+  return train_backward(arch, true, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved, saved_bytes,
+                        stream);
 }
 
 extern "C" int nsr_train_status_reset(void* workspace, void* stream) {
@@ -748,19 +813,28 @@ extern "C" int nsr_train_status(void* workspace, int clear, unsigned* flags_out,
   return NSR_OK;
 }
 
-extern "C" int nsr_adam_step(float* const* w, const float* const* g, float* const* m, float* const* v, int step, float lr,
-                             float beta1, float beta2, float eps, void* stream) {
-  if (!w || !g || !m || !v || step < 1) return NSR_ERR_INVALID_ARG;
-  AdamPtrs a;
-  for (int i = 0; i < NSR_N_STATE_TENSORS; ++i) {
-    if (!w[i] || !g[i] || !m[i] || !v[i]) return NSR_ERR_INVALID_ARG;
-    a.w[i] = w[i]; a.g[i] = g[i]; a.m[i] = m[i]; a.v[i] = v[i];
+extern "C" int nsr_adam_step_n(int n, const int64_t* numel, float* const* w, const float* const* g, float* const* m, float* const* v,
+                               int step, float lr, float beta1, float beta2, float eps, void* stream) {
+  if (n < 1 || n > kMaxT || !numel || !w || !g || !m || !v || step < 1) return NSR_ERR_INVALID_ARG;
+  AdamN a{};
+  for (int i = 0; i < n; ++i) {
+    if (!w[i] || !g[i] || !m[i] || !v[i] || numel[i] < 0) return NSR_ERR_INVALID_ARG;
+    a.w[i] = w[i]; a.g[i] = g[i]; a.m[i] = m[i]; a.v[i] = v[i]; a.n[i] = numel[i];
   }
   // bias corrections in double like Python's floats, then one rounding to fp32
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  hipLaunchKernelGGL(adam_kernel, dim3(64, NSR_N_STATE_TENSORS), dim3(256), 0, nsr_stream(stream), a, beta1, beta2, eps,
-                     step_size, bc2_sqrt);
+  hipLaunchKernelGGL(adam_n_kernel, dim3(64, n), dim3(256), 0, nsr_stream(stream), a, beta1, beta2, eps, step_size, bc2_sqrt);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
+}
+
+// the 24 tensors of the default network
+extern "C" int nsr_adam_step(float* const* w, const float* const* g, float* const* m, float* const* v, int step, float lr,
+                             float beta1, float beta2, float eps, void* stream) {
+  Shape S;
+  NSR_TRY(make_shape(&kDefaultArch, S));
+  int64_t numel[NSR_N_STATE_TENSORS];
+  for (int t = 0; t < NSR_N_STATE_TENSORS; ++t) numel[t] = tensor_numel_of(S, t);
+  return nsr_adam_step_n(NSR_N_STATE_TENSORS, numel, w, g, m, v, step, lr, beta1, beta2, eps, stream);
 }

@@ -1,19 +1,28 @@
-// Layer-by-layer GEMM path of the training step (precisions NSR_FP32 and NSR_F16X3_GEMM; nsr_train.hip calls it).
+// The layer-by-layer network of the training step (precisions NSR_FP32 and NSR_F16X3_GEMM; the drivers of nsr_train.hip call
+// it), for ANY architecture the reference's flags describe (include/nsr_train.h, nsr_arch: --D --W --skips --deg_pos --deg_dir
+// --no_dir).  The default 8 x 256 network is the descriptor {8, 256, skips {4}, 10, 4, 0}: there is no second implementation.
 //
 // The MLP runs layer by layer on one fp32-MFMA GEMM kernel (nsr_gemm.hip; nsr_gemm_f16.hip for the split-fp16 forward
 // products) whose epilogue fuses bias / ReLU / sigmoid / the ReLU mask of the backward pass.  The kernel takes either memory
 // orientation of each operand, so all three products of a linear layer (forward, input gradient, weight gradient) read
 // the row-major (P, C) activations and the nn.Linear weights as they lie: nothing is transposed and nothing is stored
 // twice.  The weight gradient is a split-K GEMM over the sample points with a deterministic second-pass reduction (no
-// atomics: results are run-to-run identical).  Layers are padded to MFMA-friendly shapes once per step (63 -> 64 input
-// channels, the skip concat as [pe64 | h4], the density head stacked under xyz_encoding_final as one 288-row layer, the
-// colour head as 32 rows); the gradients are scattered back to the nn.Linear shapes by the reduction kernel.
+// atomics: results are run-to-run identical).
+//
+// Everything is a function of the descriptor at run time (Shape, nsr_train_work.h: the layout of a pass is described there):
+// the padded shapes, the kept state, the padded weight copies and their split-fp16 halves (Pack), the drivers over the D trunk
+// layers (net_forward / net_backward).  Layers are padded to multiples of 32 once per call; the gradients are scattered back
+// to the nn.Linear shapes by the reduction kernel.  Backward: the density head is stacked under xyz_encoding_final as one
+// (Wp + 32)-row layer, so the gradient of the trunk's last activation is one product over [d final | d sigma 0 .. 0]; the
+// colour head is 32 rows.
 #include "nsr_gemm.h"
 #include "nsr_train_work.h"
 
 using namespace nsr;
 
 namespace {
+
+inline int r32(int n) { return (n + 31) & ~31; }
 
 // dst[(r0 + i) * ld + c0 + j] = src[i][col0 + j]  (or the transpose: dst[(r0 + j) * ld + c0 + i])
 __global__ void place_kernel(float* __restrict__ dst, int dst_ld, int r0, int c0, const float* __restrict__ src,
@@ -26,39 +35,70 @@ __global__ void place_kernel(float* __restrict__ dst, int dst_ld, int r0, int c0
   else dst[(int64_t)(r0 + i) * dst_ld + c0 + j] = v;
 }
 
-// E1 + cast_rays for the training layout: one thread per sample point.
-//   x5 (P, 320) columns 0..63  = [pe63, 0]
-//   gs (P, 288) columns 257..287 = [0 0 0, de27, 0]
-__global__ void __launch_bounds__(256) encode_train_kernel(const float* __restrict__ rays, int stride,
-                                                           const float* __restrict__ z, int64_t P, int N,
-                                                           float* __restrict__ x5, float* __restrict__ gs) {
-  const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// E1 + cast_rays with run-time degree: one thread per (sample point, 4 columns) writes dst[p][4 g .. 4 g + 4) of
+//   [x, sin(2^0 x), cos(2^0 x), sin(2^1 x), ...  | zeros up to 4 n_groups]      (x: the point o + z d, or the view direction)
+// with nsr_sincos on the ldexpf frequencies.
+// The row is computed once and written to every destination (one x buffer per skip layer; all with row stride ld).
+struct EncodeDst {
+  float* p[kMaxD];
+  int n;
+};
+__global__ void __launch_bounds__(256) encode_arch_kernel(const float* __restrict__ rays, int stride, const float* __restrict__ z,
+                                                          int64_t P, int N, int deg, int view_dir, EncodeDst dst, int64_t ld,
+                                                          int n_groups) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t p = idx / n_groups;
+  const int g = (int)(idx % n_groups);
   if (p >= P) return;
   const NsrRay q = nsr_load_ray(rays, p / N, stride);
-  const float zk = z[p];
-  float pe[64];
+  float x[3];
+  if (view_dir) {
 #pragma unroll
-  for (int c = 0; c < 3; ++c) pe[c] = __fadd_rn(q.o[c], __fmul_rn(zk, q.d[c]));   // cast_rays, models/utils.py:5-14
+    for (int c = 0; c < 3; ++c) x[c] = q.v[c];
+  } else {
+    const float zk = z[p];
 #pragma unroll
-  for (int f = 0; f < 10; ++f)
+    for (int c = 0; c < 3; ++c) x[c] = __fadd_rn(q.o[c], __fmul_rn(zk, q.d[c]));   // cast_rays, models/utils.py:5-14
+  }
+  const int n_valid = 3 + 6 * deg;
+  float out[4];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) nsr_sincos(ldexpf(pe[c], f), pe[3 + 6 * f + c], pe[3 + 6 * f + 3 + c]);
-  pe[63] = 0.0f;
-  float4* row = reinterpret_cast<float4*>(x5 + p * kX5);
-#pragma unroll
-  for (int i = 0; i < 16; ++i) row[i] = make_float4(pe[4 * i], pe[4 * i + 1], pe[4 * i + 2], pe[4 * i + 3]);
-  float de[31];   // columns 257..287
-  de[0] = de[1] = de[2] = 0.0f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) de[3 + c] = q.v[c];
-#pragma unroll
-  for (int f = 0; f < 4; ++f)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) nsr_sincos(ldexpf(q.v[c], f), de[6 + 6 * f + c], de[6 + 6 * f + 3 + c]);
-  de[30] = 0.0f;
-#pragma unroll
-  for (int c = 0; c < 31; ++c) gs[p * kGs + 257 + c] = de[c];
+  for (int e = 0; e < 4; ++e) {
+    const int c = 4 * g + e;
+    float v = 0.0f;
+    if (c < 3) {
+      v = c == 0 ? x[0] : (c == 1 ? x[1] : x[2]);
+    } else if (c < n_valid) {
+      const int f = (c - 3) / 6, r = (c - 3) % 6, comp = r % 3;
+      const float xc = comp == 0 ? x[0] : (comp == 1 ? x[1] : x[2]);
+      float sn, cs;
+      nsr_sincos(ldexpf(xc, f), sn, cs);
+      v = r < 3 ? sn : cs;
+    }
+    out[e] = v;
+  }
+  for (int j = 0; j < dst.n; ++j)
+    *reinterpret_cast<float4*>(dst.p[j] + p * ld + 4 * g) = make_float4(out[0], out[1], out[2], out[3]);
 }
+
+// the compositing backward's compact rows d4[p] = (d rgb_pre 0..2, d sigma) into the layouts the two heads' products read:
+// drgb (P, 32) = [d rgb_pre | 0], gsig[p * ldg + 0 .. 32) = [d sigma | 0].  One thread per (point, float4).
+__global__ void __launch_bounds__(256) scatter_heads_kernel(const float4* __restrict__ d4, int64_t P, float* __restrict__ drgb,
+                                                            float* __restrict__ gsig, int64_t ldg) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t p = idx >> 3;
+  const int j = (int)(idx & 7);
+  if (p >= P) return;
+  float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+  if (j == 0) {
+    const float4 v = d4[p];
+    a = make_float4(v.x, v.y, v.z, 0.0f);
+    b.x = v.w;
+  }
+  reinterpret_cast<float4*>(drgb + p * 32)[j] = a;
+  reinterpret_cast<float4*>(gsig + p * ldg)[j] = b;
+}
+
 // bias gradients.  Two deterministic passes each (double accumulation, then one finishing block):
 //   colsum_few:  sums of <= 4 columns of a row-major buffer over all P rows (colour-head and density-head biases,
 //                whose pre-activation gradients come from the compositing backward, not from a GEMM)
@@ -127,11 +167,9 @@ __global__ void __launch_bounds__(256) reduce_place_kernel(float* __restrict__ d
   float* d = dst + (int64_t)i * dst_ld + dc0 + j;
   *d = (accumulate ? *d : 0.0f) + (float)(s * (double)scale);   // scale: a power of two (pre-scaled operands)
 }
-}  // namespace
-
-// ---- host wrappers over the kernels above, shared with nsr_train_arch.hip (declared in nsr_train_work.h)
-int nsr::place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* src, int src_ld, int rows, int cols,
-               int col0, int transpose) {
+// ---- host wrappers over the kernels above: one linear layer's three products, the deterministic reductions behind them
+int place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* src, int src_ld, int rows, int cols,
+          int col0, int transpose) {
   const int n = rows * cols;
   hipLaunchKernelGGL(place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, dst_ld, r0, c0, src, src_ld, rows, cols,
                      col0, transpose);
@@ -140,9 +178,9 @@ int nsr::place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const flo
 }
 
 // y (P, N) = act(x (P, K) w (N, K)^T + b); hi / lo (the weights' split-fp16 halves, row stride ldh) select the split-fp16 product
-int nsr::lin_fwd_at(hipStream_t st, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
-                    float* y, int64_t ldy, int64_t P, int N, int n_valid, const unsigned short* hi, const unsigned short* lo,
-                    int ldh) {
+int lin_fwd_at(hipStream_t st, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
+               float* y, int64_t ldy, int64_t P, int N, int n_valid, const unsigned short* hi, const unsigned short* lo,
+               int ldh) {
   GemmArgs g{};
   g.A = x; g.lda = ldx; g.B = w; g.ldb = ldw; g.C = y; g.ldc = ldy; g.bias = b;
   g.M = P; g.N = N; g.K = K; g.n_valid = n_valid; g.act = act; g.splits = 1;
@@ -155,30 +193,21 @@ int nsr::lin_fwd_at(hipStream_t st, const float* x, int64_t ldx, int K, const fl
   a.ldbh = ldh;
   return gemm_f16x3(a, st);
 }
-namespace {
-// the default network: `split` (entry e of the pack's split block) selects the split-fp16 product
-int lin_fwd(hipStream_t st, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
-            float* y, int64_t ldy, int64_t P, int N, int n_valid, const unsigned short* split = nullptr, int e = 0) {
-  const unsigned short* hi = split ? split + split_offset(e) : nullptr;
-  return lin_fwd_at(st, x, ldx, K, w, ldw, b, act, y, ldy, P, N, n_valid, hi, hi ? hi + (int64_t)kSplitRows[e] * kSplitK[e] : nullptr,
-                    kSplitK[e]);
-}
-}  // namespace
 // dx (P, N) = (dy (P, K) w[:, 0 : N]) * [mask > 0], w (K, ldw) in the nn.Linear layout (mask may be null);
 // bias_grad (N) (+)= column sums of dx = the bias gradient of the layer that produced the masked activation
 // n_bias (0: N): how many of the N columns the bias has (a padded layer's trailing columns are exact zeros)
-int nsr::lin_dgrad(hipStream_t st, const Work& k, const float* dy, int64_t lddy, int K, const float* w, int ldw,
-                   const float* mask, int64_t ldm, float* dx, int64_t lddx, int64_t P, int N, float* bias_grad, int acc,
-                   int n_bias) {
+int lin_dgrad(hipStream_t st, float* col_tiles, const float* dy, int64_t lddy, int K, const float* w, int ldw,
+              const float* mask, int64_t ldm, float* dx, int64_t lddx, int64_t P, int N, float* bias_grad, int acc,
+              int n_bias) {
   GemmArgs g{};
   g.A = dy; g.lda = lddy; g.B = w; g.ldb = ldw; g.b_kmajor = 1; g.C = dx; g.ldc = lddx;
   g.mask = mask; g.ldm = ldm; g.M = P; g.N = N; g.K = K; g.n_valid = N; g.act = kActNone; g.splits = 1;
-  g.col_sums = bias_grad ? k.col_tiles : nullptr;
+  g.col_sums = bias_grad ? col_tiles : nullptr;
   const int rc = gemm(g, st);
   if (rc != NSR_OK || !bias_grad) return rc;
-  double* part = reinterpret_cast<double*>(k.col_tiles + ((P + 127) / 128) * N);   // behind the tile sums
+  double* part = reinterpret_cast<double*>(col_tiles + ((P + 127) / 128) * N);   // behind the tile sums
   const int slices = 64;
-  hipLaunchKernelGGL(tilesum_partial_kernel, dim3((N + 63) / 64, slices), dim3(256), 0, st, k.col_tiles, (P + 127) / 128, N,
+  hipLaunchKernelGGL(tilesum_partial_kernel, dim3((N + 63) / 64, slices), dim3(256), 0, st, col_tiles, (P + 127) / 128, N,
                      N, part);
   NSR_CHECK_LAUNCH();
   const int nb = n_bias > 0 ? n_bias : N;
@@ -188,15 +217,15 @@ int nsr::lin_dgrad(hipStream_t st, const Work& k, const float* dy, int64_t lddy,
 }
 // partial[z] (M x N) = sum over the z-th slice of the points of dy[p][0..M) x[p][0..N)^T
 // (slice z at partial + z * stride)
-int nsr::lin_wgrad(hipStream_t st, const float* dy, int64_t lddy, int M, const float* x, int64_t ldx, int N, int64_t P,
-                   float* partial, int splits, int64_t stride) {
+int lin_wgrad(hipStream_t st, const float* dy, int64_t lddy, int M, const float* x, int64_t ldx, int N, int64_t P,
+              float* partial, int splits, int64_t stride) {
   GemmArgs g{};
   g.A = dy; g.lda = lddy; g.a_kmajor = 1; g.B = x; g.ldb = ldx; g.b_kmajor = 1; g.C = partial; g.ldc = N;
   g.M = M; g.N = N; g.K = P; g.n_valid = N; g.act = kActNone; g.splits = splits; g.split_stride = stride;
   return gemm(g, st);
 }
-int nsr::reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows, int cols, const float* partial, int splits,
-                      int p_ld, int pr0, int pc0, int accumulate, float scale, int64_t stride) {
+int reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows, int cols, const float* partial, int splits,
+                 int p_ld, int pr0, int pc0, int accumulate, float scale, int64_t stride) {
   const int n = rows * cols;
   hipLaunchKernelGGL(reduce_place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, dst_ld, dc0, rows, cols, partial,
                      splits, stride, p_ld, pr0, pc0, accumulate, scale);
@@ -204,8 +233,8 @@ int nsr::reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows,
   return NSR_OK;
 }
 // `scratch`: >= kSumBlocks * 4 doubles (the split-K partial buffer is free between two weight gradients)
-int nsr::colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, float* dst, int accumulate,
-                float* scratch) {
+int colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, float* dst, int accumulate,
+           float* scratch) {
   if (cols > 4) return NSR_ERR_INVALID_ARG;
   double* part = reinterpret_cast<double*>(scratch);
   hipLaunchKernelGGL(colsum_few_kernel, dim3(kSumBlocks), dim3(256), 0, st, src, ld, P, col0, cols, part);
@@ -215,104 +244,243 @@ int nsr::colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col
   return NSR_OK;
 }
 
-int nsr::prepare_weights(hipStream_t st, const float* const* w, const WeightPack& q, int precision) {
-  // zero the whole pack first (padding rows / columns), it is one contiguous block starting at w1p
-  if (hipMemsetAsync(q.w1p, 0, (size_t)((q.brgbp + align64(64)) - q.w1p) * sizeof(float), st) != hipSuccess)
-    return NSR_ERR_LAUNCH;
-  NSR_TRY(place(st, q.w1p, 64, 0, 0, w[0], 63, 256, 63, 0, 0));
-  NSR_TRY(place(st, q.w5p, 320, 0, 0, w[8], 319, 256, 63, 0, 0));
-  NSR_TRY(place(st, q.w5p, 320, 0, 64, w[8], 319, 256, 256, 63, 0));
-  NSR_TRY(place(st, q.w9p, 256, 0, 0, w[kFinalW], 256, 256, 256, 0, 0));
-  NSR_TRY(place(st, q.w9p, 256, 256, 0, w[kSigmaW], 256, 1, 256, 0, 0));
-  NSR_TRY(place(st, q.wdirp, 288, 0, 0, w[kDirW], 283, 128, 256, 0, 0));
-  NSR_TRY(place(st, q.wdirp, 288, 0, kDeCol, w[kDirW], 283, 128, 27, 256, 0));
-  NSR_TRY(place(st, q.wrgbp, 128, 0, 0, w[kRgbW], 128, 3, 128, 0, 0));
-  NSR_TRY(place(st, q.b9p, 320, 0, 0, w[kFinalB], 256, 1, 256, 0, 0));
-  NSR_TRY(place(st, q.b9p, 320, 0, 256, w[kSigmaB], 1, 1, 1, 0, 0));
-  NSR_TRY(place(st, q.brgbp, 64, 0, 0, w[kRgbB], 3, 1, 3, 0, 0));
-  if (precision == NSR_F16X3) {
-    const float* src[12] = {q.w1p, w[2], w[4], w[6], q.w5p, w[10], w[12], w[14], q.w9p, q.w9p + 256 * 256, q.wdirp, q.wrgbp};
-    for (int e = 0; e < 12; ++e) {
-      const int64_t n = (int64_t)kSplitRows[e] * kSplitK[e];
-      NSR_TRY(split_f16(src[e], n, q.split + split_offset(e), q.split + split_offset(e) + n, st));
-    }
+// ---- the network
+struct Mat { float* p; int64_t ld; };
+Mat out_of(const Shape& S, const Kept& s, int l) {
+  if (s.h[l]) return {s.h[l], S.Wp};
+  return {s.x[S.x_of[l + 1]] + S.Kx, S.Xs};
+}
+Mat in_of(const Shape& S, const Kept& s, int l) {
+  if (l == 0) return {s.x[0], S.ldx};
+  if (S.skip(l)) return {s.x[S.x_of[l]], S.Xs};
+  return out_of(S, s, l - 1);
+}
+
+struct Lin {   // a trunk layer's forward operand: weights with row stride ldw (the padded copy, or the caller's tensor), bias
+  const float* w;
+  int ldw;
+  const float* b;
+};
+Lin trunk_lin(const Shape& S, const Pack& q, const float* const* w, int l) {
+  return {q.wl[l] ? q.wl[l] : w[2 * l], q.wl[l] ? S.kin(l) : S.W, q.bl[l] ? q.bl[l] : w[2 * l + 1]};
+}
+
+// one forward layer: x (P, K) -> y (P, N); split: on entry e of the pack's split-fp16 halves
+int fwd(hipStream_t st, const Pack& q, bool split, int e, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
+        float* y, int64_t ldy, int64_t P, int N, int n_valid) {
+  const unsigned short* hi = split ? q.hi[e] : nullptr;
+  return lin_fwd_at(st, x, ldx, K, w, ldw, b, act, y, ldy, P, N, n_valid, hi, hi ? hi + (int64_t)N * K : nullptr, K);
+}
+
+}  // namespace
+
+int nsr::make_shape(const nsr_arch* a, Shape& S) {
+  if (!a) return NSR_ERR_INVALID_ARG;
+  if (a->D < 1 || a->W < 2 || (a->W & 1) || a->deg_pos < 0 || a->deg_dir < 0 || (a->no_dir != 0 && a->no_dir != 1))
+    return NSR_ERR_INVALID_ARG;
+  if ((a->skips & 1u) || (a->D < 32 && (a->skips >> a->D) != 0u)) return NSR_ERR_INVALID_ARG;
+  if (a->D > NSR_ARCH_MAX_D || a->W > NSR_ARCH_MAX_W || a->deg_pos > NSR_ARCH_MAX_DEG || a->deg_dir > NSR_ARCH_MAX_DEG)
+    return NSR_ERR_UNSUPPORTED;
+  S.arch = *a;
+  S.D = a->D; S.W = a->W; S.H = a->W / 2; S.skips = a->skips; S.no_dir = a->no_dir;
+  S.in_xyz = 3 + 6 * a->deg_pos; S.in_dir = 3 + 6 * a->deg_dir;
+  S.Kx = r32(S.in_xyz); S.Wp = r32(S.W); S.Hp = r32(S.H); S.Dp = a->no_dir ? 0 : r32(S.in_dir);
+  S.Ci = S.Wp + S.Dp; S.Xs = S.Kx + S.Wp;
+  int ns = 0;
+  for (int l = 0; l < S.D; ++l) {
+    S.x_of[l] = -1;
+    if (S.skip(l)) S.x_of[l] = ns++;
   }
+  S.x_of[0] = 0;
+  S.n_x = ns > 0 ? ns : 1;
+  S.ldx = ns > 0 ? S.Xs : S.Kx;
+  int kin_max = S.Kx > S.Wp ? S.Kx : S.Wp;
+  if (ns > 0) kin_max = S.Xs;
+  int64_t m = (int64_t)S.Wp * kin_max;
+  if ((int64_t)S.Hp * S.Ci > m) m = (int64_t)S.Hp * S.Ci;
+  if (32 * (int64_t)S.Wp > m) m = 32 * (int64_t)S.Wp;
+  S.part_stride = align64(m);
   return NSR_OK;
 }
-int nsr::net_forward(hipStream_t st, const float* rays, int ray_stride, const float* z, int N, const float* const* w,
-                     const WeightPack& q, const Kept& s, int64_t P, int precision, int color_none) {
-  hipLaunchKernelGGL(encode_train_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, rays, ray_stride, z, P, N, s.x5, s.gs);
-  NSR_CHECK_LAUNCH();
-  const unsigned short* sp = precision == NSR_F16X3 ? q.split : nullptr;
-  NSR_TRY(lin_fwd(st, s.x5, kX5, kPe, q.w1p, 64, w[1], kActRelu, s.h[1], kW, P, kW, kW, sp, 0));
-  NSR_TRY(lin_fwd(st, s.h[1], kW, kW, w[2], 256, w[3], kActRelu, s.h[2], kW, P, kW, kW, sp, 1));
-  NSR_TRY(lin_fwd(st, s.h[2], kW, kW, w[4], 256, w[5], kActRelu, s.h[3], kW, P, kW, kW, sp, 2));
-  NSR_TRY(lin_fwd(st, s.h[3], kW, kW, w[6], 256, w[7], kActRelu, s.x5 + kPe, kX5, P, kW, kW, sp, 3));
-  NSR_TRY(lin_fwd(st, s.x5, kX5, kX5, q.w5p, 320, w[9], kActRelu, s.h[5], kW, P, kW, kW, sp, 4));
-  NSR_TRY(lin_fwd(st, s.h[5], kW, kW, w[10], 256, w[11], kActRelu, s.h[6], kW, P, kW, kW, sp, 5));
-  NSR_TRY(lin_fwd(st, s.h[6], kW, kW, w[12], 256, w[13], kActRelu, s.h[7], kW, P, kW, kW, sp, 6));
-  NSR_TRY(lin_fwd(st, s.h[7], kW, kW, w[14], 256, w[15], kActRelu, s.h[8], kW, P, kW, kW, sp, 7));
-  // xyz_encoding_final stacked over the density head: [g | sigma] into columns 0..256 of the dir layer's input
-  // (two launches: the 256 wide columns on the 8-wave tile, the density row on the narrow one, instead of a second
-  // 256-wide column tile that would be 7/8 padding)
-  NSR_TRY(lin_fwd(st, s.h[8], kW, kW, q.w9p, 256, q.b9p, kActNone, s.gs, kGs, P, kW, kW, sp, 8));
-  NSR_TRY(lin_fwd(st, s.h[8], kW, kW, q.w9p + 256 * 256, 256, q.b9p + 256, kActNone, s.gs + kSigmaCol, kGs, P, 32, 1, sp, 9));
-  NSR_TRY(lin_fwd(st, s.gs, kGs, kGs, q.wdirp, 288, w[kDirB], kActRelu, s.cc, kDirOut, P, kDirOut, kDirOut, sp, 10));
-  NSR_TRY(lin_fwd(st, s.cc, kDirOut, kDirOut, q.wrgbp, 128, q.brgbp, color_none ? kActNone : kActSigmoid, s.rgb, 4, P, kRgbPad, 3, sp, 11));
+int64_t nsr::tensor_numel_of(const Shape& S, int t) {
+  if (t < 0 || t >= S.n_tensors()) return 0;
+  if (t < 2 * S.D) return (t & 1) ? S.W : (int64_t)S.W * S.fan_in(t / 2);
+  switch (t - 2 * S.D) {
+    case 0: return (int64_t)S.W * S.W;
+    case 1: return S.W;
+    case 2: return (int64_t)S.H * S.dir_in();
+    case 3: return S.H;
+    case 4: return S.W;
+    case 5: return 1;
+    case 6: return 3 * (int64_t)S.H;
+    default: return 3;
+  }
+}
+
+void nsr::carve_net_kept(Carver& a, const Shape& S, int64_t P, Kept& q) {
+  for (int j = 0; j < S.n_x; ++j) q.x[j] = a.take(P * S.ldx);
+  for (int l = 0; l < S.D; ++l) q.h[l] = (l + 1 < S.D && S.skip(l + 1)) ? nullptr : a.take(P * S.Wp);
+  q.ci = a.take(P * S.Ci);   q.cc = a.take(P * S.Hp);
+}
+Pack nsr::carve_pack(Carver& a, const Shape& S, bool split) {
+  Pack q{};
+  const int64_t off0 = a.off;
+  q.first = a.take(0);
+  for (int l = 0; l < S.D; ++l) {
+    const bool pad = l == 0 || S.skip(l) || S.W != S.Wp;
+    q.wl[l] = a.take((int64_t)S.Wp * S.kin(l), pad);
+    q.bl[l] = a.take(S.Wp, S.W != S.Wp);
+  }
+  q.w9 = a.take((int64_t)(S.Wp + 32) * S.Wp);   q.b9 = a.take(S.Wp + 32);
+  q.wdir = a.take((int64_t)S.Hp * S.Ci);        q.bdir = a.take(S.Hp, S.H != S.Hp);
+  q.wrgb = a.take(32 * (int64_t)S.Hp);          q.brgb = a.take(32);
+  q.floats = a.off - off0;
+  if (split) {
+    for (int l = 0; l < S.D; ++l) q.hi[l] = reinterpret_cast<unsigned short*>(a.take((int64_t)S.Wp * S.kin(l)));
+    q.hi[kFinalE] = reinterpret_cast<unsigned short*>(a.take((int64_t)S.Wp * S.Wp));
+    q.hi[kSigmaE] = reinterpret_cast<unsigned short*>(a.take(32 * (int64_t)S.Wp));
+    q.hi[kDirE] = reinterpret_cast<unsigned short*>(a.take((int64_t)S.Hp * S.Ci));
+    q.hi[kRgbE] = reinterpret_cast<unsigned short*>(a.take(32 * (int64_t)S.Hp));
+  }
+  return q;
+}
+int nsr::prepare_weights(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, bool split) {
+  if (hipMemsetAsync(q.first, 0, (size_t)q.floats * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
+  for (int l = 0; l < S.D; ++l) {
+    if (q.wl[l]) {
+      const int fi = S.fan_in(l), kin = S.kin(l);
+      if (S.skip(l)) {
+        NSR_TRY(place(st, q.wl[l], kin, 0, 0, w[2 * l], fi, S.W, S.in_xyz, 0, 0));
+        NSR_TRY(place(st, q.wl[l], kin, 0, S.Kx, w[2 * l], fi, S.W, S.W, S.in_xyz, 0));
+      } else {
+        NSR_TRY(place(st, q.wl[l], kin, 0, 0, w[2 * l], fi, S.W, fi, 0, 0));
+      }
+    }
+    if (q.bl[l]) NSR_TRY(place(st, q.bl[l], S.Wp, 0, 0, w[2 * l + 1], S.W, 1, S.W, 0, 0));
+  }
+  const int F = S.final_w();
+  NSR_TRY(place(st, q.w9, S.Wp, 0, 0, w[F], S.W, S.W, S.W, 0, 0));
+  NSR_TRY(place(st, q.w9, S.Wp, S.Wp, 0, w[S.sigma_w()], S.W, 1, S.W, 0, 0));
+  NSR_TRY(place(st, q.b9, S.Wp + 32, 0, 0, w[F + 1], S.W, 1, S.W, 0, 0));
+  NSR_TRY(place(st, q.b9, S.Wp + 32, 0, S.Wp, w[S.sigma_w() + 1], 1, 1, 1, 0, 0));
+  NSR_TRY(place(st, q.wdir, S.Ci, 0, 0, w[S.dir_w()], S.dir_in(), S.H, S.W, 0, 0));
+  if (!S.no_dir) NSR_TRY(place(st, q.wdir, S.Ci, 0, S.Wp, w[S.dir_w()], S.dir_in(), S.H, S.in_dir, S.W, 0));
+  if (q.bdir) NSR_TRY(place(st, q.bdir, S.Hp, 0, 0, w[S.dir_w() + 1], S.H, 1, S.H, 0, 0));
+  NSR_TRY(place(st, q.wrgb, S.Hp, 0, 0, w[S.rgb_w()], S.H, 3, S.H, 0, 0));
+  NSR_TRY(place(st, q.brgb, 32, 0, 0, w[S.rgb_w() + 1], 3, 1, 3, 0, 0));
+  if (split) {
+    for (int l = 0; l < S.D; ++l) {
+      const int64_t n = (int64_t)S.Wp * S.kin(l);
+      NSR_TRY(split_f16(trunk_lin(S, q, w, l).w, n, q.hi[l], q.hi[l] + n, st));
+    }
+    const int64_t nf = (int64_t)S.Wp * S.Wp, ns = 32 * (int64_t)S.Wp, nd = (int64_t)S.Hp * S.Ci, nr = 32 * (int64_t)S.Hp;
+    NSR_TRY(split_f16(q.w9, nf, q.hi[kFinalE], q.hi[kFinalE] + nf, st));
+    NSR_TRY(split_f16(q.w9 + nf, ns, q.hi[kSigmaE], q.hi[kSigmaE] + ns, st));
+    NSR_TRY(split_f16(q.wdir, nd, q.hi[kDirE], q.hi[kDirE] + nd, st));
+    NSR_TRY(split_f16(q.wrgb, nr, q.hi[kRgbE], q.hi[kRgbE] + nr, st));
+  }
   return NSR_OK;
 }
 
-int nsr::net_backward(hipStream_t st, const float* const* w, const WeightPack& q, const Work& k, int64_t P, float* const* g,
-                      int acc, int stop_grad) {
+// E1 + cast_rays of the P = rays x N sample points, then the network with everything kept for the backward pass
+int nsr::net_forward(hipStream_t st, const Shape& S, const float* rays, int ray_stride, const float* z, int N, const float* const* w,
+                const Pack& q, const Kept& s, int64_t P, bool split, int color_none) {
+  {
+    EncodeDst dst{};
+    for (int j = 0; j < S.n_x; ++j) dst.p[j] = s.x[j];
+    dst.n = S.n_x;
+    const int64_t n = P * (S.Kx / 4);
+    hipLaunchKernelGGL(encode_arch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rays, ray_stride, z, P, N,
+                       S.arch.deg_pos, 0, dst, (int64_t)S.ldx, S.Kx / 4);
+    NSR_CHECK_LAUNCH();
+  }
+  if (!S.no_dir) {
+    const int64_t n = P * (S.Dp / 4);
+    EncodeDst dst{};
+    dst.p[0] = s.ci + S.Wp;
+    dst.n = 1;
+    hipLaunchKernelGGL(encode_arch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rays, ray_stride, z, P, N,
+                       S.arch.deg_dir, 1, dst, (int64_t)S.Ci, S.Dp / 4);
+    NSR_CHECK_LAUNCH();
+  }
+  for (int l = 0; l < S.D; ++l) {
+    const Mat x = in_of(S, s, l), y = out_of(S, s, l);
+    const Lin a = trunk_lin(S, q, w, l);
+    NSR_TRY(fwd(st, q, split, l, x.p, x.ld, S.kin(l), a.w, a.ldw, a.b, kActRelu, y.p, y.ld, P, S.Wp, S.Wp));
+  }
+  const Mat hD = out_of(S, s, S.D - 1);
+  // xyz_encoding_final into the colour branch's input, the density head (stacked under it in w9) into column 3 of rgb
+  NSR_TRY(fwd(st, q, split, kFinalE, hD.p, hD.ld, S.Wp, q.w9, S.Wp, q.b9, kActNone, s.ci, S.Ci, P, S.Wp, S.Wp));
+  NSR_TRY(fwd(st, q, split, kSigmaE, hD.p, hD.ld, S.Wp, q.w9 + (int64_t)S.Wp * S.Wp, S.Wp, q.b9 + S.Wp, kActNone, s.rgb + 3, 4, P, 32, 1));
+  NSR_TRY(fwd(st, q, split, kDirE, s.ci, S.Ci, S.Ci, q.wdir, S.Ci, q.bdir ? q.bdir : w[S.dir_w() + 1], kActRelu, s.cc, S.Hp, P, S.Hp, S.Hp));
+  NSR_TRY(fwd(st, q, split, kRgbE, s.cc, S.Hp, S.Hp, q.wrgb, S.Hp, q.brgb, color_none ? kActNone : kActSigmoid, s.rgb, 4, P, 32, 3));
+  return NSR_OK;
+}
+
+// backward of the network from k.d4 (composite_bwd's rows); g: its 2 D + 8 gradient tensors
+int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, const Work& k, int64_t P,
+                      float* const* g, int acc, int stop_grad) {
   const Kept& s = k.kept;
   const int sp = n_splits(P);
+  const int64_t ps = S.part_stride;
   float* part = k.partial;
+  const int ldg = S.Wp + 32;
+  hipLaunchKernelGGL(scatter_heads_kernel, dim3((unsigned)((P * 8 + 255) / 256)), dim3(256), 0, st,
+                     reinterpret_cast<const float4*>(k.d4), P, k.drgb, k.g1 + S.Wp, (int64_t)ldg);
+  NSR_CHECK_LAUNCH();
   // rgb head
-  NSR_TRY(lin_wgrad(st, k.drgb, kRgbPad, kRgbPad, s.cc, kDirOut, kDirOut, P, part, sp));
-  NSR_TRY(reduce_place(st, g[kRgbW], 128, 0, 3, 128, part, sp, kDirOut, 0, 0, acc));
-  NSR_TRY(colsum(st, k.drgb, kRgbPad, P, 0, 3, g[kRgbB], acc, part));
-  NSR_TRY(lin_dgrad(st, k, k.drgb, kRgbPad, kRgbPad, q.wrgbp, 128, s.cc, kDirOut, k.g0, kDirOut, P, kDirOut, g[kDirB], acc));
-  // dir_encoding
-  NSR_TRY(lin_wgrad(st, k.g0, kDirOut, kDirOut, s.gs, kGs, kGs, P, part, sp));
-  NSR_TRY(reduce_place(st, g[kDirW], 283, 0, 128, 256, part, sp, kGs, 0, 0, acc));
-  NSR_TRY(reduce_place(st, g[kDirW], 283, 256, 128, 27, part, sp, kGs, 0, kDeCol, acc));
-  // d g (its column sums are xyz_encoding_final's bias gradient); column 256 keeps d sigma
-  if (stop_grad) {   // --stop_grad (models/networks.py:218-219): dir_encoding's input is detached, d g = 0
-    if (hipMemset2DAsync(k.g1, (size_t)kGs * sizeof(float), 0, (size_t)kW * sizeof(float), (size_t)P, st) != hipSuccess) return NSR_ERR_LAUNCH;
-    if (!acc && hipMemsetAsync(g[kFinalB], 0, (size_t)kW * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
+  NSR_TRY(lin_wgrad(st, k.drgb, 32, 32, s.cc, S.Hp, S.Hp, P, part, sp, ps));
+  NSR_TRY(reduce_place(st, g[S.rgb_w()], S.H, 0, 3, S.H, part, sp, S.Hp, 0, 0, acc, 1.0f, ps));
+  NSR_TRY(colsum(st, k.drgb, 32, P, 0, 3, g[S.rgb_w() + 1], acc, part));
+  NSR_TRY(lin_dgrad(st, k.col_tiles, k.drgb, 32, 32, q.wrgb, S.Hp, s.cc, S.Hp, k.g0, S.Hp, P, S.Hp, g[S.dir_w() + 1], acc, S.H));
+  // dir_encoding: its input is [final | dir pe]
+  NSR_TRY(lin_wgrad(st, k.g0, S.Hp, S.Hp, s.ci, S.Ci, S.Ci, P, part, sp, ps));
+  NSR_TRY(reduce_place(st, g[S.dir_w()], S.dir_in(), 0, S.H, S.W, part, sp, S.Ci, 0, 0, acc, 1.0f, ps));
+  if (!S.no_dir) NSR_TRY(reduce_place(st, g[S.dir_w()], S.dir_in(), S.W, S.H, S.in_dir, part, sp, S.Ci, 0, S.Wp, acc, 1.0f, ps));
+  const int F = S.final_w();
+  if (stop_grad) {   // --stop_grad (models/networks.py:218-219): dir_encoding's input is detached, d final = 0
+    if (hipMemset2DAsync(k.g1, (size_t)ldg * sizeof(float), 0, (size_t)S.Wp * sizeof(float), (size_t)P, st) != hipSuccess) return NSR_ERR_LAUNCH;
+    if (!acc && hipMemsetAsync(g[F + 1], 0, (size_t)S.W * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
   } else {
-    NSR_TRY(lin_dgrad(st, k, k.g0, kDirOut, kDirOut, q.wdirp, 288, nullptr, 0, k.g1, kGs, P, kW, g[kFinalB], acc));
+    NSR_TRY(lin_dgrad(st, k.col_tiles, k.g0, S.Hp, S.Hp, q.wdir, S.Ci, nullptr, 0, k.g1, ldg, P, S.Wp, g[F + 1], acc, S.W));
   }
-  // xyz_encoding_final + sigma (288-row layer over h8)
-  NSR_TRY(lin_wgrad(st, k.g1, kGs, kW, s.h[8], kW, kW, P, part, sp));                 // rows 0..255: xyz_encoding_final
-  NSR_TRY(reduce_place(st, g[kFinalW], 256, 0, 256, 256, part, sp, kW, 0, 0, acc));
-  NSR_TRY(lin_wgrad(st, k.g1 + kSigmaCol, kGs, 32, s.h[8], kW, kW, P, part, sp));     // row 256 (+ 31 zero rows): sigma
-  NSR_TRY(reduce_place(st, g[kSigmaW], 256, 0, 1, 256, part, sp, kW, 0, 0, acc));
-  NSR_TRY(colsum(st, k.g1, kGs, P, 256, 1, g[kSigmaB], acc, part));
-  NSR_TRY(lin_dgrad(st, k, k.g1, kGs, kGs, q.w9p, 256, s.h[8], kW, k.g0, kW, P, kW, g[15], acc));   // + bias of layer 8
-  // xyz_encoding_8 .. 1; the gradient of layer L's pre-activation alternates between the two buffers
+  // xyz_encoding_final + sigma: the (Wp + 32)-row layer over the trunk's last activation
+  const Mat hD = out_of(S, s, S.D - 1);
+  NSR_TRY(lin_wgrad(st, k.g1, ldg, S.Wp, hD.p, hD.ld, S.Wp, P, part, sp, ps));
+  NSR_TRY(reduce_place(st, g[F], S.W, 0, S.W, S.W, part, sp, S.Wp, 0, 0, acc, 1.0f, ps));
+  NSR_TRY(lin_wgrad(st, k.g1 + S.Wp, ldg, 32, hD.p, hD.ld, S.Wp, P, part, sp, ps));
+  NSR_TRY(reduce_place(st, g[S.sigma_w()], S.W, 0, 1, S.W, part, sp, S.Wp, 0, 0, acc, 1.0f, ps));
+  NSR_TRY(colsum(st, k.g1, ldg, P, S.Wp, 1, g[S.sigma_w() + 1], acc, part));
+  NSR_TRY(lin_dgrad(st, k.col_tiles, k.g1, ldg, ldg, q.w9, S.Wp, hD.p, hD.ld, k.g0, S.Wp, P, S.Wp, g[2 * (S.D - 1) + 1], acc, S.W));
+  // trunk, top down; the gradient of a layer's pre-activation alternates between the two buffers
   const float* dy = k.g0;
   float* nx = k.g1;
-  for (int L = 8; L >= 1; --L) {
-    const float* xin = (L == 1 || L == 5) ? s.x5 : s.h[L - 1];
-    const int64_t ldx = (L == 1 || L == 5) ? kX5 : kW;
-    const int kin = (L == 1) ? kPe : (L == 5 ? kX5 : kW);
-    NSR_TRY(lin_wgrad(st, dy, kW, kW, xin, ldx, kin, P, part, sp));
-    float* gw = g[2 * (L - 1)];
-    if (L == 1) NSR_TRY(reduce_place(st, gw, 63, 0, 256, 63, part, sp, kPe, 0, 0, acc));
-    else if (L == 5) {
-      NSR_TRY(reduce_place(st, gw, 319, 0, 256, 63, part, sp, kX5, 0, 0, acc));
-      NSR_TRY(reduce_place(st, gw, 319, 63, 256, 256, part, sp, kX5, 0, kPe, acc));
-    } else NSR_TRY(reduce_place(st, gw, 256, 0, 256, 256, part, sp, kW, 0, 0, acc));
-    if (L == 1) break;
-    // input of layer L is the output of layer L - 1 (relu'd): h4 sits in x5[:, 64:]
-    const float* mask = (L - 1 == 4) ? s.x5 + kPe : s.h[L - 1];
-    const int64_t ldm = (L - 1 == 4) ? kX5 : kW;
-    // weights in the nn.Linear layout (out, in) ARE the K-major B operand of the input gradient
-    const float* wl = (L == 5) ? q.w5p + kPe : w[2 * (L - 1)];
-    const int ldw = (L == 5) ? kX5 : kW;
-    NSR_TRY(lin_dgrad(st, k, dy, kW, kW, wl, ldw, mask, ldm, nx, kW, P, kW, g[2 * (L - 2) + 1], acc));   // + bias of layer L - 1
+  for (int l = S.D - 1; l >= 0; --l) {
+    const Mat x = in_of(S, s, l);
+    const int kin = S.kin(l), fi = S.fan_in(l);
+    NSR_TRY(lin_wgrad(st, dy, S.Wp, S.Wp, x.p, x.ld, kin, P, part, sp, ps));
+    float* gw = g[2 * l];
+    if (S.skip(l)) {   // [pe | h] columns of the padded product -> the nn.Linear columns
+      NSR_TRY(reduce_place(st, gw, fi, 0, S.W, S.in_xyz, part, sp, kin, 0, 0, acc, 1.0f, ps));
+      NSR_TRY(reduce_place(st, gw, fi, S.in_xyz, S.W, S.W, part, sp, kin, 0, S.Kx, acc, 1.0f, ps));
+    } else {
+      NSR_TRY(reduce_place(st, gw, fi, 0, S.W, fi, part, sp, kin, 0, 0, acc, 1.0f, ps));
+    }
+    if (l == 0) break;
+    // the layer's input h is the ReLU output of layer l - 1: its mask, and that layer's bias gradient
+    const Mat m = out_of(S, s, l - 1);
+    const Lin a = trunk_lin(S, q, w, l);
+    NSR_TRY(lin_dgrad(st, k.col_tiles, dy, S.Wp, S.Wp, a.w + (S.skip(l) ? S.Kx : 0), a.ldw, m.p, m.ld, nx, S.Wp, P, S.Wp, g[2 * (l - 1) + 1],
+                      acc, S.W));
     const float* t0 = dy; dy = nx; nx = const_cast<float*>(t0);
   }
   return NSR_OK;
 }
+
+// a trunk layer without a padded copy is the GEMMs' operand where the caller holds it: 16-byte aligned (include/nsr_train.h)
+int nsr::check_alignment(const Shape& S, const float* const* w) {
+  for (int l = 1; l < S.D; ++l)
+    if (!S.skip(l) && S.W == S.Wp && (reinterpret_cast<uintptr_t>(w[2 * l]) & 15) != 0) return NSR_ERR_INVALID_ARG;
+  return NSR_OK;
+}
+

@@ -1,37 +1,23 @@
-// What the units of the training step share (internal; nsr_train.hip, nsr_train_gemm.hip, nsr_train_wgrad.hip): the padded
-// layer shapes, the workspace of a call (Work), its validated arguments (Run), the host functions that cross a unit boundary.
+// What the units of the training step share (internal; nsr_train.hip, nsr_train_gemm.hip, nsr_train_wgrad.hip): the shapes of
+// the layer-by-layer network (Shape), what a pass keeps (Kept), the workspace of a call (Work), its validated arguments (Run),
+// the host functions that cross a unit boundary.
 #pragma once
 #include <initializer_list>
 #include "nsr_common.h"
+#include "../../include/nsr_train.h"
 
 namespace nsr {
 
-constexpr int kW = 256, kPe = 64, kX5 = 320, kGs = 288, kDirOut = 128, kRgbPad = 32;
-constexpr int kSigmaCol = 256, kDeCol = 260;     // columns of the [g | sigma | 0 0 0 | de27 | 0] buffer
+constexpr int kW = 256, kPe = 64, kDirOut = 128;   // the default network's padded widths (the chain path is laid out for them)
 #ifndef NSR_MAX_SPLITS
 #define NSR_MAX_SPLITS 256   // one workgroup per CU.  Same box, 2,048-ray step: 128 -> 6.15 ms, 256 -> 5.30 ms, 512 -> 5.60 ms
 #endif
 constexpr int kMaxSplits = NSR_MAX_SPLITS;
-constexpr int64_t kPartialFloats = (int64_t)kGs * kX5;   // >= every padded weight-gradient shape
 constexpr int kChainSlots = 14, kChainRowSlots = 12;     // chain path: partial sums of a network's 14 weight-gradient
                                                         // products and of its bias row sums, all alive until ONE finishing launch
 
-// state_dict indices (nsr.h): layer i (1..8) weight = 2 (i - 1), bias = 2 (i - 1) + 1
+// state_dict indices of the default network (nsr.h): layer i (1..8) weight = 2 (i - 1), bias = 2 (i - 1) + 1
 constexpr int kFinalW = 16, kFinalB = 17, kDirW = 18, kDirB = 19, kSigmaW = 20, kSigmaB = 21, kRgbW = 22, kRgbB = 23;
-__host__ __device__ static constexpr int64_t tensor_numel(int t) {
-  switch (t) {
-    case 0: return 256 * 63;
-    case 8: return 256 * 319;
-    case kFinalW: return 256 * 256;
-    case kDirW: return 128 * 283;
-    case kDirB: return 128;
-    case kSigmaW: return 256;
-    case kSigmaB: return 1;
-    case kRgbW: return 3 * 128;
-    case kRgbB: return 3;
-    default: return (t & 1) ? 256 : 256 * 256;
-  }
-}
 
 static inline int64_t align64(int64_t n) { return (n + 63) & ~(int64_t)63; }   // floats -> 256-byte granules
 // split-K factor of the weight gradients: 2 row tiles x splits workgroups should cover the 256 CUs at least once
@@ -46,22 +32,65 @@ static inline int n_splits(int64_t P) {
     if (rc_ != NSR_OK) return rc_; \
   } while (0)
 
-// GEMM path: zero-padded copies of the weights whose shapes are not MFMA friendly (floats, one block)
-struct WeightPack {
-  float *w1p, *w5p, *w9p, *wdirp, *wrgbp, *b9p, *brgbp;
-  unsigned short* split;   // NSR_F16X3: (hi, lo) fp16 halves of the twelve forward weight matrices (kSplit* below)
+struct Carver {   // hands out consecutive 256-byte granules of `base` (null: only counts them)
+  float* base;
+  int64_t off = 0;
+  float* take(int64_t n, bool on = true) {
+    if (!on) return nullptr;
+    float* p = base ? base + off : nullptr;
+    off += align64(n);
+    return p;
+  }
 };
-// forward weight matrices in split-fp16 form: index, rows, K
-constexpr int kSplitRows[12] = {256, 256, 256, 256, 256, 256, 256, 256, 256, 32, 128, 32};
-constexpr int kSplitK[12] = {64, 256, 256, 256, 320, 256, 256, 256, 256, 256, 288, 128};
-static constexpr int64_t split_offset(int e) { return e == 0 ? 0 : split_offset(e - 1) + 2 * (int64_t)kSplitRows[e - 1] * kSplitK[e - 1]; }
-constexpr int64_t kSplitHalves = split_offset(11) + 2 * (int64_t)kSplitRows[11] * kSplitK[11];
+
+// ---- the layer-by-layer network (nsr_train_gemm.hip): everything is a function of the descriptor at run time -----------
+// Layout of a pass over P sample points, r32 = rounded up to 32 (the K tile of the GEMM kernels; padding columns hold zeros
+// and meet zero weight columns):
+//   Kx = r32(3 + 6 deg_pos), Wp = r32(W), Hp = r32(W / 2), Dp = r32(3 + 6 deg_dir) (0 under no_dir)
+//   x[j]  (P, Kx + Wp)   one per skip layer: [pe | h of the layer below]: cat([pe, h]) is the buffer itself; layer 0 reads
+//                        columns 0 .. Kx of x[0].  A network without skips has one (P, Kx) buffer.
+//   h[l]  (P, Wp)        output of trunk layer l, unless layer l + 1 is a skip layer (then it lies in that layer's x)
+//   ci    (P, Wp + Dp)   the colour branch's input [xyz_encoding_final | dir pe]
+//   cc    (P, Hp)        dir_encoding's output;  rgb (P, 4) = colours + raw sigma
+constexpr int kMaxD = NSR_ARCH_MAX_D, kMaxT = 2 * NSR_ARCH_MAX_D + 8;
+constexpr nsr_arch kDefaultArch = {8, 256, 1u << 4, 10, 4, 0};
+struct Shape {
+  int D, W, H, in_xyz, in_dir, Kx, Wp, Hp, Dp, Ci, Xs, ldx, n_x, no_dir;
+  unsigned skips;
+  int x_of[kMaxD];        // the x buffer that is layer l's input (layer 0 and skip layers), else -1
+  int64_t part_stride;    // floats of one split-K slice: >= every padded weight-gradient shape
+  nsr_arch arch;
+  bool skip(int l) const { return l > 0 && ((skips >> l) & 1u); }
+  int n_tensors() const { return 2 * D + 8; }
+  int kin(int l) const { return l == 0 ? Kx : (skip(l) ? Xs : Wp); }             // padded fan-in of trunk layer l
+  int fan_in(int l) const { return l == 0 ? in_xyz : (skip(l) ? in_xyz + W : W); }
+  int dir_in() const { return W + (no_dir ? 0 : in_dir); }
+  // indices into the state tensors
+  int final_w() const { return 2 * D; }
+  int dir_w() const { return 2 * D + 2; }
+  int sigma_w() const { return 2 * D + 4; }
+  int rgb_w() const { return 2 * D + 6; }
+};
+
+// Zero-padded copies of the weights whose shapes are not the GEMM's (one block, zeroed per call), and the (hi, lo) fp16
+// halves of the forward matrices.  A trunk layer whose shape needs no padding is read where the caller holds it.
+constexpr int kFinalE = kMaxD, kSigmaE = kMaxD + 1, kDirE = kMaxD + 2, kRgbE = kMaxD + 3, kNumE = kMaxD + 4;
+struct Pack {
+  float* first;
+  int64_t floats;
+  float* wl[kMaxD];
+  float* bl[kMaxD];
+  float *w9, *b9, *wdir, *bdir, *wrgb, *brgb;
+  unsigned short* hi[kNumE];
+};
 
 // What the forward half of a pass over P sample points leaves for its backward half (all row-major).  The fused step keeps
-// it in the workspace; nsr_train_forward keeps one per pass in the caller's `saved` buffer (nsr_train.hip, kept_floats).
+// it in the workspace; nsr_train_forward keeps one per pass in the caller's `saved` buffer (nsr_train.hip, carve_kept).
 struct Kept {
-  float *x5, *h[9], *gs, *cc;   // GEMM path: [pe64 | h4], h1..h8 (h[0], h[4] unused), [g | sigma | de], dir_encoding's output
-  float *rgb, *sig, *z;         // both paths: (P, 4) colours (+ raw sigma on the chain path), noisy sigma, sample depths
+  float* x[kMaxD];              // layer-by-layer network: the layout above
+  float* h[kMaxD];              //   null: the layer's output lies in the x buffer of the skip layer above it
+  float *ci, *cc;
+  float *rgb, *sig, *z;         // both paths: (P, 4) colours + raw sigma, noisy sigma, sample depths
   char* zpan;                   // chain path: activation panels of the forward pass (2 bytes per value, nsr_f16x3_core.h)
   unsigned* sgn;                //             and its sign panels
 };
@@ -69,13 +98,15 @@ struct Kept {
 struct Work {   // the workspace of a call, sized for P_max = chunk * (Nc + Ni) sample points
   unsigned* status; // sticky NSR_FLAG_* word of the training step (include/nsr_train.h): ALWAYS the first bytes of the workspace
   Kept kept;        // of the pass at hand (sized for a fine pass; kept.z is the fine pass's z)
-  float *g0, *g1, *drgb, *col_tiles;
-  float* d4;        // chain path: (P, 4) = d(rgb_pre) 0..2, d(sigma) of every sample point (composite_bwd_kernel COMPACT)
+  float* d4;        // (P, 4) = d(rgb_pre) 0..2, d(sigma) of every sample point (composite_bwd)
+  // layer-by-layer network: the two alternating gradient matrices (P, Wp + 32), [d rgb_pre | 0] (P, 32), per-tile column sums
+  // of a dgrad product, split-K slices of a weight gradient, the padded weights of both networks
+  float *g0, *g1, *drgb, *col_tiles, *partial;
+  Pack pack[2];
   float* bias_part; // chain path: (rays, 4) per-ray sums of d4: the bias gradients of the colour and density heads before their finish
-  float *z_c, *w_c, *comp, *g_comp, *partial, *scratch_out;
+  float *z_c, *w_c, *g_comp, *scratch_out;
   double *block_sums, *carry;
   float* g_depth;   // per ray: d(loss) / d(depth) of the depth-variance loss (zeros when it is off)
-  WeightPack pack[2];
   // chain path: gradient panels of the backward chain, the two weight streams per network, per-slice row sums and partial
   // tiles of the weight-gradient products
   char* dpan;
@@ -89,7 +120,8 @@ struct Run {   // the validated arguments of one call
   int64_t R, chunk;
   int nc, ni, flags, precision, lindisp, ray_stride;
   float noise_std;
-  bool chain;
+  bool chain;   // which implementation the precision selects: the chain kernels, or the layer-by-layer network `net`
+  Shape net;
 };
 
 // one element of torch.optim.Adam: torch/optim/adam.py (_single_tensor_adam) operation order, fp32
@@ -103,17 +135,6 @@ __device__ __forceinline__ void adam_update(const float* gp, float* mp, float* v
   const float denom = __fadd_rn(__fdiv_rn(sqrtf(v), bc2_sqrt), eps);
   wp[i] = __fsub_rn(wp[i], __fmul_rn(step_size, __fdiv_rn(m, denom)));
 }
-
-struct Carver {   // hands out consecutive 256-byte granules of `base` (null: only counts them)
-  float* base;
-  int64_t off = 0;
-  float* take(int64_t n, bool on = true) {
-    if (!on) return nullptr;
-    float* p = base ? base + off : nullptr;
-    off += align64(n);
-    return p;
-  }
-};
 
 // ---- the passes of a call ----------------------------------------------------------------------------------------------
 struct Pass {
@@ -144,44 +165,26 @@ struct Need {   // the pointers a driver requires of its caller
   std::initializer_list<const void*> with_rays;       // when there are rays
   std::initializer_list<const void*> aligned;         // on 256 bytes
   int n_state = 24;                                   // NSR_N_STATE_TENSORS, or 2 D + 8 of an architecture descriptor
-  bool gemm_only = false;                             // the chain precisions are NSR_ERR_UNSUPPORTED (nsr_train_arch.hip)
+  bool gemm_only = false;                             // the chain precisions are NSR_ERR_UNSUPPORTED (nsr_train_arch_*)
 };
 
-// ---- nsr_train.hip: what its drivers share with those of nsr_train_arch.hip
-NSR_INTERNAL int check_shape(int64_t R, int s2, int n_coarse, int n_importance, int precision, int64_t& ray_chunk, bool gemm_only = false);
-NSR_INTERNAL int check_flags(int flags);
-NSR_INTERNAL int check_args(const Need& need, Run* c, int s2);
-NSR_INTERNAL int pass_sample(const Run& c, const Pass& q, const float* rays, const float* u, const float* z_c, const float* w_c, float* z,
-                             void* stream);
-NSR_INTERNAL int pass_finish(hipStream_t st, const Run& c, const Pass& q, const float* sigma_raw, int sigma_stride, const float* noise,
-                             float* rgb4, float* sig, const float* z, float* comp, float* depth, float* opac, float* wts, void* stream);
-// reads k.kept.rgb / k.kept.sig; compact: (P, 4) rows into k.d4 (k.gmax, k.bias_part may be null), else k.drgb / k.g1
-NSR_INTERNAL int composite_bwd(hipStream_t st, const Work& k, const float* z, const float* g_comp, int64_t R, int N, int white, bool compact,
-                               const float* g_depth, const float* g_opacity, const float* g_weights);
-
-// ---- nsr_train_gemm.hip: the layer-by-layer path.  precision: NSR_FP32 or NSR_F16X3 (split-fp16 forward products)
-NSR_INTERNAL int prepare_weights(hipStream_t st, const float* const* w, const WeightPack& q, int precision);
-// E1 + cast_rays of the P = rays x N sample points into s.x5 / s.gs, then M1 forward with everything kept for the backward pass
-NSR_INTERNAL int net_forward(hipStream_t st, const float* rays, int ray_stride, const float* z, int N, const float* const* w,
-                             const WeightPack& q, const Kept& s, int64_t P, int precision, int color_none);
-// backward of M1: d_rgb_pre in k.drgb (P, 32), d_sigma in column 256 of k.g1 (P, 288)
-NSR_INTERNAL int net_backward(hipStream_t st, const float* const* w, const WeightPack& q, const Work& k, int64_t P, float* const* g,
-                              int acc, int stop_grad);
-// the host wrappers of its kernels (one linear layer's three products, the deterministic reductions behind them)
-NSR_INTERNAL int place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* src, int src_ld, int rows, int cols,
-                       int col0, int transpose);
-NSR_INTERNAL int lin_fwd_at(hipStream_t st, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
-                            float* y, int64_t ldy, int64_t P, int N, int n_valid, const unsigned short* hi, const unsigned short* lo,
-                            int ldh);
-NSR_INTERNAL int lin_dgrad(hipStream_t st, const Work& k, const float* dy, int64_t lddy, int K, const float* w, int ldw,
-                           const float* mask, int64_t ldm, float* dx, int64_t lddx, int64_t P, int N, float* bias_grad, int acc,
-                           int n_bias = 0);
-NSR_INTERNAL int lin_wgrad(hipStream_t st, const float* dy, int64_t lddy, int M, const float* x, int64_t ldx, int N, int64_t P,
-                           float* partial, int splits, int64_t stride = kPartialFloats);
-NSR_INTERNAL int reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows, int cols, const float* partial, int splits,
-                              int p_ld, int pr0, int pc0, int accumulate, float scale = 1.0f, int64_t stride = kPartialFloats);
-NSR_INTERNAL int colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, float* dst, int accumulate,
-                        float* scratch);
+// ---- nsr_train_gemm.hip: the layer-by-layer network
+// malformed descriptor -> NSR_ERR_INVALID_ARG, beyond the stated limits -> NSR_ERR_UNSUPPORTED (include/nsr_train.h)
+NSR_INTERNAL int make_shape(const nsr_arch* a, Shape& S);
+NSR_INTERNAL int64_t tensor_numel_of(const Shape& S, int t);
+NSR_INTERNAL void carve_net_kept(Carver& a, const Shape& S, int64_t P, Kept& q);   // x, h, ci, cc
+NSR_INTERNAL Pack carve_pack(Carver& a, const Shape& S, bool split);
+// a trunk layer without a padded copy is the GEMMs' operand where the caller holds it: 16-byte aligned, else NSR_ERR_INVALID_ARG
+NSR_INTERNAL int check_alignment(const Shape& S, const float* const* w);
+// split: also the (hi, lo) fp16 halves of the forward matrices (NSR_F16X3_GEMM; the pack must have been carved with them)
+NSR_INTERNAL int prepare_weights(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, bool split);
+// E1 + cast_rays of the P = rays x N sample points, then the network with everything kept for the backward pass; the raw
+// density goes to column 3 of s.rgb.  split: the forward products on the pack's split-fp16 halves
+NSR_INTERNAL int net_forward(hipStream_t st, const Shape& S, const float* rays, int ray_stride, const float* z, int N,
+                             const float* const* w, const Pack& q, const Kept& s, int64_t P, bool split, int color_none);
+// backward of the network from k.d4 (composite_bwd's rows); g: its 2 D + 8 gradient tensors
+NSR_INTERNAL int net_backward(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, const Work& k, int64_t P,
+                              float* const* g, int acc, int stop_grad);
 // ---- nsr_train_wgrad.hip: weight and bias gradients of the chain path from the panels
 NSR_INTERNAL int chain_weight_grads(hipStream_t st, const Work& k, int64_t P, int64_t n_rays, float* const* g, int acc);
 

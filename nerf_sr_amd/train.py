@@ -299,8 +299,6 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
         raise ValueError("forward_rays_train: rays must not require grad (there is no gradient with respect to rays)")
     if arch is not None:      # everything about the architecture is checked before a device is touched
         arch = normalize_arch(arch)
-        if sigma_activation not in ("relu", "softplus") or color_activation not in ("sigmoid", "none"):
-            raise ValueError("sigma_activation: 'relu' or 'softplus'; color_activation: 'sigmoid' or 'none'")
         if gamma_correct and color_activation == "none":
             raise ValueError("gamma_correct with color_activation='none': pow(rgb, 1 / 2.2) of an unbounded head is NaN for every negative value")
         precision = arch_precision(arch, precision)
