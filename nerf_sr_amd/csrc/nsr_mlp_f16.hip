@@ -454,6 +454,36 @@ extern "C" int nsr_dbg_timeline(void* host_dst, size_t bytes) {
 #define NSR_TL(k) ((void)0)
 #endif
 
+// COMP: the encoded view direction of a wave's ray (16 operand columns of this lane's half h, nsr_mlp_layout.h) and its
+// split into the operand registers of dir_encoding's last two k-steps: statement for statement what the kernel's prologue
+// does per tile (the other instantiations keep that text: routed through these helpers their register allocation, and
+// with it their whole ISA, moves away from the measured builds)
+__device__ __forceinline__ void encode_direction(const float (&d)[3], int h, float (&de)[16]) {
+  de[0] = h ? d[2] : d[0];
+  de[1] = h ? 0.0f : d[1];
+#pragma unroll
+  for (int f = 0; f < 2; ++f)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float sn, cs;
+      nsr_sincos(ldexpf(d[c], 2 * h + f), sn, cs);
+      de[2 + 6 * f + c] = sn;
+      de[2 + 6 * f + 3 + c] = cs;
+    }
+  de[14] = 0.0f;
+  de[15] = 0.0f;
+}
+__device__ __forceinline__ void split_direction(const float (&de)[16], u32x4 (&deh)[2], u32x4 (&del)[2]) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    unsigned a[4], b[4];
+#pragma unroll
+    for (int pr = 0; pr < 4; ++pr) split2(de[8 * s + 2 * pr], de[8 * s + 2 * pr + 1], a[pr], b[pr]);
+    deh[s] = u32x4{a[0], a[1], a[2], a[3]};
+    del[s] = u32x4{b[0], b[1], b[2], b[3]};
+  }
+}
+
 // COMP: the tile's points are whole rays (MODE 1, NS = 64 or 128) and the kernel composites them itself (V1 fused into
 // D2 + M1: the (R, N, 4) network output never goes to HBM); `out` may then be null.
 // TRAIN: the forward pass of the training step (nsr_train.hip): additionally keeps every layer's pre-activations for the
@@ -543,17 +573,40 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   const int64_t my_ray_c = my_ray < n_rays ? my_ray : n_rays - 1;
   float res[kWindows][4];                                              // COMP: (r, g, b, sigma) of the finished windows (h == 0 lanes)
   u32x4 bh[16], bl[16], oh[16], ol[16];
+  // COMP: what depends on the ray alone is done once per ray, not once per window: the ray fetch, the range check of the
+  // encoded direction and its encoding, split into deh / del (which live through the trunk anyway).  (Fetching a window's
+  // depths one window ahead, behind the density block, and a vote barrier without __syncthreads()'s vmcnt(0) were built on
+  // top and measured no gain: profiles/window_loop_ab.json.)
+  NsrRay ray_q{};
+  if (COMP) {
+    ray_q = nsr_load_ray(x, my_ray_c, stride);
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ok = ok && fabsf(ray_q.v[c]) <= 65504.0f;
+    if (!ok) flags |= NSR_FLAG_INPUT_RANGE;
+    float de[16];
+    encode_direction(ray_q.v, h, de);
+    split_direction(de, deh, del);
+  }
 #pragma unroll 1
   for (int win = 0; win < kWindows; ++win) {
   NSR_TL(0);
-  const int64_t p = COMP ? (my_ray < n_rays ? my_ray * NS + win * 32 + m : P) : tile * 128 + wave * 32 + m;
+  // COMP: the wave index is made opaque once per window.  Every chunk's DMA descriptor is a function of it; left
+  // transparent, they are all hoisted out of the window loop and parked in VGPR lanes, and the v_readlane that fetch them
+  // back (with the s_nop of their hazards) land in the MFMA gaps of every chunk.
+  int wv = wave;
+  if (COMP) {
+    asm volatile("" : "+s"(wv));
+    ld.wave = wv;
+  }
+  const int64_t p = COMP ? (my_ray < n_rays ? my_ray * NS + win * 32 + m : P) : tile * 128 + wv * 32 + m;
   const int64_t pc = COMP ? my_ray_c * NS + win * 32 + m : (p < P ? p : P - 1);
   if (COMP && threadIdx.x == 0) *vote = 0u;                            // published by the barrier below
   PanelRef tr{};
   if (TRAIN) {
     tr.base = reinterpret_cast<char*>(pan);
     tr.n_groups = n_tiles * 4;
-    tr.group = tile * 4 + wave;
+    tr.group = tile * 4 + wv;
     tr.sgn = sgn;
   }
   float amax = 0.0f;       // see resplit_a
@@ -578,7 +631,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     if (!ok) flags |= NSR_FLAG_INPUT_RANGE;
   } else {
     const int64_t ray = pc / ((NS > 0) ? NS : N);
-    const NsrRay rq = nsr_load_ray(x, ray, stride);
+    const NsrRay rq = COMP ? ray_q : nsr_load_ray(x, ray, stride);
     const float zk = zv[pc];
     const float d[3] = {rq.v[0], rq.v[1], rq.v[2]};           // the direction that is ENCODED
     const float v[3] = {__fadd_rn(rq.o[0], __fmul_rn(zk, rq.d[0])), __fadd_rn(rq.o[1], __fmul_rn(zk, rq.d[1])),
@@ -586,7 +639,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     // the raw coordinates are operands too (columns 0..2 of both encodings): fp16's range, and false for NaN
     bool ok = true;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) ok = ok && fabsf(v[c]) <= 65504.0f && fabsf(d[c]) <= 65504.0f;
+    for (int c = 0; c < 3; ++c) ok = ok && fabsf(v[c]) <= 65504.0f && (COMP || fabsf(d[c]) <= 65504.0f);
     if (!ok) flags |= NSR_FLAG_INPUT_RANGE;
     pe[0] = h ? v[2] : v[0];
     pe[1] = h ? 0.0f : v[1];
@@ -599,6 +652,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
         pe[2 + 6 * f + c] = sn;
         pe[2 + 6 * f + 3 + c] = cs;
       }
+    if (!COMP) {    // COMP: deh / del were made before the window loop
     de[0] = h ? d[2] : d[0];
     de[1] = h ? 0.0f : d[1];
 #pragma unroll
@@ -612,6 +666,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
       }
     de[14] = 0.0f;
     de[15] = 0.0f;
+    }
   }
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
@@ -621,6 +676,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     peh[s] = u32x4{a[0], a[1], a[2], a[3]};
     pel[s] = u32x4{b[0], b[1], b[2], b[3]};
   }
+  if (!COMP) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     unsigned a[4], b[4];
@@ -629,7 +685,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     deh[s] = u32x4{a[0], a[1], a[2], a[3]};
     del[s] = u32x4{b[0], b[1], b[2], b[3]};
   }
-
+  }
 
   if (TRAIN) {   // the encodings themselves (their hi halves): operands of the weight gradients of L1, L5 (skip part) and
                  // dir_encoding; the direction panel's second 32 rows are zeros (the narrowest weight-gradient tile is 64)
@@ -674,7 +730,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   for (int c = 0; c < 2; ++c) {
     // c == 0: publishes chunk 1 (issued before the encoding); chunk 0 was published by the drain and barrier above, and its
     // head is already in `l1pre`
-    loader_publish(ld, layer_ref(1, c, wave));    // chunk j+2 = first / second chunk of L2
+    loader_publish(ld, layer_ref(1, c, wv));    // chunk j+2 = first / second chunk of L2
     const unsigned a_chunk = ld.slot_cur + ld.lane_off;
     const unsigned next_bias = 32u * 1024u;       // L1 chunk 1 and L2's chunks: 32 weight pieces, then the bias
 #pragma unroll
@@ -686,7 +742,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
       cur.m = l1pre.bias;
       Resplit ptmp;
       block_mma3<4, -1>(
-          cur, l1pre, a_addr, ld, first_ref(0, wave), [&](int s, int part) -> u32x4 { return part ? pel[s] : peh[s]; },
+          cur, l1pre, a_addr, ld, first_ref(0, wv), [&](int s, int part) -> u32x4 { return part ? pel[s] : peh[s]; },
           [&](int s, int gp) {
             const int i = 4 * g + s;        // DMA of chunk j+2: one piece per k-step over the chunk's 16 k-steps
             if (gp == 0 && i < 11) loader_issue(ld, i);
@@ -731,22 +787,22 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
 #pragma unroll 1
   for (int pair = 0; pair < 3; ++pair) {
     const int L = 1 + 2 * pair;
-    trunk_layer<true, TRAIN>(L, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(L + 1, 0, wave), layer_ref(L + 1, 1, wave), amax, sbits, tr, voff0, voff1);
-    trunk_layer<true, TRAIN>(L + 1, oh, ol, bh, bl, stash, ld, h, pend, pre, layer_ref(L + 2, 0, wave), layer_ref(L + 2, 1, wave), amax,
+    trunk_layer<true, TRAIN>(L, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(L + 1, 0, wv), layer_ref(L + 1, 1, wv), amax, sbits, tr, voff0, voff1);
+    trunk_layer<true, TRAIN>(L + 1, oh, ol, bh, bl, stash, ld, h, pend, pre, layer_ref(L + 2, 0, wv), layer_ref(L + 2, 1, wv), amax,
                              sbits, tr, voff0, voff1);
   }
   if (SIGMA_ONLY) {   // xyz_encoding_final is not evaluated: L8 is followed by the density head, then nothing
-    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wave), first_ref(0, wave), amax, sbits);
+    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), first_ref(0, wv), amax, sbits);
   } else if (COMP) {  // the density head comes next (SIGMA_ONLY's sequence), xyz_encoding_final after it
-    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wave), layer_ref(8, 0, wave), amax, sbits);
+    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), layer_ref(8, 0, wv), amax, sbits);
   } else {
 #ifdef NSR_ABL_TIMELINE
-    trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wave), layer_ref(8, 1, wave), amax, sbits, tr, voff0, voff1, tk);
+    trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wv), layer_ref(8, 1, wv), amax, sbits, tr, voff0, voff1, tk);
     ld.tk = nullptr;
 #else
-    trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wave), layer_ref(8, 1, wave), amax, sbits, tr, voff0, voff1);
+    trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wv), layer_ref(8, 1, wv), amax, sbits, tr, voff0, voff1);
 #endif
-    trunk_layer<false, TRAIN>(8, oh, ol, bh, bl, stash, ld, h, pend, pre, sigma_ref(wave), dir_ref(0, wave), amax, sbits, tr, voff0, voff1);
+    trunk_layer<false, TRAIN>(8, oh, ol, bh, bl, stash, ld, h, pend, pre, sigma_ref(wv), dir_ref(0, wv), amax, sbits, tr, voff0, voff1);
   }
 
   NSR_TL(3);
@@ -766,7 +822,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     constexpr bool kDensityMma = true;
 #endif
     block_mma3<16, kBar, (TRAIN ? kTrainYoung : 0), true, kDensityMma>(
-        cur, pre, ld.slot_cur + ld.lane_off, ld, SIGMA_ONLY ? first_ref(1, wave) : (COMP ? layer_ref(8, 1, wave) : dir_ref(1, wave)),
+        cur, pre, ld.slot_cur + ld.lane_off, ld, SIGMA_ONLY ? first_ref(1, wv) : (COMP ? layer_ref(8, 1, wv) : dir_ref(1, wv)),
         [&](int s, int part) -> u32x4 { return part ? ol[s] : oh[s]; },
         [&](int s, int g) {
           if (SIGMA_ONLY || COMP)
@@ -812,10 +868,10 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
       dma_drain();
       __syncthreads();          // every wave's DMA has landed and nobody reads the ring
       if (win + 1 < kWindows) {
-        loader_prepare_dma(ld, first_ref(0, wave), ld.slot_cur);
+        loader_prepare_dma(ld, first_ref(0, wv), ld.slot_cur);
 #pragma unroll
         for (int i = 0; i < 11; ++i) loader_issue(ld, i);
-        loader_prepare_dma(ld, first_ref(1, wave), ld.slot_next);
+        loader_prepare_dma(ld, first_ref(1, wv), ld.slot_next);
 #pragma unroll
         for (int i = 0; i < 11; ++i) loader_issue(ld, i);
       }
@@ -823,7 +879,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     }
   }
   if (colour) {
-  if (COMP) trunk_layer<false, false, false>(8, oh, ol, bh, bl, stash, ld, h, pend, pre, dir_ref(0, wave), dir_ref(1, wave), amax, sbits);
+  if (COMP) trunk_layer<false, false, false>(8, oh, ol, bh, bl, stash, ld, h, pend, pre, dir_ref(0, wv), dir_ref(1, wv), amax, sbits);
 
   NSR_TL(4);
   // ---- dir_encoding (cat([g, de]) -> 128, relu) fused with the rgb head (128 -> 3, sigmoid)
@@ -838,7 +894,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     // in flight behind the previous block's DMA: the density block's 2 stores | nothing | a dir block's 2 + sign word
     const unsigned a_seq = ld.slot_cur + ld.lane_off;
     // (blocks 2 and 3 fetch nothing, except COMP: the next window's L1 chunks; dead traffic after the last window)
-    const ChunkRef c2 = nb < 2 ? dir_ref(nb + 2, wave) : first_ref(nb - 2, wave);
+    const ChunkRef c2 = nb < 2 ? dir_ref(nb + 2, wv) : first_ref(nb - 2, wv);
     Resplit ptmp;
     auto b_of = [&](int s, int part) -> u32x4 {
       return (s < 16) ? (part ? bl[s & 15] : bh[s & 15]) : (part ? del[s & 1] : deh[s & 1]);
