@@ -1,10 +1,11 @@
-"""Host-side mirror of ``NeRFDownXModel`` for the render path only.
+"""Host-side mirror of ``NeRFDownXModel`` for the render path and its scoring.
 
 Reproduces the call protocol the reference's loops use
 (``set_input -> forward -> out_* -> comp_low_res_output``; train.py:79-80,
 test.py:52, models/nerf_downX_model.py:235-353,410-416,621-669) on top of the HIP
-path.  Losses, optimisers, checkpoints, visualisers and the GAN / refinement
-branches are out of scope.
+path, and the eval-side ``calculate_losses`` / ``validate`` (:355-388, :469-516) over
+``nerf_sr_amd.metrics``.  Training losses and optimisers live in ``nerf_sr_amd.train``;
+checkpoints, visualisers and the GAN branches are out of scope.
 """
 from __future__ import annotations
 
@@ -144,6 +145,86 @@ class NeRFDownXModel:
 
     def unflatten_reshape(self, input: torch.Tensor) -> torch.Tensor:
         return ops.unflatten_reshape(input, self.opt.img_wh, self.opt.downscale)
+
+    # -- scoring (nerf_downX_model.py:355-388, the eval-side half; :469-516) ---------------
+    @torch.no_grad()
+    def calculate_losses(self):
+        """``comp_low_res_output()``, then the MSE losses and the PSNRs of the LR means against ``data_rgbs`` and, when
+        ``data_rgbs_ori`` is set, of the rendered rays against it -- each a 0-d fp32 device tensor out of ``nsr_psnr`` (sums in
+        double, no host read).  Like the reference's, it reduces the ``out_*`` of ONE ``forward()``: call it once per forward."""
+        from . import metrics
+        self.comp_low_res_output()
+        fine = hasattr(self, "out_fine_comp_rgbs")
+        mse_c, psnr_c = metrics.mse_psnr(self.out_coarse_comp_rgbs, self.data_rgbs)
+        self.loss_coarse_mse = (mse_c * float(getattr(self.opt, "lambda_coarse_mse", 1))).float()
+        self.loss_coarse_psnr = psnr_c.float()
+        if fine:
+            mse_f, psnr_f = metrics.mse_psnr(self.out_fine_comp_rgbs, self.data_rgbs)
+            self.loss_fine_mse = (mse_f * float(getattr(self.opt, "lambda_fine_mse", 1))).float()
+            self.loss_fine_psnr = psnr_f.float()
+        else:
+            self.loss_fine_mse, self.loss_fine_psnr = 0, 0
+        self.loss_tot = self.loss_coarse_mse + self.loss_fine_mse
+        if hasattr(self, "data_rgbs_ori"):
+            self.loss_coarse_psnr_ori = metrics.mse_psnr(self.out_coarse_comp_rgbs_ori, self.data_rgbs_ori)[1].float()
+            if fine:
+                self.loss_fine_psnr_ori = metrics.mse_psnr(self.out_fine_comp_rgbs_ori, self.data_rgbs_ori)[1].float()
+
+    @torch.no_grad()
+    def calculate_ssim(self):
+        """This build's addition (the reference lists SSIM as a to-do, nerf_downX_model.py:103): ``loss_fine_ssim`` of the LR
+        image against ``data_rgbs`` and ``loss_fine_ssim_ori`` of the HR image against ``data_rgbs_ori``, (H, W, 3) frames
+        read in place (layout BHWC), data_range (0, 1).  Needs ``opt.img_wh`` to be the frame the rays cover; returns False
+        (and sets nothing) when it is not, or when there is no fine pass."""
+        from . import metrics
+        W, H = int(self.opt.img_wh[0]), int(self.opt.img_wh[1])
+        s = int(self.opt.downscale)
+        H1, W1 = H // s, W // s
+        if not hasattr(self, "out_fine_comp_rgbs_ori") or not hasattr(self, "data_rgbs") or self.data_rgbs.shape[0] != H1 * W1 \
+                or self.out_fine_comp_rgbs_ori.shape[0] != H1 * W1 * s * s:
+            return False
+        if not hasattr(self, "_ssim"):
+            self._ssim = metrics.SSIM(data_range=(0, 1))
+        self.loss_fine_ssim = self._ssim(self.out_fine_comp_rgbs.reshape(1, H1, W1, 3), self.data_rgbs.reshape(1, H1, W1, 3), layout="BHWC")
+        if hasattr(self, "data_rgbs_ori"):
+            self.loss_fine_ssim_ori = self._ssim(self.unflatten_reshape(self.out_fine_comp_rgbs_ori).unsqueeze(0),
+                                                 self.unflatten_reshape(self.data_rgbs_ori).unsqueeze(0), layout="BHWC")
+        return True
+
+    @torch.no_grad()
+    def validate(self, dataset) -> Dict[str, float]:
+        """The reference's validation loop without its savers: for every dict of ``dataset`` ``set_input`` -> ``forward`` ->
+        ``calculate_losses`` (-> ``calculate_ssim``) in eval mode, the scores averaged over the dataset.  They are accumulated on the
+        device and read ONCE at the end (the reference: four ``.item()`` per image); the ``loss_*`` attributes end up as
+        Python floats, as there, and are returned by name."""
+        names = ["loss_coarse_psnr", "loss_fine_psnr", "loss_coarse_psnr_ori", "loss_fine_psnr_ori", "loss_fine_ssim",
+                 "loss_fine_ssim_ori"]
+        for k in names[2:]:
+            if hasattr(self, k):
+                delattr(self, k)
+        was, self.randomized = self.randomized, False
+        sums, n = {}, 0
+        try:
+            for data in dataset:
+                self.set_input(data)
+                self.forward()
+                self.calculate_losses()
+                self.calculate_ssim()
+                for k in names:
+                    v = getattr(self, k, None)
+                    if isinstance(v, torch.Tensor):
+                        sums[k] = v.double() if k not in sums else sums[k] + v.double()
+                n += 1
+        finally:
+            self.randomized = was
+        if n == 0:
+            raise ValueError("validate: the dataset is empty")
+        keys = list(sums)
+        means = (torch.stack([sums[k] for k in keys]) / n).tolist() if keys else []       # the one host read
+        res = dict(zip(keys, means))
+        for k, v in res.items():
+            setattr(self, k, v)
+        return res
 
     # -- full image (test loop body, nerf_downX_model.py:621-669 without the savers) -----
     @torch.no_grad()

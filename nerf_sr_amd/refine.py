@@ -234,6 +234,24 @@ def refine_image(net: MaxPoolingModel, sr_img: torch.Tensor, ref_img: torch.Tens
     return stitch_patches(pred, starts, (sr_img.shape[2], sr_img.shape[1]))
 
 
+def evaluate_image(net: MaxPoolingModel, sr_img: torch.Tensor, ref_img: torch.Tensor, locs: torch.Tensor, gt_img: torch.Tensor,
+                   patch_len: int = 64, num_ref_patches: int = 8, batch: int = 256) -> Dict[str, torch.Tensor]:
+    """``refine_image``, then the scores of ``RefineModel.test`` / ``validate`` (models/refine_model.py:225-226): the SSIM of
+    the SR frame and of the refined frame against ``gt_img`` on the (1, 3, H, W) frames with ``data_range=(-1, 1)``, and a
+    PSNR beside each.  Returns ``refined`` (3, H, W) and ``psnr_input``, ``psnr_refine``, ``ssim_input``, ``ssim_refine`` as
+    0-d device tensors (no host read here)."""
+    from . import metrics
+    gt = _f32(gt_img, "gt_img")
+    if tuple(gt.shape) != tuple(sr_img.shape):
+        raise ValueError(f"gt_img must have the SR image's shape {tuple(sr_img.shape)}, got {tuple(gt.shape)}")
+    refined = refine_image(net, sr_img, ref_img, locs, patch_len, num_ref_patches, batch)
+    sr = _f32(sr_img, "sr_img")
+    ssim, psnr = metrics.SSIM(data_range=(-1, 1)), metrics.PSNR()
+    return {"refined": refined,
+            "psnr_input": psnr(sr, gt), "psnr_refine": psnr(refined, gt),
+            "ssim_input": ssim(sr.unsqueeze(0), gt.unsqueeze(0)), "ssim_refine": ssim(refined.unsqueeze(0), gt.unsqueeze(0))}
+
+
 # ------------------------------------------------------------------------------------------------------- training
 _TRAIN_WS: Dict[torch.device, torch.Tensor] = {}     # scratch of the train-mode pair, one per device (grows, never shrinks)
 
