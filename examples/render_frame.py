@@ -32,13 +32,16 @@ def main():
     ap.add_argument("--pose-t", type=float, default=0.4, help="position on the LLFF spiral path")
     ap.add_argument("--precision", default="f16x3")
     ap.add_argument("--out", default="frame")
+    ap.add_argument("--early-stop", type=float, default=0.0,
+                    help="early ray termination at this transmittance (precision f16x3; colours move by at most eps + 2e-6; 0 = off)")
     a = ap.parse_args()
     if a.checkpoint_dir:
         pc, pf = io.checkpoint_paths(a.checkpoint_dir, a.name, a.epoch)
         sd_c, sd_f = io.load_network_state(pc), io.load_network_state(pf)
     else:
         sd_c, sd_f = make_state_dict(99), make_state_dict(100)
-    opt = default_options(img_wh=tuple(a.wh), downscale=a.downscale, white_bkgd=False, precision=a.precision)
+    opt = default_options(img_wh=tuple(a.wh), downscale=a.downscale, white_bkgd=False, precision=a.precision,
+                          early_stop=a.early_stop)
     model = NeRFDownXModel(opt, device="cuda").load_networks(sd_c, sd_f).eval()
     res = model.render_image(cameras.spiral_pose(a.pose_t), cameras.llff_focal(a.wh[0]), ndc=True)
     torch.cuda.synchronize()

@@ -190,6 +190,46 @@ int nsr_render_rays_composited(const void* packed_dev, int precision, const floa
                                int64_t R, int n_samples, int render_flags, float* raw, float* comp_rgb, float* depth,
                                float* opacity, float* weights, void* stream);
 
+/* ---- early ray termination (opt-in) ---------------------------------------------------
+ * Every NeRF renderer stops a ray once its transmittance is spent; the two entry points below do that for the NSR_F16X3
+ * launch of nsr_render_rays_composited, which walks each group of 4 consecutive rays through its n_samples / 32 depth
+ * windows front to back.  `early_stop` = eps is a transmittance threshold, 0 <= eps < 1; 0 = off: the call forwards to the
+ * entry point without the option (same launch, same bits).
+ *   Scope.          Only the LAST network pass of nsr_forward_rays_ert is cut: the fine pass, or the coarse pass when
+ *                   n_importance == 0; and a direct nsr_render_rays_composited_ert launch.  The coarse pass that feeds the
+ *                   resampler never is: a cut changes the coarse weights, and the resampler's conditioning
+ *                   (models/utils.py:87-88) gives no bound on what that does to the fine colours.
+ *   Optical depth.  For window w of a ray, tau_w = sum_{k < 32 (w + 1)} relu(sigma_k) (z_{k+1} - z_k), in fp32 over the
+ *                   samples evaluated so far, the delta that reaches into the next window included (summation order
+ *                   unspecified).  A window ended by the empty-window skip (above) contributes 0.
+ *   Cut condition.  After window w, w + 1 < n_samples / 32, the group ends if tau_w >= -ln(eps) for EVERY ray present in
+ *                   the group of four.  A ray past the end of the batch counts as terminated; a ray whose tau is NaN is
+ *                   never terminated.  -ln(eps) is made on the host in double and rounded to fp32.
+ *   Effect.         The remaining windows are not evaluated; their (r, g, b, sigma) are (0, 0, 0, 0) and the compositor
+ *                   runs unchanged on the ray, so those samples get alpha = +0 and weight = +0 exactly.  Weights before
+ *                   the cut are bit-identical to the uncut launch.  `windows_cut` (DEVICE, may be NULL) is ADDED to, one
+ *                   per window of a group not run; the status word reports the windows that ran.
+ *   Bound (derived, not measured).  Truncating a ray at transmittance T loses a total weight of at most T (1 + N 1e-10);
+ *                   the compositor's T is within ~1e-7 of exp(-tau) (per-factor fp32 rounding of 1 - alpha, at most one
+ *                   dominant factor), and re-rounding the lane sums and the six-level wave sum of <= 128 terms <= 1 costs
+ *                   under 1e-6:   |d comp_rgb| <= eps + 2e-6 (white-background term included),
+ *                                 |d opacity|  <= eps + 2e-6,      |d depth| <= (eps + 2e-6) max_k z_k   per ray.
+ *   Restrictions.   The bound needs colours in [0, 1] and a weightless tail.  NSR_SIGMA_SOFTPLUS (raw 0 still has weight)
+ *                   is refused here; a network packed with NSR_OPT_COLOR_NONE (colours outside [0, 1]) is NOT detected at
+ *                   this level: the colour-range condition is the caller's responsibility (the Python mirror refuses it).
+ * Both enqueue without any host synchronisation and can be captured in a graph like their parents.  Before anything touches
+ * the device they return NSR_ERR_INVALID_ARG for a NaN, negative or >= 1 threshold and, with early_stop > 0,
+ * NSR_ERR_UNSUPPORTED for a precision other than NSR_F16X3, for a last-pass sample count other than 64 or 128, and for
+ * NSR_SIGMA_SOFTPLUS.  The raw network output is not available with the option (there is no `raw` argument).
+ * nsr_forward_rays_ert takes the arguments of nsr_forward_rays_profiled (`events` may be NULL), then the two new ones. */
+int nsr_render_rays_composited_ert(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
+                                   int64_t R, int n_samples, int render_flags, float early_stop, float* comp_rgb, float* depth,
+                                   float* opacity, float* weights, unsigned* windows_cut, void* stream);
+int nsr_forward_rays_ert(const void* packed_coarse, const void* packed_fine, int precision, const float* rays, int ray_stride,
+                         int64_t R, int n_coarse, int n_importance, int render_flags, int lindisp, float* const* outs,
+                         void* workspace, size_t workspace_bytes, void* stream, void* const* events, float early_stop,
+                         unsigned* windows_cut);
+
 /* ---- V1: volumetric compositing ------------------------------------------------
  * Replaces VolumetricRenderer.forward (models/rendering.py:75-111).
  * rgb: element (r,k,c) at rgb[(r*N+k)*rgb_stride + c]; sigma: (r,k) at

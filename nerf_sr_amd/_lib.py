@@ -54,6 +54,8 @@ SIGNATURES = {
     "nsr_render_rays": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "nsr_render_rays_composited": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nsr_render_rays_composited_ert": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nsr_composite": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nsr_resample_along_rays": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
@@ -64,6 +66,8 @@ SIGNATURES = {
                                  POINTER(c_void_p), c_void_p, c_size_t, c_void_p]),
     "nsr_forward_rays_profiled": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int,
                                           POINTER(c_void_p), c_void_p, c_size_t, c_void_p, POINTER(c_void_p)]),
+    "nsr_forward_rays_ert": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int,
+                                     POINTER(c_void_p), c_void_p, c_size_t, c_void_p, POINTER(c_void_p), c_float, c_void_p]),
     "nsr_event_create": (c_int, [POINTER(c_void_p)]),
     "nsr_event_destroy": (c_int, [c_void_p]),
     "nsr_event_elapsed_ms": (c_int, [c_void_p, c_void_p, POINTER(c_float)]),

@@ -128,6 +128,8 @@ def build(force: bool = False, verbose: bool = True, variant: str = "", defines=
 TEST_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks.hip")
 # ... and the render launch with its skipped-window counter (tests/test_gpu_empty_skip.py)
 TEST_HOOKS_SRCS = [TEST_HOOKS_SRC, os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_render.hip")]
+# ... and the same launch with early ray termination and both of its counters (tests/test_gpu_early_stop.py)
+TEST_HOOKS_SRCS.append(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_ert.hip"))
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -73,6 +73,27 @@ extern "C" int nsr_forward_rays_profiled(const void* packed_coarse, const void* 
                                          const float* rays, int ray_stride, int64_t R, int n_coarse, int n_importance,
                                          int white_bkgd, int lindisp, float* const* outs, void* workspace,
                                          size_t workspace_bytes, void* stream, void* const* events) {
+  return nsr_forward_rays_ert(packed_coarse, packed_fine, precision, rays, ray_stride, R, n_coarse, n_importance, white_bkgd, lindisp,
+                              outs, workspace, workspace_bytes, stream, events, 0.0f, nullptr);
+}
+
+// early_stop > 0: the LAST network pass (the fine one, or the coarse one when n_importance == 0) is launched with early ray
+// termination; the coarse pass that feeds the resampler never is (include/nsr.h)
+extern "C" int nsr_forward_rays_ert(const void* packed_coarse, const void* packed_fine, int precision, const float* rays,
+                                    int ray_stride, int64_t R, int n_coarse, int n_importance, int white_bkgd, int lindisp,
+                                    float* const* outs, void* workspace, size_t workspace_bytes, void* stream,
+                                    void* const* events, float early_stop, unsigned* windows_cut) {
+  {
+    const int erc = nsr_ert_check(early_stop, precision, n_importance > 0 ? n_coarse + n_importance : n_coarse, white_bkgd);
+    if (erc != NSR_OK) return erc;
+  }
+  // one pass: network + compositing in one launch, cut short if it is the last pass and the option is on
+  auto composited = [&](bool last, const void* packed, const float* z, int n, float* c, float* d, float* o, float* w) {
+    return (last && early_stop > 0.0f)
+               ? nsr_render_rays_composited_ert(packed, precision, rays, ray_stride, z, R, n, white_bkgd, early_stop, c, d, o, w,
+                                                windows_cut, stream)
+               : nsr_render_rays_composited(packed, precision, rays, ray_stride, z, R, n, white_bkgd, nullptr, c, d, o, w, stream);
+  };
   hipStream_t st = nsr_stream(stream);
   auto mark = [&](int i) {
     if (events && events[i]) (void)hipEventRecord(static_cast<hipEvent_t>(events[i]), st);
@@ -104,8 +125,7 @@ extern "C" int nsr_forward_rays_profiled(const void* packed_coarse, const void* 
   // are needed by the resampler even if the caller does not want them.
   float* w_c = outs[3] ? outs[3] : w_c_ws;
   mark(0);
-  rc = nsr_render_rays_composited(packed_coarse, precision, rays, ray_stride, z_c, R, n_coarse, white_bkgd, nullptr, outs[0],
-                                  outs[1], outs[2], w_c, stream);
+  rc = composited(n_importance == 0, packed_coarse, z_c, n_coarse, outs[0], outs[1], outs[2], w_c);
   if (rc == NSR_ERR_UNSUPPORTED) {   // other sample counts / the single-operand fast paths: network, then compositor
     rc = nsr_render_rays(packed_coarse, precision, rays, ray_stride, z_c, R, n_coarse, raw_c, stream);
     mark(1);
@@ -121,8 +141,7 @@ extern "C" int nsr_forward_rays_profiled(const void* packed_coarse, const void* 
   if (rc != NSR_OK) return rc;
   // fine network + compositing
   mark(2);
-  rc = nsr_render_rays_composited(packed_fine, precision, rays, ray_stride, z_f, R, n_coarse + n_importance, white_bkgd, nullptr,
-                                  outs[4], outs[5], outs[6], outs[7], stream);
+  rc = composited(true, packed_fine, z_f, n_coarse + n_importance, outs[4], outs[5], outs[6], outs[7]);
   if (rc != NSR_ERR_UNSUPPORTED) {
     mark(3);
     return rc;

@@ -129,6 +129,15 @@ __device__ __forceinline__ NsrRay nsr_load_ray(const float* __restrict__ rays, i
 }
 static inline bool nsr_ray_stride_ok(int stride) { return stride == 8 || stride == 11; }
 
+// early ray termination (include/nsr.h): the argument checks of the *_ert entry points, made before anything touches the
+// device.  `n_last`: the sample count of the pass that would be cut.  A threshold of 0 is "off" and passes.
+static inline int nsr_ert_check(float early_stop, int precision, int n_last, int render_flags) {
+  if (!(early_stop >= 0.0f && early_stop < 1.0f)) return NSR_ERR_INVALID_ARG;      // NaN, negative, >= 1
+  if (early_stop == 0.0f) return NSR_OK;
+  if (precision != NSR_F16X3 || (n_last != 64 && n_last != 128) || (render_flags & NSR_SIGMA_SOFTPLUS) != 0) return NSR_ERR_UNSUPPORTED;
+  return NSR_OK;
+}
+
 // ---- wave64 reductions / scans (DPP-free, shuffle based) -------------------
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

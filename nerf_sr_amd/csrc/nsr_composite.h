@@ -85,6 +85,10 @@ struct NsrCompOut {
   float* weights;
   int white;
   unsigned* skipped = nullptr;   // tests only: counts the windows the split-fp16 render kernel ended after the density head
+  // early ray termination of the split-fp16 render kernel (include/nsr.h): the optical depth -ln(eps) at which a ray is
+  // spent (0 = off; made on the host in double, rounded to fp32) and a counter of the windows not run (may be null)
+  float ert_tau = 0.0f;
+  unsigned* cut = nullptr;
 };
 
 // Epilogue of a 128-point MLP tile whose points are whole rays (NS = 64: two rays, NS = 128: one ray): stage the tile's

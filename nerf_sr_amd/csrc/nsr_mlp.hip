@@ -544,9 +544,11 @@ extern "C" int nsr_render_rays(const void* packed_dev, int precision, const floa
 extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const float* rays, int ray_stride, const float* z,
                                                        int64_t R, int N, float* raw, const NsrCompOut* co, unsigned* tail, void* stream);
 
-extern "C" int nsr_render_rays_composited(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
-                                          int64_t R, int n_samples, int white_bkgd, float* raw, float* comp_rgb, float* depth,
-                                          float* opacity, float* weights, void* stream) {
+// the one body of both entry points below: argument checks, then the launch.  ert_tau / cut: early ray termination of the
+// split-fp16 kernel (0 / null: off), already checked by the caller
+static int render_rays_composited(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
+                                  int64_t R, int n_samples, int white_bkgd, float* raw, float* comp_rgb, float* depth,
+                                  float* opacity, float* weights, float ert_tau, unsigned* cut, void* stream) {
   if (!packed_dev || R < 0 || n_samples <= 0 || !nsr_ray_stride_ok(ray_stride) || (white_bkgd & ~(NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS)) != 0)
     return NSR_ERR_INVALID_ARG;
   if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
@@ -555,7 +557,9 @@ extern "C" int nsr_render_rays_composited(const void* packed_dev, int precision,
   if (!rays || !z) return NSR_ERR_INVALID_ARG;
   if ((raw && (reinterpret_cast<uintptr_t>(raw) & 15) != 0) || (ray_stride == 8 && (reinterpret_cast<uintptr_t>(rays) & 15) != 0))
     return NSR_ERR_INVALID_ARG;
-  const NsrCompOut co{comp_rgb, depth, opacity, weights, white_bkgd};
+  NsrCompOut co{comp_rgb, depth, opacity, weights, white_bkgd};
+  co.ert_tau = ert_tau;
+  co.cut = cut;
   unsigned* tail = nsr_blob_tail(packed_dev, precision);
   if (precision == NSR_F16X3) return nsr_f16x3_render_composite(packed_dev, rays, ray_stride, z, R, n_samples, raw, &co, tail, stream);
   const int64_t P = R * n_samples;
@@ -567,4 +571,24 @@ extern "C" int nsr_render_rays_composited(const void* packed_dev, int precision,
     hipLaunchKernelGGL((mlp_fp32_kernel<1, false, 128>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, n_samples, ray_stride, raw, NsrTail{tail}, co);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
+}
+
+extern "C" int nsr_render_rays_composited(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
+                                          int64_t R, int n_samples, int white_bkgd, float* raw, float* comp_rgb, float* depth,
+                                          float* opacity, float* weights, void* stream) {
+  return render_rays_composited(packed_dev, precision, rays, ray_stride, z, R, n_samples, white_bkgd, raw, comp_rgb, depth, opacity,
+                                weights, 0.0f, nullptr, stream);
+}
+
+/* the same launch with early ray termination (split-fp16 kernel only), see include/nsr.h.  It lives here, next to its parent
+ * and the launch both share, not in nsr_render.hip (the stand-alone compositor) */
+extern "C" int nsr_render_rays_composited_ert(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
+                                              int64_t R, int n_samples, int render_flags, float early_stop, float* comp_rgb,
+                                              float* depth, float* opacity, float* weights, unsigned* windows_cut, void* stream) {
+  const int rc = nsr_ert_check(early_stop, precision, n_samples, render_flags);
+  if (rc != NSR_OK) return rc;
+  const bool on = early_stop > 0.0f;
+  return render_rays_composited(packed_dev, precision, rays, ray_stride, z, R, n_samples, render_flags, nullptr, comp_rgb, depth, opacity,
+                                weights, on ? (float)(-log((double)early_stop)) : 0.0f,      // -ln eps in double, rounded once
+                                on ? windows_cut : nullptr, stream);
 }

@@ -506,7 +506,16 @@ __device__ __forceinline__ void split_direction(const float (&de)[16], u32x4 (&d
 // to 0.  Consecutive rays are the sub-pixel rays of one LR pixel, so the four waves' depth windows are empty together far
 // more often than the 128 samples of whole rays (scripts/empty_tile_stats.py).  The skip is off under the softplus density
 // and when the raw network output is asked for; a NaN density never skips.
-template <int MODE, bool SIGMA_ONLY, int NS, bool COMP = false, bool TRAIN = false>
+//
+// ERT (COMP only, opt-in: nsr_render_rays_composited_ert, "early ray termination" in include/nsr.h): after every window but
+// the last, each wave adds the window's optical depth sum relu(sigma_k) (z_{k+1} - z_k) -- lane 31's delta reaches the next
+// window's first depth -- to a running fp32 scalar, and when every ray present in the group has reached co.ert_tau = -ln eps
+// the group stops: the remaining windows keep the (0, 0, 0, 0) their registers were initialised with (alpha = +0 and weight
+// = +0 exactly under the relu density) and the loop breaks into the ordinary epilogue, which drains the dead L1 prefetch of
+// a last window anyway.  A NaN optical depth compares false and never terminates; a window ended by the empty skip adds 0.
+// The four waves vote in a word of their own per window (the words behind the skip's vote word, zeroed once before the loop):
+// the skip's word is re-zeroed by wave 0 at the top of the next window, which another wave's late read of it would race.
+template <int MODE, bool SIGMA_ONLY, int NS, bool COMP = false, bool TRAIN = false, bool ERT = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, const float* __restrict__ zv,
                  int64_t P, int N, int stride, float* __restrict__ out, NsrTail tail, NsrCompOut co = NsrCompOut{},
@@ -518,6 +527,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   constexpr int kStash0 = 3 * kSlotFloats, kAux0 = kStash0 + 4 * 8 * 256, kComp0 = kAux0 + hx::kAuxFloats;
   __shared__ __attribute__((aligned(16))) float ring[kComp0 + 640];
   static_assert(!COMP || (MODE == 1 && !SIGMA_ONLY && !TRAIN && (NS == 64 || NS == 128)), "COMP: whole rays of 64 or 128 samples");
+  static_assert(!ERT || COMP, "ERT: an option of the COMP launches");
   constexpr int kWindows = COMP ? NS / 32 : 1;     // COMP: depth windows of a ray group, walked in a loop
   // COMP: the compositor stages in the idle ring after the last window; the first word of the old staging area is the
   // workgroup's vote "some sample of this window is live"
@@ -587,6 +597,12 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     float de[16];
     encode_direction(ray_q.v, h, de);
     split_direction(de, deh, del);
+  }
+  float tau = 0.0f;                                                    // ERT: this wave's optical depth so far
+  if (ERT) {
+#pragma unroll
+    for (int w = 0; w < kWindows; ++w) res[w][0] = res[w][1] = res[w][2] = res[w][3] = 0.0f;
+    if (threadIdx.x < kWindows) vote[1 + threadIdx.x] = 0u;            // published by the first window's barrier
   }
 #pragma unroll 1
   for (int win = 0; win < kWindows; ++win) {
@@ -977,6 +993,18 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
         res[w][3] = sigma;
       }
   }
+  if (ERT && win + 1 < kWindows) {
+    // (the depths are fetched again rather than kept through the window: two cached loads against a register per lane)
+    const float z0 = zv[pc], z1 = zv[pc + 1];                          // pc + 1 <= the next window's first sample
+    tau += wave_sum(h == 0 ? nsr_relu_nan(sigma) * (z1 - z0) : 0.0f);  // (a NaN density stays one)
+    const bool done = my_ray >= n_rays || tau >= co.ert_tau;           // a ray past the end of the batch counts as terminated
+    if (!done && lane == 0) vote[1 + win] = 1u;
+    __syncthreads();
+    if (__builtin_amdgcn_readfirstlane(vote[1 + win]) == 0u) {
+      if (co.cut && threadIdx.x == 0) atomicAdd(co.cut, (unsigned)(kWindows - 1 - win));
+      break;
+    }
+  }
   }   // window
   // COMP: the ring is idle after the drain and the barrier (the last window's dead L1 prefetch included): every wave
   // stages its own ray in it, sample by sample as the two-call route's (R, N, 4) tensor holds them, and composites it
@@ -1038,10 +1066,15 @@ extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const
   const int64_t P = R * N;
   const dim3 grid((unsigned)((R + 3) / 4)), block(256);     // one workgroup per group of 4 consecutive rays
   const float* pk = static_cast<const float*>(packed);
-  if (N == 64)
+  const bool ert = co->ert_tau > 0.0f;                       // early ray termination asked for (0 = off: today's instantiations)
+  if (N == 64 && !ert)
     hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 64, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
-  else if (N == 128)
+  else if (N == 128 && !ert)
     hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 128, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
+  else if (N == 64)
+    hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 64, true, false, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
+  else if (N == 128)
+    hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 128, true, false, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
   else
     return NSR_ERR_UNSUPPORTED;
   if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;

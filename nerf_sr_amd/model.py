@@ -28,6 +28,7 @@ def default_options(**kw) -> SimpleNamespace:
         sigma_activation="relu", gamma_correct=False,   # models/rendering.py:69-73 ('softplus'); nerf_downX_model.py:271-276
         ray_chunk=4096, point_chunk=262144, precision="fp32",
         check_numerics=True,    # forward() raises on NaN / out-of-range values (the reference: pdb, nerf_downX_model.py:273-274)
+        early_stop=0.0,         # eval mode, precision 'f16x3': early ray termination at this transmittance (0 = off; include/nsr.h)
     )
     for k, v in kw.items():
         setattr(opt, k, v)
@@ -44,6 +45,7 @@ class NeRFDownXModel:
         if int(self.opt.N_coarse) < 2 or int(self.opt.N_importance) < 0:
             raise ValueError("N_coarse must be >= 2 and N_importance >= 0")
         self.renderer = VolumetricRenderer(self.opt)      # validates sigma_activation before any device is touched
+        self._check_early_stop()                          # ... and the early-termination option with its restrictions
         self.device = torch.device(device)
         # the fused kernels for the architecture every script of the reference uses, nn.Linear by nn.Linear for any other
         self.netCoarse = ops.make_mlp(self.opt, precision=self.opt.precision, device=self.device)
@@ -62,6 +64,29 @@ class NeRFDownXModel:
         self.netCoarse.load_state_dict(sd_coarse)
         self.netFine.load_state_dict(sd_fine)
         return self        # (the colour-head options of `opt` -- gamma_correct, color_activation -- are applied by VanillaMLP)
+
+    def _check_early_stop(self) -> float:
+        """``opt.early_stop`` checked against the options it depends on, before any device is touched (ops.check_early_stop
+        repeats the check on the networks themselves at every call).  Like every other option it is read from ``opt`` at
+        call time: the constructor checks it early, every eval-mode forward checks it again, so a later
+        ``model.opt.early_stop = eps`` takes effect or raises, never passes unnoticed."""
+        opt = self.opt
+        eps = float(getattr(opt, "early_stop", 0.0))
+        if not (0.0 <= eps < 1.0):
+            raise ValueError(f"early_stop={getattr(opt, 'early_stop', None)!r}: a transmittance threshold in [0, 1) (0 = off)")
+        if eps == 0.0:
+            return eps
+        if opt.precision != "f16x3":
+            raise ValueError(f"early_stop needs precision 'f16x3' (the split-fp16 render kernel), not {opt.precision!r}")
+        if self.renderer.sigma_activation != "relu":
+            raise ValueError("early_stop needs the relu density: under sigma_activation='softplus' a raw density of 0 still has weight")
+        if getattr(opt, "color_activation", "sigmoid") == "none":
+            raise ValueError("early_stop needs colours in [0, 1]: color_activation='none' leaves them unbounded")
+        if int(opt.N_coarse) + int(opt.N_importance) not in (64, 128):
+            raise ValueError(f"early_stop needs 64 or 128 samples in the pass that is cut, not {int(opt.N_coarse) + int(opt.N_importance)}")
+        if not ops.is_default_arch(ops.arch_of(opt)):
+            raise ValueError("early_stop needs the architecture of the fused kernels (8 x 256, skip at 4, degrees 10 / 4)")
+        return eps
 
     # -- mode toggles (nerf_downX_model.py:250-258) ------------------------------
     def train(self):
@@ -95,12 +120,13 @@ class NeRFDownXModel:
 
     # -- D3 ------------------------------------------------------------------------
     def forward_rays(self, rays: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """``opt.early_stop`` applies to the eval-mode forward only (the fine pass, include/nsr.h); ``train()`` mode ignores it."""
         opt = self.opt
         if not self.randomized and self.fused:
             self._outs = ops.forward_rays(self.netCoarse, self.netFine if opt.N_importance > 0 else None, rays,
                                           opt.N_coarse, opt.N_importance, opt.white_bkgd, opt.lindisp,
                                           check=bool(getattr(opt, "check_numerics", True)),
-                                          sigma_activation=self.renderer.sigma_activation)
+                                          sigma_activation=self.renderer.sigma_activation, early_stop=self._check_early_stop())
             return self._outs
         # randomized (training-mode) forward, and every forward of a GenericMLP pair: same kernels, stage by stage, jitter
         # drawn with torch.rand
@@ -245,7 +271,10 @@ class NeRFDownXModel:
         GENERATES its own ray block on its device (nothing is scattered), runs the eval-mode ``forward_rays`` on it, and
         ONE all-gather assembles the frame on every rank.  Replaces the per-MLP-call scatter / gather of
         nn.DataParallel (models/networks.py:54-69).  No reduction crosses a block boundary, so the result is
-        bit-identical to ``render_image`` on one GPU.
+        bit-identical to ``render_image`` on one GPU.  That holds with ``opt.early_stop`` too, at the same threshold: the kernel
+        decides per group of four consecutive rays, shards start at multiples of s*s >= 4 rays, so the groups of a sharded
+        render are the groups of the whole frame.  The exception is ``downscale`` s = 1, whose shards start at any ray: the
+        groups then differ between the two renders and the frames agree within the option's bound only.
 
         ``gather``: what the collective carries.
           * ``"lr"`` (default): the s*s means, [r, g, b, depth] per LR pixel (16 B / LR pixel) -> ``lr_rgb``, ``lr_depth``.
@@ -273,7 +302,7 @@ class NeRFDownXModel:
         if self.fused:
             out = ops.forward_rays(self.netCoarse, self.netFine if fine else None, rays, opt.N_coarse, opt.N_importance,
                                    opt.white_bkgd, opt.lindisp, workspace=workspace, outs=outs, want_weights=want_weights,
-                                   sigma_activation=self.renderer.sigma_activation)
+                                   sigma_activation=self.renderer.sigma_activation, early_stop=self._check_early_stop())
         else:               # a GenericMLP pair: the eval-mode staged route
             was, self.randomized = self.randomized, False
             try:

@@ -547,23 +547,59 @@ def render_rays(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.Tensor):
     return raw[..., :3], raw[..., 3]
 
 
+def check_early_stop(early_stop: float, net, n_last: int, sigma_activation: str = "relu") -> float:
+    """Validates the early-ray-termination threshold of ``render_rays_composited`` / ``forward_rays`` against everything the
+    bound of include/nsr.h needs (``n_last``: the sample count of the pass that would be cut) and returns it as a float; a
+    ``ValueError`` names the condition that fails -- the option is never ignored silently.  0 is "off" and always passes."""
+    eps = float(early_stop)
+    if not (0.0 <= eps < 1.0):          # NaN included
+        raise ValueError(f"early_stop={early_stop!r}: a transmittance threshold in [0, 1) (0 = off)")
+    if eps == 0.0:
+        return eps
+    if not isinstance(net, VanillaMLP) or net.precision != "f16x3":
+        raise ValueError(f"early_stop needs precision 'f16x3' (the split-fp16 render kernel), not {getattr(net, 'precision', None)!r}")
+    if sigma_activation != "relu":
+        raise ValueError("early_stop needs the relu density: under sigma_activation='softplus' a raw density of 0 still has weight")
+    if net.color_activation == "none":
+        raise ValueError("early_stop needs colours in [0, 1]: the network was built with color_activation='none'")
+    if int(n_last) not in (64, 128):
+        raise ValueError(f"early_stop needs 64 or 128 samples in the pass that is cut, not {int(n_last)}")
+    return eps
+
+
 def render_rays_composited(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.Tensor, white_bkgd: bool,
-                           want_raw: bool = False, sigma_activation: str = "relu"):
+                           want_raw: bool = False, sigma_activation: str = "relu", early_stop: float = 0.0,
+                           want_cut_count: bool = False):
     """``render_rays`` + ``VolumetricRenderer.forward`` in one launch (models/nerf_downX_model.py:289-291): 64 or 128
     samples per ray, fp32 / f16x3.  Returns ``(comp_rgb (R,3), depth (R), opacity (R), weights (R,N))`` and, if
-    ``want_raw``, the (R, N, 4) network output as a fifth element.  Bit-identical to the two-call route."""
+    ``want_raw``, the (R, N, 4) network output as a fifth element.  Bit-identical to the two-call route.
+
+    ``early_stop`` = eps > 0 (f16x3 only): early ray termination -- a group of four consecutive rays stops after a 32-sample
+    window once every one of its rays has optical depth >= -ln(eps); outputs move by at most eps + 2e-6 (include/nsr.h).
+    Not bit-identical to anything, not combinable with ``want_raw``.  ``want_cut_count`` appends the number of windows not
+    run as a 1-element int32 device tensor (0 with the option off)."""
     rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
     R, N = z_vals.shape
     dev = rays.device
+    eps = check_early_stop(early_stop, model, N, sigma_activation)
+    if eps > 0.0 and want_raw:
+        raise ValueError("early_stop and want_raw exclude each other: the windows that are cut have no network output")
     comp = torch.empty(R, 3, dtype=torch.float32, device=dev)
     depth = torch.empty(R, dtype=torch.float32, device=dev)
     opac = torch.empty(R, dtype=torch.float32, device=dev)
     w = torch.empty(R, N, dtype=torch.float32, device=dev)
     raw = torch.empty(R, N, 4, dtype=torch.float32, device=dev) if want_raw else None
+    cut = torch.zeros(1, dtype=torch.int32, device=dev) if want_cut_count else None
+    if eps > 0.0:
+        _lib.check(_lib.load().nsr_render_rays_composited_ert(_p(model.packed), model._prec, _p(rays), _ray_stride(rays), _p(z_vals), R, N,
+                                                              renderer_flags(white_bkgd, sigma_activation), eps, _p(comp), _p(depth),
+                                                              _p(opac), _p(w), _p(cut), _stream()), "nsr_render_rays_composited_ert")
+        return (comp, depth, opac, w, cut) if want_cut_count else (comp, depth, opac, w)
     _lib.check(_lib.load().nsr_render_rays_composited(_p(model.packed), model._prec, _p(rays), _ray_stride(rays), _p(z_vals), R, N,
                                                       renderer_flags(white_bkgd, sigma_activation), _p(raw), _p(comp), _p(depth), _p(opac), _p(w),
                                                       _stream()), "nsr_render_rays_composited")
-    return (comp, depth, opac, w, raw) if want_raw else (comp, depth, opac, w)
+    res = (comp, depth, opac, w, raw) if want_raw else (comp, depth, opac, w)
+    return res + (cut,) if want_cut_count else res
 
 
 OUT_KEYS = ("coarse_comp_rgbs", "coarse_depth", "coarse_opacity", "coarse_weights",
@@ -574,7 +610,8 @@ def forward_rays(coarse: VanillaMLP, fine: Optional[VanillaMLP], rays: torch.Ten
                  N_importance: int = 64, white_bkgd: bool = False, lindisp: bool = False,
                  workspace: Optional[torch.Tensor] = None, outs: Optional[Dict[str, torch.Tensor]] = None,
                  want_weights: bool = True, events=None, check: bool = False,
-                 sigma_activation: str = "relu") -> Dict[str, torch.Tensor]:
+                 sigma_activation: str = "relu", early_stop: float = 0.0,
+                 cut_count: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
     """Eval-mode forward_rays for the WHOLE batch in one enqueue sequence
     (models/nerf_downX_model.py:280-324; with 11-wide rays: the vanilla model's models/nerf_model.py:207-242):
     returns the reference's 8-entry dict.
@@ -583,7 +620,10 @@ def forward_rays(coarse: VanillaMLP, fine: Optional[VanillaMLP], rays: torch.Ten
     ``check=True`` reads both networks' numerics status words after the enqueue (one stream wait) and raises
     ``NsrNumericsError`` on non-finite inputs / outputs or out-of-range activations -- the reference's NaN trap
     (models/nerf_downX_model.py:273-274) as an exception; ``False`` leaves the sticky flags for a later
-    ``net.check()`` / ``net.status()`` (nothing is synchronised)."""
+    ``net.check()`` / ``net.status()`` (nothing is synchronised).
+    ``early_stop`` = eps > 0 (f16x3 only): early ray termination in the LAST network pass (the fine one, or the coarse one when
+    ``N_importance == 0``; the coarse pass that feeds the resampler is never cut), see ``render_rays_composited`` and
+    include/nsr.h; ``cut_count``: a 1-element int32 device tensor the launch ADDS the number of windows not run to."""
     lib = _lib.load()
     rays = _f32(rays, "rays")
     rays = rays.reshape(-1, rays.shape[-1])
@@ -593,6 +633,9 @@ def forward_rays(coarse: VanillaMLP, fine: Optional[VanillaMLP], rays: torch.Ten
         raise ValueError("N_importance > 0 needs the fine network")
     if fine is not None and fine._prec != coarse._prec:
         raise ValueError("coarse and fine networks must use the same precision")
+    eps = check_early_stop(early_stop, fine if N_importance > 0 else coarse, N_coarse + N_importance, sigma_activation)
+    if cut_count is not None and (cut_count.dtype != torch.int32 or cut_count.numel() != 1 or cut_count.device != rays.device):
+        raise ValueError("cut_count must be a 1-element int32 tensor on the rays' device")
     dev = rays.device
     need = lib.nsr_forward_rays_workspace_bytes_for(coarse._prec, R, N_coarse, N_importance)
     if workspace is None or workspace.numel() < need:
@@ -610,11 +653,13 @@ def forward_rays(coarse: VanillaMLP, fine: Optional[VanillaMLP], rays: torch.Ten
             outs[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
     ptrs = (c_void_p * 8)(*[_p(outs.get(k)) for k in OUT_KEYS])
     ev = (c_void_p * 4)(*events) if events is not None else None
-    _lib.check(lib.nsr_forward_rays_profiled(_p(coarse.packed), _p(fine.packed) if fine is not None else c_void_p(0),
-                                             coarse._prec, _p(rays), stride, R, N_coarse, N_importance,
-                                             renderer_flags(white_bkgd, sigma_activation),
-                                             int(bool(lindisp)), ptrs, _p(workspace), workspace.numel(), _stream(), ev),
-               "nsr_forward_rays")
+    args = (_p(coarse.packed), _p(fine.packed) if fine is not None else c_void_p(0), coarse._prec, _p(rays), stride, R, N_coarse,
+            N_importance, renderer_flags(white_bkgd, sigma_activation), int(bool(lindisp)), ptrs, _p(workspace), workspace.numel(),
+            _stream(), ev)
+    if eps > 0.0:
+        _lib.check(lib.nsr_forward_rays_ert(*args, eps, _p(cut_count)), "nsr_forward_rays_ert")
+    else:
+        _lib.check(lib.nsr_forward_rays_profiled(*args), "nsr_forward_rays")
     if check:
         coarse.check("coarse network")
         if fine is not None and N_importance > 0:
