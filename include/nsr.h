@@ -81,11 +81,17 @@ size_t nsr_packed_weights_bytes(int precision);
 /* w: HOST array of 24 DEVICE pointers (nn.Linear layout (out,in) row-major).
  * Checked: returns NSR_ERR_RANGE (the blob is written all the same) when a weight or bias is non-finite, or when
  * a weight leaves the operand range of `precision` -- NSR_F16X3 carries 2^6 w as an fp16 (hi, lo) pair and NSR_F16
- * carries w as fp16, so |w| must stay below 1023.75 / 65520; NSR_FP32 and NSR_BF16 have the fp32 range.  To return
+ * carries w as fp16, so |w| must stay below 1023.75 / 65520; NSR_FP32 and NSR_BF16 have the fp32 range.
+ * NSR_F16X3 additionally folds xyz_encoding_final (a bare Linear that feeds dir_encoding alone) into dir_encoding while
+ * packing -- W' = W_dir[:, :256] W_final (summed in double, rounded once), b' = b_dir + W_dir[:, :256] b_final -- and W'
+ * enters the stream like every weight: the same verdict when any |W'| >= 1023.75 or any W' / b' is non-finite.  A network
+ * whose 24 tensors pass can therefore be refused at NSR_F16X3; it takes products of magnitude ~1e3 summed over 256 terms
+ * (the benchmark's networks: |W'| <= 0.52).  Load such a network with NSR_FP32.  To return
  * that verdict the call WAITS for `stream` (a load-time call; one of the two synchronising entry points). */
 int nsr_pack_weights(const float* const* w, void* packed_dev, int precision, void* stream);
-/* The same, enqueue only (re-packing inside a training loop): the range verdict lands in the blob's status word as
- * NSR_FLAG_WEIGHT_RANGE and is read with nsr_weights_status. */
+/* The same, enqueue only (re-packing inside a training loop): the range verdict -- of the 24 tensors and, at NSR_F16X3, of
+ * the folded W' / b' as well -- lands in the blob's status word as NSR_FLAG_WEIGHT_RANGE and is read with
+ * nsr_weights_status. */
 int nsr_pack_weights_async(const float* const* w, void* packed_dev, int precision, void* stream);
 
 /* ---- numerics status word ------------------------------------------------------
@@ -93,7 +99,8 @@ int nsr_pack_weights_async(const float* const* w, void* packed_dev, int precisio
  * SURVEY 8b "Error conventions": a replacement reports an error instead).  Every packed blob ends in a 32-bit STICKY
  * status word (cleared by nsr_pack_weights*).  Every launch that evaluates the network through that blob ORs flags into
  * it -- nothing is synchronised, nothing is checked on the host, until the caller asks:
- *   NSR_FLAG_WEIGHT_RANGE       set while packing, see nsr_pack_weights
+ *   NSR_FLAG_WEIGHT_RANGE       set while packing (nsr_pack_weights and nsr_pack_weights_async alike), see nsr_pack_weights: a
+ *                               tensor out of the precision's range or non-finite, or, NSR_F16X3, the folded W' / b'
  *   NSR_FLAG_INPUT_RANGE        a ray origin / direction / depth (or an embedded input row) was non-finite, or -- split
  *                               and single fp16 paths -- a sample position / direction beyond fp16's 65,504
  *   NSR_FLAG_ACTIVATION_RANGE   NSR_F16X3: a hidden activation left the range in which the (hi, lo) split keeps its 22
@@ -102,7 +109,7 @@ int nsr_pack_weights_async(const float* const* w, void* packed_dev, int precisio
  *                               (6 x below the limit); a diverged network trips it.  Re-run with NSR_FP32.
  *   NSR_FLAG_OUTPUT_NONFINITE   a network output (r, g, b, sigma) was inf / NaN
  * One exception: the NSR_F16X3 launch of nsr_render_rays_composited / nsr_forward_rays* does not evaluate the colour branch
- * (xyz_encoding_final, dir_encoding, rgb) of a window of 4 consecutive rays x 32 consecutive samples whose 128 raw
+ * (dir_encoding with xyz_encoding_final folded into it, rgb) of a window of 4 consecutive rays x 32 consecutive samples whose 128 raw
  * densities are all <= 0 (relu density, raw == NULL: those colours have weight exactly 0).  For such a window the word
  * reports the inputs, the trunk and the density only; a NaN density is not <= 0 and keeps its window whole.
  * nsr_weights_status copies the word to *flags_out (HOST), clears it on the device if `clear`, and WAITS for `stream`

@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(256) pack_fp32_kernel(PackPtrs w, float* __res
 
 // split-fp16 kernels (nsr_mlp_f16.hip)
 extern "C" NSR_INTERNAL size_t nsr_f16x3_packed_bytes(void);
-extern "C" NSR_INTERNAL int nsr_f16x3_pack(const float* const* w, void* packed_dev, void* stream);
+extern "C" NSR_INTERNAL int nsr_f16x3_pack(const float* const* w, void* packed_dev, float limit, unsigned* tail, void* stream);
 extern "C" NSR_INTERNAL int nsr_f16x3_mlp_forward(const void* packed, const float* x, int64_t P, int sigma_only, float* out,
                                      unsigned* tail, void* stream);
 extern "C" NSR_INTERNAL int nsr_f16x3_render_rays(const void* packed, const float* rays, int ray_stride, const float* z, int64_t R,
@@ -181,7 +181,8 @@ extern "C" int nsr_pack_weights_async(const float* const* w, void* packed_dev, i
   hipLaunchKernelGGL(check_weights_kernel, dim3(16, NSR_N_STATE_TENSORS), dim3(256), 0, nsr_stream(stream), cp,
                      precision_weight_limit(precision), tail);
   NSR_CHECK_LAUNCH();
-  if (precision == NSR_F16X3) return nsr_f16x3_pack(w, packed_dev, stream);
+  // (folds xyz_encoding_final into dir_encoding first; the folded matrix is range-checked like the 24 tensors)
+  if (precision == NSR_F16X3) return nsr_f16x3_pack(w, packed_dev, precision_weight_limit(precision), tail, stream);
   if (precision_h1(precision)) return nsr_h1_pack(precision == NSR_BF16, w, packed_dev, stream);
   PackPtrs pp;
   for (int i = 0; i < NSR_N_STATE_TENSORS; ++i) pp.p[i] = w[i];

@@ -40,7 +40,34 @@ __device__ __forceinline__ int tensor_ld_h(int tensor) {
 }
 
 
-// one thread per 32-bit word of the blob
+// The fold (nsr_mlp_layout.h, "Folded dir_encoding"): one thread per element of W' (128 x 256), then of b' (128).  Each sums
+// its 256 products in double, in index order, and rounds once to float: two more fp32 roundings per element would be the
+// precision the 22-bit hi + lo split of W' exists to keep.  W' enters the fp16 stream x 2^6 like every weight, so it gets
+// the weights' range check (include/nsr.h, nsr_pack_weights); b' only has to be finite.  tail: the blob's status word.
+__global__ void __launch_bounds__(256) fold_final_kernel(PackPtrsH w, float* __restrict__ out, float limit, unsigned* __restrict__ tail) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  constexpr int kW = (kWidth / 2) * kWidth;
+  const int kLd = tensor_ld_h(18);
+  if (idx >= kW + kWidth / 2) return;
+  const float* wd = w.p[18];
+  double acc;
+  float lim = limit;
+  if (idx < kW) {
+    const int n = idx >> 8, c = idx & 255;
+    acc = 0.0;
+    for (int k = 0; k < kWidth; ++k) acc += (double)wd[n * kLd + k] * (double)w.p[16][k * kWidth + c];
+  } else {
+    const int n = idx - kW;
+    acc = (double)w.p[19][n];
+    for (int k = 0; k < kWidth; ++k) acc += (double)wd[n * kLd + k] * (double)w.p[17][k];
+    lim = 3.402823466e38f;
+  }
+  const float v = (float)acc;
+  out[kFoldW0 + idx] = v;
+  if (!(fabsf(v) <= lim)) atomicOr(tail, NSR_FLAG_WEIGHT_RANGE);   // also true for NaN; never on a healthy network
+}
+
+// one thread per 32-bit word of the blob up to the end of the folded chunks (TWO: of the aux block)
 template <bool TWO>
 __device__ __forceinline__ void pack_f16x3_body(const PackPtrsH& w, unsigned* __restrict__ out);
 __global__ void __launch_bounds__(256) pack_f16x3_kernel(PackPtrsH w, unsigned* __restrict__ out) { pack_f16x3_body<false>(w, out); }
@@ -53,9 +80,31 @@ template <bool TWO>
 __device__ __forceinline__ void pack_f16x3_body(const PackPtrsH& w, unsigned* __restrict__ out) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   const int stream_words = kPiecesTotal * 256;
-  if (idx >= stream_words + hx::kAuxFloats) return;
+  if (idx >= (TWO ? stream_words + hx::kAuxFloats : kFoldW0)) return;
   unsigned v = 0u;
-  if (idx < stream_words) {
+  if (!TWO && idx >= stream_words + hx::kAuxFloats) {
+    // folded dir_encoding chunks behind the aux block (the words between the two stay zero); W' / b': fold_final_kernel
+    const int piece = (idx >> 8) - kFoldPiece0, word = idx & 255;
+    if (piece >= 0) {
+      const float* fw = reinterpret_cast<const float*>(out) + kFoldW0;
+      const float* fb = reinterpret_cast<const float*>(out) + kFoldB0;
+      const int nb = piece / kFoldChunkPieces, local = piece % kFoldChunkPieces;
+      if (local == kFoldChunkPieces - 1) {
+        if (word < 32) v = __float_as_uint(kWScale * fb[32 * nb + word]);
+      } else {
+        const int s = local >> 1, part = local & 1;
+        const int lane = word >> 2, jj = word & 3;
+        const int n = 32 * nb + (lane & 31), h = lane >> 5;
+        float f[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const int col = column_of(18, s, 2 * jj + e, h);
+          f[e] = (col == kPad) ? 0.0f : kWScale * (col < kWidth ? fw[n * kWidth + col] : w.p[18][n * tensor_ld_h(18) + col]);
+        }
+        v = pack_hl(f[0], f[1], part);
+      }
+    }
+  } else if (idx < stream_words) {
     const int piece = idx >> 8, word = idx & 255;
     const Chunk c = chunk_info(chunk_of_piece(piece));
     const int local = piece - c.piece0;
@@ -89,16 +138,20 @@ __device__ __forceinline__ void pack_f16x3_body(const PackPtrsH& w, unsigned* __
   out[idx] = v;
 }
 
-extern "C" NSR_INTERNAL size_t nsr_f16x3_packed_bytes(void) { return 4 * (size_t)(kPiecesTotal * 256 + hx::kAuxFloats); }
+extern "C" NSR_INTERNAL size_t nsr_f16x3_packed_bytes(void) { return 4 * (size_t)kBlobWords; }
 
-extern "C" NSR_INTERNAL int nsr_f16x3_pack(const float* const* w, void* packed_dev, void* stream) {
+// tail: the blob's status word (NSR_FLAG_WEIGHT_RANGE of the folded matrix); limit: the weights' range limit
+extern "C" NSR_INTERNAL int nsr_f16x3_pack(const float* const* w, void* packed_dev, float limit, unsigned* tail, void* stream) {
   PackPtrsH pp;
   for (int i = 0; i < NSR_N_STATE_TENSORS; ++i) {
     if (!w[i]) return NSR_ERR_INVALID_ARG;
     pp.p[i] = w[i];
   }
-  const int total = kPiecesTotal * 256 + hx::kAuxFloats;
-  hipLaunchKernelGGL(pack_f16x3_kernel, dim3((total + 255) / 256), dim3(256), 0, nsr_stream(stream), pp,
+  constexpr int n_fold = (kWidth / 2) * kWidth + kWidth / 2;
+  hipLaunchKernelGGL(fold_final_kernel, dim3((n_fold + 255) / 256), dim3(256), 0, nsr_stream(stream), pp,
+                     static_cast<float*>(packed_dev), limit, tail);
+  NSR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(pack_f16x3_kernel, dim3((kFoldW0 + 255) / 256), dim3(256), 0, nsr_stream(stream), pp,
                      static_cast<unsigned*>(packed_dev));
   NSR_CHECK_LAUNCH();
   return NSR_OK;
@@ -118,7 +171,7 @@ extern "C" NSR_INTERNAL int nsr_f16x3_pack2(const float* const* w0, void* packed
   return NSR_OK;
 }
 
-// trunk layer L (1..8: L2..L8, xyz_encoding_final), output block nb: chunk ids 2 + 8(L-1) + nb (see chunk_info)
+// trunk layer L (1..8: L2..L8, xyz_encoding_final -- TRAIN only), output block nb: chunk ids 2 + 8(L-1) + nb (see chunk_info)
 __device__ __forceinline__ ChunkRef layer_ref(int L, int nb, int wave) {
   const int pieces = (L == 4) ? 41 : 33;
   const int base = (L <= 3) ? 66 + 264 * (L - 1) : (L == 4 ? 858 : 1186 + 264 * (L - 5));
@@ -126,6 +179,8 @@ __device__ __forceinline__ ChunkRef layer_ref(int L, int nb, int wave) {
 }
 __device__ __forceinline__ ChunkRef sigma_ref(int wave) { return make_ref(2242, 33, wave); }
 __device__ __forceinline__ ChunkRef dir_ref(int nb, int wave) { return make_ref(2275 + 37 * nb, 37, wave); }
+// the folded dir_encoding chunks behind the aux block (nsr_mlp_layout.h): what every kernel but the TRAIN forward reads
+__device__ __forceinline__ ChunkRef fdir_ref(int nb, int wave) { return make_ref(kFoldPiece0 + kFoldChunkPieces * nb, kFoldChunkPieces, wave); }
 // past the end of the sequence chunk 0 is re-fetched into the idle slot (32 KiB of dead traffic, twice per
 // tile) so that the first eight DMA issues of every chunk need no bounds test; the kernel drains before exit
 __device__ __forceinline__ ChunkRef end_ref(int wave) { return make_ref(0, 32, wave); }
@@ -145,8 +200,9 @@ __device__ __forceinline__ ChunkRef first_ref(int c, int wave) { return make_ref
 //                                        means another small number -- harmless, because lo is computed from the bits
 //                                        hi actually holds, so hi + lo is x / 64 either way)
 //   lo     = RNE_f16(x * 2^-6 - hi)     (v_fma_mixlo / mixhi with an f16 source; the fma result is exact in fp32)
-// xyz_encoding_final has no ReLU and negative values do not survive the unsigned exponent trick: there hi comes from
-// two v_fma_mix (RNE_f16(x * 2^-6)) instead of the cvt / sub pair.
+// xyz_encoding_final (evaluated by the TRAIN forward only; folded into dir_encoding everywhere else) has no ReLU and negative
+// values do not survive the unsigned exponent trick: there hi comes from two v_fma_mix (RNE_f16(x * 2^-6)) instead of the
+// cvt / sub pair.
 // The work is issued as 17 HALF-STEPS of three instructions; the lo of pair P - 1 is interleaved with the hi of pair P.
 // asm volatile pins each half-step into its k-step (MFMA shadow); LLVM would otherwise sink the work to its first
 // use, i.e. serialise all eight blocks' conversions at the layer end.
@@ -347,9 +403,8 @@ __device__ __forceinline__ void prefetch_next_chunk(Pre& nxt, int k, int g, cons
 // chunk's last DMA piece (k-step 13).  Vector-memory operations complete in issue order, so the next publish point --
 // which must see that DMA landed -- may leave those stores in flight (block_mma's YOUNGER); they have a whole further
 // chunk to reach HBM.  (Rounds 2-4 stored the sixteen raw fp32 accumulators of a block here.)
-// PEND0 = false: nothing is pending on entry (the windowed render kernel runs the density head between L8 and
-// xyz_encoding_final: L8's last block was re-split in the density block's shadow, and that block has no re-split).
-template <bool RELU_OUT, bool TRAIN = false, bool PEND0 = true>   // relu on L2..L8 (true), none on xyz_encoding_final (L == 8: false)
+// Only the TRAIN forward evaluates xyz_encoding_final (L == 8); everywhere else it is folded into dir_encoding.
+template <bool RELU_OUT, bool TRAIN = false>   // relu on L2..L8 (true), none on xyz_encoding_final (L == 8: false)
 __device__ __forceinline__ void trunk_layer(int L, u32x4 (&bh)[16], u32x4 (&bl)[16], u32x4 (&oh)[16], u32x4 (&ol)[16],
                                             const u32x4* stash, Loader& ld, int h, Acc& pend, Pre& pre,
                                             const ChunkRef& after0, const ChunkRef& after1, float& amax, unsigned& sbits,
@@ -403,7 +458,7 @@ __device__ __forceinline__ void trunk_layer(int L, u32x4 (&bh)[16], u32x4 (&bl)[
           if (nb == 0) {
             // block 7 of the previous layer (always relu'd: the previous layer is L1..L7) -> k-steps 14, 15
             // of THIS layer's input, needed only at the end of this chunk
-            if (PEND0) pending_gap<true>(s, g, pend, ptmp, bh[14], bl[14], bh[15], bl[15], amax);
+            pending_gap<true>(s, g, pend, ptmp, bh[14], bl[14], bh[15], bl[15], amax);
           } else
             pending_gap<RELU_OUT>(s, g, pend, ptmp, oh[2 * nb - 2], ol[2 * nb - 2], oh[2 * nb - 1], ol[2 * nb - 1], amax);
           if (TRAIN && s >= 8 && g == 2) {
@@ -498,11 +553,10 @@ __device__ __forceinline__ void split_direction(const float (&de)[16], u32x4 (&d
 // RAYS (grid = ceil(R / 4)), wave w owns ray 4 g + w and walks its NS / 32 windows of 32 consecutive samples in a loop; the
 // weight ring keeps streaming across windows (the last two dir_encoding blocks fetch the next window's L1 chunks), a
 // finished window's (r, g, b, sigma) stays in four registers, and after the last window every wave stages its own ray in the
-// by then idle ring and composites it.  The density head runs BEFORE xyz_encoding_final there (L8 -> sigma ->
-// xyz_encoding_final -> dir_encoding: the blocks are independent sums over the same operands, so every value is bit for
-// bit what the other order gives), which lets a window whose 128 samples all have raw density <= 0 stop after it: under
+// by then idle ring and composites it.  The density head runs right behind L8 (L8 -> sigma -> folded dir_encoding: every
+// inference instantiation's order), which lets a window whose 128 samples all have raw density <= 0 stop after it: under
 // the relu density such a sample's alpha is exactly 0, its weight +0 and w * rgb = 0 for any finite rgb (composite_ray), so
-// xyz_encoding_final, dir_encoding and the colour head -- 200 of the window's 1,184 k-steps -- are dead work and rgb is set
+// dir_encoding and the colour head -- 80 of the window's 1,056 k-steps -- are dead work and rgb is set
 // to 0.  Consecutive rays are the sub-pixel rays of one LR pixel, so the four waves' depth windows are empty together far
 // more often than the 128 samples of whole rays (scripts/empty_tile_stats.py).  The skip is off under the softplus density
 // and when the raw network output is asked for; a NaN density never skips.
@@ -797,9 +851,9 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   pre = l1pre;
 
   NSR_TL(2);
-  // ---- L2..L8 (+ xyz_encoding_final), two layers per trip so the register sets swap roles.  Three trips of relu
-  // layers (L2..L7); the last pair (L8 + xyz_encoding_final, which has no relu) is peeled so that the activation is a
-  // compile-time property of every re-split.
+  // ---- L2..L8, two layers per trip so the register sets swap roles.  Three trips of relu layers (L2..L7); L8 is peeled:
+  // what follows it differs (the density head; in the TRAIN forward xyz_encoding_final, which has no relu -- the
+  // activation is a compile-time property of every re-split).
 #pragma unroll 1
   for (int pair = 0; pair < 3; ++pair) {
     const int L = 1 + 2 * pair;
@@ -807,24 +861,23 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     trunk_layer<true, TRAIN>(L + 1, oh, ol, bh, bl, stash, ld, h, pend, pre, layer_ref(L + 2, 0, wv), layer_ref(L + 2, 1, wv), amax,
                              sbits, tr, voff0, voff1);
   }
-  if (SIGMA_ONLY) {   // xyz_encoding_final is not evaluated: L8 is followed by the density head, then nothing
+  if (SIGMA_ONLY) {   // L8 is followed by the density head, then nothing
     trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), first_ref(0, wv), amax, sbits);
-  } else if (COMP) {  // the density head comes next (SIGMA_ONLY's sequence), xyz_encoding_final after it
-    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), layer_ref(8, 0, wv), amax, sbits);
-  } else {
+  } else if (!TRAIN) {  // the density head comes next (SIGMA_ONLY's sequence), the folded dir_encoding after it
 #ifdef NSR_ABL_TIMELINE
-    trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wv), layer_ref(8, 1, wv), amax, sbits, tr, voff0, voff1, tk);
+    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), fdir_ref(0, wv), amax, sbits, tr, voff0, voff1, tk);
     ld.tk = nullptr;
 #else
-    trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wv), layer_ref(8, 1, wv), amax, sbits, tr, voff0, voff1);
+    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), fdir_ref(0, wv), amax, sbits);
 #endif
+  } else {              // the training forward keeps xyz_encoding_final: its output (panel 8) feeds the weight gradients
+    trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wv), layer_ref(8, 1, wv), amax, sbits, tr, voff0, voff1);
     trunk_layer<false, TRAIN>(8, oh, ol, bh, bl, stash, ld, h, pend, pre, sigma_ref(wv), dir_ref(0, wv), amax, sbits, tr, voff0, voff1);
   }
 
   NSR_TL(3);
-  // ---- density head: sigma.weight as row 0 of one more 32-row block over h8 (= oh/ol: the input of
-  // xyz_encoding_final, still intact).  The pending block is xyz_encoding_final's last one (-> bh, no
-  // activation), or L8's last one in a sigma_only or COMP launch (-> oh, relu).
+  // ---- density head: sigma.weight as row 0 of one more 32-row block over h8 (= oh/ol).  The pending block is L8's
+  // last one (-> oh, relu); in the TRAIN forward xyz_encoding_final's last one (-> bh, no activation).
   float sigma;
   {
     Acc cur;
@@ -838,10 +891,10 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     constexpr bool kDensityMma = true;
 #endif
     block_mma3<16, kBar, (TRAIN ? kTrainYoung : 0), true, kDensityMma>(
-        cur, pre, ld.slot_cur + ld.lane_off, ld, SIGMA_ONLY ? first_ref(1, wv) : (COMP ? layer_ref(8, 1, wv) : dir_ref(1, wv)),
+        cur, pre, ld.slot_cur + ld.lane_off, ld, SIGMA_ONLY ? first_ref(1, wv) : (TRAIN ? dir_ref(1, wv) : fdir_ref(1, wv)),
         [&](int s, int part) -> u32x4 { return part ? ol[s] : oh[s]; },
         [&](int s, int g) {
-          if (SIGMA_ONLY || COMP)
+          if (!TRAIN)
             pending_gap<true>(s, g, pend, ptmp, oh[14], ol[14], oh[15], ol[15], amax);
           else
             pending_gap<false>(s, g, pend, ptmp, bh[14], bl[14], bh[15], bl[15], amax);
@@ -852,9 +905,8 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
           }
         },
         [&](int k, int g) {
-          // sigma_only: the tile ends here, the next chunk is L1 chunk 0 again (bias behind 32 weight pieces); COMP: the
-          // first block of xyz_encoding_final (the same)
-          prefetch_next_chunk(nxt, k, g, ld, (SIGMA_ONLY || COMP) ? 32u * 1024u : next_bias, h);
+          // sigma_only: the tile ends here, the next chunk is L1 chunk 0 again (bias behind 32 weight pieces)
+          prefetch_next_chunk(nxt, k, g, ld, SIGMA_ONLY ? 32u * 1024u : next_bias, h);
         });
     sigma = cur.m[0] * kWInvScale;           // row 0 of the block lives in register 0 of the h == 0 lanes
     pre = nxt;
@@ -871,7 +923,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
 
   float rgb[3] = {0.0f, 0.0f, 0.0f};
   // ---- COMP: is any sample of the workgroup's window live?  (!(sigma <= 0): a NaN density is live.)  If none is, the
-  // window ends here with rgb = 0: the two chunks already under way (xyz_encoding_final's first two blocks) are left to
+  // window ends here with rgb = 0: the two chunks already under way (the folded dir_encoding's first two blocks) are left to
   // land and are discarded, and the ring is restarted on the next window's L1 chunks exactly as the kernel's prologue
   // starts it.  The status word of such a window reports its inputs, its trunk and its density only.
   bool colour = true;
@@ -895,10 +947,9 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     }
   }
   if (colour) {
-  if (COMP) trunk_layer<false, false, false>(8, oh, ol, bh, bl, stash, ld, h, pend, pre, dir_ref(0, wv), dir_ref(1, wv), amax, sbits);
-
   NSR_TL(4);
-  // ---- dir_encoding (cat([g, de]) -> 128, relu) fused with the rgb head (128 -> 3, sigmoid)
+  // ---- dir_encoding (cat([g, de]) -> 128, relu) fused with the rgb head (128 -> 3, sigmoid).  Folded (every kernel but
+  // the TRAIN forward): W' over relu(h8) itself, still intact in oh / ol, instead of dir_encoding's own rows over g in bh / bl
   float2 w2[3];          // colour-head weights of the pair consumed in the next k-step (rgb_gap)
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
@@ -910,16 +961,14 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     // in flight behind the previous block's DMA: the density block's 2 stores | nothing | a dir block's 2 + sign word
     const unsigned a_seq = ld.slot_cur + ld.lane_off;
     // (blocks 2 and 3 fetch nothing, except COMP: the next window's L1 chunks; dead traffic after the last window)
-    const ChunkRef c2 = nb < 2 ? dir_ref(nb + 2, wv) : first_ref(nb - 2, wv);
-    Resplit ptmp;
+    const ChunkRef c2 = nb < 2 ? (TRAIN ? dir_ref(nb + 2, wv) : fdir_ref(nb + 2, wv)) : first_ref(nb - 2, wv);
     auto b_of = [&](int s, int part) -> u32x4 {
-      return (s < 16) ? (part ? bl[s & 15] : bh[s & 15]) : (part ? del[s & 1] : deh[s & 1]);
+      if (s >= 16) return part ? del[s & 1] : deh[s & 1];
+      return TRAIN ? (part ? bl[s & 15] : bh[s & 15]) : (part ? ol[s & 15] : oh[s & 15]);
     };
     auto hook = [&](int s, int g) {
       // the pending dir block is consumed in k-steps 6..13, one pair per k-step, one colour channel per gap
       if (nb > 0) rgb_gap<kConvStep0>(s, g, pend, aux + hx::kAuxRgbW + 32 * (nb - 1), h, rgb, w2);
-      // COMP: xyz_encoding_final's last block (no activation) -> k-steps 14, 15 of this block's own input
-      if (COMP && nb == 0) pending_gap<false>(s, g, pend, ptmp, bh[14], bl[14], bh[15], bl[15], amax);
       if (TRAIN && nb > 0 && s < 8 && g == 1) relu_hi_step(s, pend, dh0, dh1);
       if (TRAIN && nb > 0 && s >= 8 && s < 16 && g == 2) {
         const char* blk = panel_block(tr, 9, nb - 1);

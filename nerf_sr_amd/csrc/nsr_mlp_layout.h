@@ -127,7 +127,7 @@ namespace nsr {
 namespace hx {
 
 constexpr int kChunks = 71;          // 2 (L1) + 24 (L2-4) + 8 (L5) + 24 (L6-8) + 8 (final) + 1 (sigma) + 4 (dir)
-constexpr int kChunkFinal0 = 58;     // first chunk of xyz_encoding_final (skipped by sigma_only launches)
+constexpr int kChunkFinal0 = 58;     // first chunk of xyz_encoding_final (read by the TRAIN forward only: folded elsewhere)
 constexpr int kChunkSigma = 66;      // density head: sigma.weight as row 0 of a 32-row block over h8
 constexpr int kSlotPieces = 41;      // largest chunk: L5, 20 k-steps * 2 + bias
 constexpr int kSlotFloats = kSlotPieces * 256;
@@ -174,6 +174,22 @@ NSR_HD int chunk_of_piece(int piece) {
 }
 // aux (fp32): rgb_w 384 | rgb_b 3
 constexpr int kAuxRgbW = 0, kAuxRgbB = 384, kAuxFloats = 448;
+
+// Folded dir_encoding (every inference kernel; the TRAIN forward keeps the unfolded sequence above).  xyz_encoding_final is
+// a bare Linear whose output feeds dir_encoding alone, so  W' = W_dir[:, :256] W_f  (128 x 256) and  b' = b_dir +
+// W_dir[:, :256] b_f  give  dir_encoding(cat([W_f h8 + b_f, de])) = relu(W' h8 + W_dir[:, 256:] de + b')  with h8 = L8's
+// output.  The blob grows BEHIND the aux block, so that every offset above stays where it was:
+//   pieces kFoldPiece0 ..: four chunks of 37 pieces in dir_encoding's own format (column_of(18, ...): feature columns from
+//                          W', the 27 direction columns from dir_encoding.0.weight[:, 256:], the bias piece from b');
+//   then fp32 W' (row-major 128 x 256) and b' (128): written by the fold kernel, read by the pack kernel behind it.
+// A training step's blobs (nsr_f16x3_pack2) leave the whole region unwritten.
+constexpr int kFoldPiece0 = kPiecesTotal + 2;           // the aux block is 1.75 pieces
+constexpr int kFoldChunkPieces = 37, kFoldPieces = 4 * kFoldChunkPieces;
+constexpr int kFoldW0 = (kFoldPiece0 + kFoldPieces) * 256;     // word offset of W'
+constexpr int kFoldB0 = kFoldW0 + (kWidth / 2) * kWidth;       // word offset of b'
+constexpr int kBlobWords = kFoldB0 + kWidth / 2;
+static_assert(kPiecesTotal * 256 + kAuxFloats <= kFoldPiece0 * 256, "the folded chunks start behind the aux block");
+static_assert(kBlobWords * 4 < (4 << 20) && kBlobWords % 4 == 0, "loader_prepare_dma: the stream is < 4 MiB");
 
 // weight column (or kPad) that register t of lane-half h multiplies in k-step space of `tensor`
 NSR_HD int column_of(int tensor, int s, int j, int h) {

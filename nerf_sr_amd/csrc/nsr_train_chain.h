@@ -13,7 +13,7 @@ extern "C" NSR_INTERNAL int nsr_check_weights_range(const float* const* w, int p
 // dwords of the sign panels (one bit per pre-activation) for P sample points
 extern "C" NSR_INTERNAL int64_t nsr_f16x3_train_sign_words(int64_t P);
 extern "C" NSR_INTERNAL size_t nsr_f16x3_packed_bytes(void);
-extern "C" NSR_INTERNAL int nsr_f16x3_pack(const float* const* w, void* packed_dev, void* stream);
+extern "C" NSR_INTERNAL int nsr_f16x3_pack(const float* const* w, void* packed_dev, float limit, unsigned* tail, void* stream);
 // backward chain: transposed weight stream, then d(rgb_pre) (P, stride) / d(sigma) (P, stride) -> gradient panels;
 // gmax[10] (device): float bits of the largest TRUE magnitude of each gradient panel (zeroed, then atomicMax);
 // pscale (10, ceil(P / 128) * 128): per panel and point the power of two that turns the stored fp16 values into true gradients

@@ -248,7 +248,8 @@ class VanillaMLP:
             self._gamma = False
             raise _lib.NsrNumericsError(
                 f"state_dict cannot be carried at precision {self.precision!r}: a weight or bias is non-finite"
-                + (" or |w| >= 1023.75 (the split-fp16 stream holds 2^6 w in fp16)" if self.precision == "f16x3" else
+                + (" or |w| >= 1023.75 (the split-fp16 stream holds 2^6 w in fp16; so does dir_encoding[:, :256] @ xyz_encoding_final, "
+                   "which the pack folds into one matrix)" if self.precision == "f16x3" else
                    " or |w| >= 65520 (fp16 operands)" if self.precision == "f16" else "")
                 + "; load it with precision='fp32'", 1)
         _lib.check(rc, "nsr_pack_weights")

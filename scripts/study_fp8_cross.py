@@ -34,8 +34,6 @@ sys.path.insert(0, REPO)
 from nerf_sr_amd.weights import make_state_dict  # noqa: E402  (numpy on the host)
 from oracle import nerf_oracle as oc  # noqa: E402  (test infrastructure; this script is a study, not the product)
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-OUT = sys.argv[2] if len(sys.argv) > 2 else None
 _orig_linear = torch.nn.functional.linear
 
 
@@ -83,6 +81,8 @@ def run(mode, sd_c, sd_f, rays, dtype=torch.float32):
 
 
 def main():
+    N = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+    OUT = sys.argv[2] if len(sys.argv) > 2 else None
     from nerf_sr_amd import cameras                    # pure host code (no GPU, no library)
     wh, s = (504, 378), 2
     # the oracle's own ray generator (the product's needs the GPU)
