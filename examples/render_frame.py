@@ -2,6 +2,7 @@
 """Render one supersampled frame with the HIP path and write it as PNGs (needs an MI355X).
 
     python examples/render_frame.py [--checkpoint-dir DIR --name EXP --epoch 30] [--wh 504 378] [--downscale 2] [--out out]
+                                    [--coarse density]
 
 Without a checkpoint the networks are the synthetic "smooth" field of nerf_sr_amd.weights (there is nothing to
 download); with one, `{epoch}_net_Coarse.pth` / `{epoch}_net_Fine.pth` of a NeRF-SR experiment are loaded as the
@@ -34,6 +35,9 @@ def main():
     ap.add_argument("--out", default="frame")
     ap.add_argument("--early-stop", type=float, default=0.0,
                     help="early ray termination at this transmittance (precision f16x3; colours move by at most eps + 2e-6; 0 = off)")
+    ap.add_argument("--coarse", default="rgb", choices=["rgb", "density"],
+                    help="'density': test-time mode -- the coarse pass only feeds the resampler and computes no colours "
+                         "(precision f16x3; the frame is bit-identical)")
     a = ap.parse_args()
     if a.checkpoint_dir:
         pc, pf = io.checkpoint_paths(a.checkpoint_dir, a.name, a.epoch)
@@ -41,7 +45,7 @@ def main():
     else:
         sd_c, sd_f = make_state_dict(99), make_state_dict(100)
     opt = default_options(img_wh=tuple(a.wh), downscale=a.downscale, white_bkgd=False, precision=a.precision,
-                          early_stop=a.early_stop)
+                          early_stop=a.early_stop, coarse_rgb=a.coarse == "rgb")
     model = NeRFDownXModel(opt, device="cuda").load_networks(sd_c, sd_f).eval()
     res = model.render_image(cameras.spiral_pose(a.pose_t), cameras.llff_focal(a.wh[0]), ndc=True)
     torch.cuda.synchronize()

@@ -190,12 +190,37 @@ int nsr_render_rays(const void* packed_dev, int precision, const float* rays, in
 
 /* render_rays followed by VolumetricRenderer.forward (models/nerf_downX_model.py:289-291 and :303-305) in ONE launch: a
  * 128-point tile of the MLP kernel holds whole rays when n_samples is 64 or 128, so the kernel composites them itself
- * and the (R, N, 4) network output need not go to HBM.  raw (R * N, 4) or NULL; comp_rgb (R, 3), depth (R), opacity (R),
+ * and the (R, N, 4) network output need not go to HBM.  NSR_F16X3 walks a group of 4 rays through n_samples / 32 depth
+ * windows and also takes 192 and 256 samples (64 + 128 importance samples, the classic NeRF setting); NSR_FP32 stays at 64
+ * and 128.  raw (R * N, 4) or NULL; comp_rgb (R, 3), depth (R), opacity (R),
  * weights (R, N): any may be NULL.  Results are bit-identical to nsr_render_rays + nsr_composite (the same device code).
  * NSR_ERR_UNSUPPORTED for other sample counts and for the NSR_F16 / NSR_BF16 fast paths (callers fall back to the pair). */
 int nsr_render_rays_composited(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
                                int64_t R, int n_samples, int render_flags, float* raw, float* comp_rgb, float* depth,
                                float* opacity, float* weights, void* stream);
+
+/* ---- test-time mode: a density-only coarse pass (opt-in) -------------------------------
+ * At test time nobody reads the coarse colour: the coarse pass exists to hand its weights to the resampler (the reference
+ * carries `sigma_only` through VanillaMLP.forward and render_rays for this, models/networks.py:182-226).
+ * nsr_render_rays_density is the NSR_F16X3 launch of nsr_render_rays_composited without the colour branch: every depth
+ * window runs the trunk and the density head only (no folded dir_encoding, no colour head, no empty-window vote), then the
+ * rays are composited.  depth (R), opacity (R), weights (R, N) -- any may be NULL -- are bit-identical to the same three
+ * outputs of nsr_render_rays_composited, under the relu and the NSR_SIGMA_SOFTPLUS density alike and whatever the colour
+ * options of the blob.  n_samples: 64, 128, 192 or 256.  The view direction is not an operand: the status word reports
+ * the sample positions, the activation range and a non-finite density.  NSR_ERR_UNSUPPORTED for a precision other than
+ * NSR_F16X3 and for other sample counts; argument checks come before any launch.
+ * nsr_forward_rays_density_coarse takes the arguments of nsr_forward_rays_ert (`events` may be NULL; early_stop == 0 /
+ * windows_cut == NULL: off) and runs the coarse pass through that launch, the fine pass exactly as nsr_forward_rays_ert
+ * does -- outs[1..7] are bit-identical to nsr_forward_rays_ert's.  outs[0] (coarse_comp_rgbs) must be NULL: the buffer
+ * would never be written (NSR_ERR_INVALID_ARG).  n_importance > 0 is required (NSR_ERR_INVALID_ARG): without a fine pass
+ * the coarse colour is the image.  NSR_ERR_UNSUPPORTED for a precision other than NSR_F16X3 or a coarse sample count
+ * outside 64 / 128 / 192 / 256.  Workspace: nsr_forward_rays_workspace_bytes_for, as for the other drivers. */
+int nsr_render_rays_density(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z, int64_t R,
+                            int n_samples, int render_flags, float* depth, float* opacity, float* weights, void* stream);
+int nsr_forward_rays_density_coarse(const void* packed_coarse, const void* packed_fine, int precision, const float* rays,
+                                    int ray_stride, int64_t R, int n_coarse, int n_importance, int render_flags, int lindisp,
+                                    float* const* outs, void* workspace, size_t workspace_bytes, void* stream,
+                                    void* const* events, float early_stop, unsigned* windows_cut);
 
 /* ---- early ray termination (opt-in) ---------------------------------------------------
  * Every NeRF renderer stops a ray once its transmittance is spent; the two entry points below do that for the NSR_F16X3
@@ -263,7 +288,8 @@ int nsr_resample_along_rays(const float* rays, int ray_stride, const float* z, c
  *   4 fine_comp_rgbs  (R,3)   5 fine_depth (R)    6 fine_opacity (R)    7 fine_weights (R,Nc+Ni)
  * n_importance == 0 skips the fine pass (outs[4..7] untouched, packed_fine may be NULL).
  * workspace: device scratch of nsr_forward_rays_workspace_bytes_for(precision, ...) bytes: the depths and the coarse
- * weights, 12 * Nc + 4 * Nf bytes per ray, on the fused route (NSR_FP32 / NSR_F16X3 with 64 or 128 samples per pass: the
+ * weights, 12 * Nc + 4 * Nf bytes per ray, on the fused route (NSR_FP32 / NSR_F16X3 with 64 or 128 samples per pass,
+ * NSR_F16X3 also with 192 or 256: the
  * launch composites its own rays and the (R, N, 4) network output never exists); 16 * (Nc + Nf) bytes per ray more when
  * a pass has to go through nsr_render_rays + nsr_composite.  nsr_forward_rays_workspace_bytes is the precision-agnostic
  * upper bound (always sufficient). */

@@ -56,6 +56,11 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "nsr_render_rays_composited_ert": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_float, c_void_p,
                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nsr_render_rays_density": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "nsr_forward_rays_density_coarse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int,
+                                                POINTER(c_void_p), c_void_p, c_size_t, c_void_p, POINTER(c_void_p), c_float,
+                                                c_void_p]),
     "nsr_composite": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nsr_resample_along_rays": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,

@@ -130,6 +130,8 @@ TEST_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_
 TEST_HOOKS_SRCS = [TEST_HOOKS_SRC, os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_render.hip")]
 # ... and the same launch with early ray termination and both of its counters (tests/test_gpu_early_stop.py)
 TEST_HOOKS_SRCS.append(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_ert.hip"))
+# ... and the render launch's counter at 192 and 256 samples, which the wrapper above refuses (tests/test_gpu_testtime.py)
+TEST_HOOKS_SRCS.append(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_testtime.hip"))
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

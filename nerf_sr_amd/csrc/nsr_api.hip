@@ -24,7 +24,8 @@ static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 // the fused route (D2 + V1 in one launch, nsr_render_rays_composited) exists for these shapes; everything else takes the
 // network launch followed by the stand-alone compositor and needs the (R, N, 4) raw tensors
 static inline bool fused_route(int precision, int n_samples) {
-  return (precision == NSR_FP32 || precision == NSR_F16X3) && (n_samples == 64 || n_samples == 128);
+  if (n_samples == 64 || n_samples == 128) return precision == NSR_FP32 || precision == NSR_F16X3;
+  return precision == NSR_F16X3 && (n_samples == 192 || n_samples == 256);     // the split-fp16 kernel's window loop
 }
 
 // workspace carve: z_coarse (R,Nc) | w_coarse (R,Nc) | z_fine (R,Nf) | [unfused route only: raw_coarse (R,Nc,4) | raw_fine (R,Nf,4)]
@@ -77,12 +78,39 @@ extern "C" int nsr_forward_rays_profiled(const void* packed_coarse, const void* 
                               outs, workspace, workspace_bytes, stream, events, 0.0f, nullptr);
 }
 
+static int forward_rays(bool density_coarse, const void* packed_coarse, const void* packed_fine, int precision, const float* rays,
+                        int ray_stride, int64_t R, int n_coarse, int n_importance, int white_bkgd, int lindisp,
+                        float* const* outs, void* workspace, size_t workspace_bytes, void* stream,
+                        void* const* events, float early_stop, unsigned* windows_cut);
+
 // early_stop > 0: the LAST network pass (the fine one, or the coarse one when n_importance == 0) is launched with early ray
 // termination; the coarse pass that feeds the resampler never is (include/nsr.h)
 extern "C" int nsr_forward_rays_ert(const void* packed_coarse, const void* packed_fine, int precision, const float* rays,
                                     int ray_stride, int64_t R, int n_coarse, int n_importance, int white_bkgd, int lindisp,
                                     float* const* outs, void* workspace, size_t workspace_bytes, void* stream,
                                     void* const* events, float early_stop, unsigned* windows_cut) {
+  return forward_rays(false, packed_coarse, packed_fine, precision, rays, ray_stride, R, n_coarse, n_importance, white_bkgd, lindisp,
+                      outs, workspace, workspace_bytes, stream, events, early_stop, windows_cut);
+}
+
+// test-time mode (include/nsr.h): the coarse pass feeds the resampler only and runs the density-only launch; its colour does
+// not exist, so outs[0] must be null and a fine pass is required.  The fine pass is nsr_forward_rays_ert's.
+extern "C" int nsr_forward_rays_density_coarse(const void* packed_coarse, const void* packed_fine, int precision, const float* rays,
+                                               int ray_stride, int64_t R, int n_coarse, int n_importance, int white_bkgd,
+                                               int lindisp, float* const* outs, void* workspace, size_t workspace_bytes,
+                                               void* stream, void* const* events, float early_stop, unsigned* windows_cut) {
+  if (!outs || outs[0] || n_importance <= 0) return NSR_ERR_INVALID_ARG;
+  if (precision != NSR_F16X3 || !fused_route(precision, n_coarse)) return NSR_ERR_UNSUPPORTED;
+  return forward_rays(true, packed_coarse, packed_fine, precision, rays, ray_stride, R, n_coarse, n_importance, white_bkgd, lindisp,
+                      outs, workspace, workspace_bytes, stream, events, early_stop, windows_cut);
+}
+
+// the one body of the entry points above.  density_coarse: checked by the caller (split fp16, a fused coarse sample count, a
+// fine pass, no coarse colour)
+static int forward_rays(bool density_coarse, const void* packed_coarse, const void* packed_fine, int precision, const float* rays,
+                        int ray_stride, int64_t R, int n_coarse, int n_importance, int white_bkgd, int lindisp,
+                        float* const* outs, void* workspace, size_t workspace_bytes, void* stream,
+                        void* const* events, float early_stop, unsigned* windows_cut) {
   {
     const int erc = nsr_ert_check(early_stop, precision, n_importance > 0 ? n_coarse + n_importance : n_coarse, white_bkgd);
     if (erc != NSR_OK) return erc;
@@ -125,7 +153,9 @@ extern "C" int nsr_forward_rays_ert(const void* packed_coarse, const void* packe
   // are needed by the resampler even if the caller does not want them.
   float* w_c = outs[3] ? outs[3] : w_c_ws;
   mark(0);
-  rc = composited(n_importance == 0, packed_coarse, z_c, n_coarse, outs[0], outs[1], outs[2], w_c);
+  rc = density_coarse ? nsr_render_rays_density(packed_coarse, precision, rays, ray_stride, z_c, R, n_coarse, white_bkgd, outs[1], outs[2],
+                                                w_c, stream)
+                      : composited(n_importance == 0, packed_coarse, z_c, n_coarse, outs[0], outs[1], outs[2], w_c);
   if (rc == NSR_ERR_UNSUPPORTED) {   // other sample counts / the single-operand fast paths: network, then compositor
     rc = nsr_render_rays(packed_coarse, precision, rays, ray_stride, z_c, R, n_coarse, raw_c, stream);
     mark(1);

@@ -544,6 +544,14 @@ extern "C" int nsr_render_rays(const void* packed_dev, int precision, const floa
 /* D2 + V1 in one launch, see include/nsr.h */
 extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const float* rays, int ray_stride, const float* z,
                                                        int64_t R, int N, float* raw, const NsrCompOut* co, unsigned* tail, void* stream);
+extern "C" NSR_INTERNAL int nsr_f16x3_render_density(const void* packed, const float* rays, int ray_stride, const float* z,
+                                                     int64_t R, int N, const NsrCompOut* co, unsigned* tail, void* stream);
+
+// sample counts of the fused launch: 128-point tiles of whole rays (fp32), ray groups walking N / 32 windows (split fp16)
+static inline bool fused_samples(int precision, int n_samples) {
+  if (n_samples == 64 || n_samples == 128) return precision == NSR_FP32 || precision == NSR_F16X3;
+  return precision == NSR_F16X3 && (n_samples == 192 || n_samples == 256);
+}
 
 // the one body of both entry points below: argument checks, then the launch.  ert_tau / cut: early ray termination of the
 // split-fp16 kernel (0 / null: off), already checked by the caller
@@ -553,7 +561,7 @@ static int render_rays_composited(const void* packed_dev, int precision, const f
   if (!packed_dev || R < 0 || n_samples <= 0 || !nsr_ray_stride_ok(ray_stride) || (white_bkgd & ~(NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS)) != 0)
     return NSR_ERR_INVALID_ARG;
   if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
-  if ((precision != NSR_FP32 && precision != NSR_F16X3) || (n_samples != 64 && n_samples != 128)) return NSR_ERR_UNSUPPORTED;
+  if (!fused_samples(precision, n_samples)) return NSR_ERR_UNSUPPORTED;
   if (R == 0) return NSR_OK;
   if (!rays || !z) return NSR_ERR_INVALID_ARG;
   if ((raw && (reinterpret_cast<uintptr_t>(raw) & 15) != 0) || (ray_stride == 8 && (reinterpret_cast<uintptr_t>(rays) & 15) != 0))
@@ -592,4 +600,19 @@ extern "C" int nsr_render_rays_composited_ert(const void* packed_dev, int precis
   return render_rays_composited(packed_dev, precision, rays, ray_stride, z, R, n_samples, render_flags, nullptr, comp_rgb, depth, opacity,
                                 weights, on ? (float)(-log((double)early_stop)) : 0.0f,      // -ln eps in double, rounded once
                                 on ? windows_cut : nullptr, stream);
+}
+
+/* the density-only pass of the same launch (split-fp16 kernel only), see include/nsr.h */
+extern "C" int nsr_render_rays_density(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
+                                       int64_t R, int n_samples, int render_flags, float* depth, float* opacity, float* weights,
+                                       void* stream) {
+  if (!packed_dev || R < 0 || n_samples <= 0 || !nsr_ray_stride_ok(ray_stride) || (render_flags & ~(NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS)) != 0)
+    return NSR_ERR_INVALID_ARG;
+  if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
+  if (precision != NSR_F16X3 || !fused_samples(precision, n_samples)) return NSR_ERR_UNSUPPORTED;
+  if (R == 0) return NSR_OK;
+  if (!rays || !z) return NSR_ERR_INVALID_ARG;
+  if (ray_stride == 8 && (reinterpret_cast<uintptr_t>(rays) & 15) != 0) return NSR_ERR_INVALID_ARG;
+  NsrCompOut co{nullptr, depth, opacity, weights, render_flags};
+  return nsr_f16x3_render_density(packed_dev, rays, ray_stride, z, R, n_samples, &co, nsr_blob_tail(packed_dev, precision), stream);
 }

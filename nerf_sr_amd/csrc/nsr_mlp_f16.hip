@@ -561,6 +561,16 @@ __device__ __forceinline__ void split_direction(const float (&de)[16], u32x4 (&d
 // more often than the 128 samples of whole rays (scripts/empty_tile_stats.py).  The skip is off under the softplus density
 // and when the raw network output is asked for; a NaN density never skips.
 //
+// DENS (COMP with SIGMA_ONLY: nsr_render_rays_density, the coarse pass of nsr_forward_rays_density_coarse): a pass whose colours
+// nobody reads -- it feeds the resampler its weights.  Every window takes SIGMA_ONLY's sequence (L8 -> sigma, nothing behind it)
+// unconditionally: no vote, no vote barrier, no colour chunk is ever fetched.  L8's last block and the density block fetch
+// the next window's L1 chunks 0 and 1 where the colour windows fetch the folded dir_encoding's first two blocks, so the ring
+// reaches the next window's top in the state the prologue (and the last two dir blocks of a colour window) leave it in.  The
+// window's result is (0, 0, 0, sigma); the epilogue composites with comp_rgb = null.  The trunk and the density head run the
+// colour windows' arithmetic, so depth, opacity and weights are bit for bit those of the COMP launch, under either density.
+// The view direction is neither encoded nor range-checked (it is no operand); the status word reports the positions, the
+// activation range and a non-finite sigma.
+//
 // ERT (COMP only, opt-in: nsr_render_rays_composited_ert, "early ray termination" in include/nsr.h): after every window but
 // the last, each wave adds the window's optical depth sum relu(sigma_k) (z_{k+1} - z_k) -- lane 31's delta reaches the next
 // window's first depth -- to a running fp32 scalar, and when every ray present in the group has reached co.ert_tau = -ln eps
@@ -580,8 +590,9 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   // 163,840
   constexpr int kStash0 = 3 * kSlotFloats, kAux0 = kStash0 + 4 * 8 * 256, kComp0 = kAux0 + hx::kAuxFloats;
   __shared__ __attribute__((aligned(16))) float ring[kComp0 + 640];
-  static_assert(!COMP || (MODE == 1 && !SIGMA_ONLY && !TRAIN && (NS == 64 || NS == 128)), "COMP: whole rays of 64 or 128 samples");
-  static_assert(!ERT || COMP, "ERT: an option of the COMP launches");
+  static_assert(!COMP || (MODE == 1 && !TRAIN && (NS == 64 || NS == 128 || NS == 192 || NS == 256)), "COMP: whole rays of 64, 128, 192 or 256 samples");
+  static_assert(!ERT || (COMP && !SIGMA_ONLY && NS <= 128), "ERT: an option of the COMP launches of 64 or 128 samples");
+  constexpr bool DENS = COMP && SIGMA_ONLY;         // the density-only composited pass (see the header)
   constexpr int kWindows = COMP ? NS / 32 : 1;     // COMP: depth windows of a ray group, walked in a loop
   // COMP: the compositor stages in the idle ring after the last window; the first word of the old staging area is the
   // workgroup's vote "some sample of this window is live"
@@ -644,6 +655,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   NsrRay ray_q{};
   if (COMP) {
     ray_q = nsr_load_ray(x, my_ray_c, stride);
+    if (!DENS) {     // DENS: the view direction is no operand of the trunk or the density head
     bool ok = true;
 #pragma unroll
     for (int c = 0; c < 3; ++c) ok = ok && fabsf(ray_q.v[c]) <= 65504.0f;
@@ -651,6 +663,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     float de[16];
     encode_direction(ray_q.v, h, de);
     split_direction(de, deh, del);
+    }
   }
   float tau = 0.0f;                                                    // ERT: this wave's optical depth so far
   if (ERT) {
@@ -671,7 +684,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   }
   const int64_t p = COMP ? (my_ray < n_rays ? my_ray * NS + win * 32 + m : P) : tile * 128 + wv * 32 + m;
   const int64_t pc = COMP ? my_ray_c * NS + win * 32 + m : (p < P ? p : P - 1);
-  if (COMP && threadIdx.x == 0) *vote = 0u;                            // published by the barrier below
+  if (COMP && !DENS && threadIdx.x == 0) *vote = 0u;                            // published by the barrier below
   PanelRef tr{};
   if (TRAIN) {
     tr.base = reinterpret_cast<char*>(pan);
@@ -912,7 +925,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     pre = nxt;
     loader_advance(ld);
   }
-  if (SIGMA_ONLY) {
+  if (SIGMA_ONLY && !COMP) {
     if (h == 0 && p < P) out[p] = sigma;
     if (amax >= 65520.0f) flags |= NSR_FLAG_ACTIVATION_RANGE;
     if (!nsr_finite(sigma)) flags |= NSR_FLAG_OUTPUT_NONFINITE;
@@ -926,8 +939,8 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   // window ends here with rgb = 0: the two chunks already under way (the folded dir_encoding's first two blocks) are left to
   // land and are discarded, and the ring is restarted on the next window's L1 chunks exactly as the kernel's prologue
   // starts it.  The status word of such a window reports its inputs, its trunk and its density only.
-  bool colour = true;
-  if (COMP && skip_on) {
+  bool colour = !DENS;   // DENS: every window ends behind the density head, with nothing to vote on and nothing to discard
+  if (COMP && !DENS && skip_on) {
     const bool live = h == 0 && p < P && !(sigma <= 0.0f);
     if (__ballot(live) != 0ull && lane == 0) *vote = 1u;
     __syncthreads();
@@ -1067,8 +1080,8 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     }
     __syncthreads();
     if (my_ray < n_rays)
-      composite_ray<(COMP ? NS / 64 : 1)>(mine, 4, mine + 3, 4, zv + my_ray * NS, NS, co.white, lane, my_ray, co.comp_rgb, co.depth,
-                                          co.opacity, co.weights);
+      composite_ray<(COMP ? NS / 64 : 1)>(mine, 4, mine + 3, 4, zv + my_ray * NS, NS, co.white, lane, my_ray, DENS ? nullptr : co.comp_rgb,
+                                          co.depth, co.opacity, co.weights);
   }
 #ifdef NSR_ABL_TIMELINE
   NSR_TL(7);
@@ -1107,7 +1120,14 @@ extern "C" NSR_INTERNAL int nsr_f16x3_mlp_forward(const void* packed, const floa
                     : launch_f16x3<0, false>(packed, x, nullptr, P, 1, 8, out, tail, nsr_stream(stream));
 }
 
-// render_rays + VolumetricRenderer.forward in one launch (n_samples 64 or 128); raw (R * N, 4) optional
+// six and eight windows per ray group.  Defined at the end of the unit, like everything instantiated after the measured builds:
+// kernels are emitted in the order of their first use, and a kernel's position is part of its listing (block labels), so
+// the listings of the instantiations above stay byte for byte what they were
+static int launch_comp_wide(const float* pk, const float* rays, int ray_stride, const float* z, int64_t R, int N, float* raw,
+                            const NsrCompOut& co, NsrTail tail, hipStream_t st);
+
+// render_rays + VolumetricRenderer.forward in one launch (n_samples 64, 128, 192 or 256; early ray termination: 64 or 128);
+// raw (R * N, 4) optional
 extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const float* rays, int ray_stride, const float* z,
                                                        int64_t R, int N, float* raw, const NsrCompOut* co, unsigned* tail_w,
                                                        void* stream) {
@@ -1120,6 +1140,8 @@ extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const
     hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 64, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
   else if (N == 128 && !ert)
     hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 128, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
+  else if ((N == 192 || N == 256) && !ert)
+    return launch_comp_wide(pk, rays, ray_stride, z, R, N, raw, *co, tail, nsr_stream(stream));
   else if (N == 64)
     hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 64, true, false, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
   else if (N == 128)
@@ -1150,4 +1172,38 @@ extern "C" NSR_INTERNAL int nsr_f16x3_train_forward(const void* packed, const fl
 extern "C" NSR_INTERNAL int nsr_f16x3_render_rays(const void* packed, const float* rays, int ray_stride, const float* z, int64_t R,
                                      int N, float* out, unsigned* tail, void* stream) {
   return launch_f16x3<1, false>(packed, rays, z, R * N, N, ray_stride, out, tail, nsr_stream(stream));
+}
+
+static int launch_comp_wide(const float* pk, const float* rays, int ray_stride, const float* z, int64_t R, int N, float* raw,
+                            const NsrCompOut& co, NsrTail tail, hipStream_t st) {
+  const int64_t P = R * N;
+  const dim3 grid((unsigned)((R + 3) / 4)), block(256);
+  if (N == 192)
+    hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 192, true>), grid, block, 0, st, pk, rays, z, P, N, ray_stride, raw, tail, co);
+  else
+    hipLaunchKernelGGL((mlp_f16x3_kernel<1, false, 256, true>), grid, block, 0, st, pk, rays, z, P, N, ray_stride, raw, tail, co);
+  if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
+  return NSR_OK;
+}
+
+// the density-only composited pass (DENS): trunk + density head in every window, then depth / opacity / weights; no colours
+extern "C" NSR_INTERNAL int nsr_f16x3_render_density(const void* packed, const float* rays, int ray_stride, const float* z,
+                                                     int64_t R, int N, const NsrCompOut* co, unsigned* tail_w, void* stream) {
+  const NsrTail tail{tail_w};
+  const int64_t P = R * N;
+  const dim3 grid((unsigned)((R + 3) / 4)), block(256);
+  const float* pk = static_cast<const float*>(packed);
+  float* const raw = nullptr;
+  if (N == 64)
+    hipLaunchKernelGGL((mlp_f16x3_kernel<1, true, 64, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
+  else if (N == 128)
+    hipLaunchKernelGGL((mlp_f16x3_kernel<1, true, 128, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
+  else if (N == 192)
+    hipLaunchKernelGGL((mlp_f16x3_kernel<1, true, 192, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
+  else if (N == 256)
+    hipLaunchKernelGGL((mlp_f16x3_kernel<1, true, 256, true>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, tail, *co);
+  else
+    return NSR_ERR_UNSUPPORTED;
+  if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
+  return NSR_OK;
 }

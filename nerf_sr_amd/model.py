@@ -29,6 +29,7 @@ def default_options(**kw) -> SimpleNamespace:
         ray_chunk=4096, point_chunk=262144, precision="fp32",
         check_numerics=True,    # forward() raises on NaN / out-of-range values (the reference: pdb, nerf_downX_model.py:273-274)
         early_stop=0.0,         # eval mode, precision 'f16x3': early ray termination at this transmittance (0 = off; include/nsr.h)
+        coarse_rgb=True,        # False: test-time mode, eval + 'f16x3' -- the coarse pass computes densities only (include/nsr.h)
     )
     for k, v in kw.items():
         setattr(opt, k, v)
@@ -46,6 +47,7 @@ class NeRFDownXModel:
             raise ValueError("N_coarse must be >= 2 and N_importance >= 0")
         self.renderer = VolumetricRenderer(self.opt)      # validates sigma_activation before any device is touched
         self._check_early_stop()                          # ... and the early-termination option with its restrictions
+        self._check_coarse_rgb()                          # ... and the test-time mode with its own
         self.device = torch.device(device)
         # the fused kernels for the architecture every script of the reference uses, nn.Linear by nn.Linear for any other
         self.netCoarse = ops.make_mlp(self.opt, precision=self.opt.precision, device=self.device)
@@ -88,6 +90,24 @@ class NeRFDownXModel:
             raise ValueError("early_stop needs the architecture of the fused kernels (8 x 256, skip at 4, degrees 10 / 4)")
         return eps
 
+    def _check_coarse_rgb(self, coarse_rgb: Optional[bool] = None) -> bool:
+        """``opt.coarse_rgb`` (or the per-call override) checked against the options the density-only coarse pass depends on,
+        before any device is touched; ``ops.check_density_coarse`` repeats the check on the networks at every call.  Read
+        from ``opt`` at call time, like ``early_stop``: a later ``model.opt.coarse_rgb = False`` takes effect or raises."""
+        opt = self.opt
+        on = bool(getattr(opt, "coarse_rgb", True)) if coarse_rgb is None else bool(coarse_rgb)
+        if on:
+            return True
+        if opt.precision != "f16x3":
+            raise ValueError(f"coarse_rgb=False needs precision 'f16x3' (the split-fp16 render kernel), not {opt.precision!r}")
+        if int(opt.N_importance) <= 0:
+            raise ValueError("coarse_rgb=False needs a fine pass (N_importance > 0): without one the coarse colour is the image")
+        if int(opt.N_coarse) not in ops.FUSED_SAMPLES_F16X3:
+            raise ValueError(f"coarse_rgb=False needs N_coarse of 64, 128, 192 or 256, not {int(opt.N_coarse)}")
+        if not ops.is_default_arch(ops.arch_of(opt)):
+            raise ValueError("coarse_rgb=False needs the architecture of the fused kernels (8 x 256, skip at 4, degrees 10 / 4)")
+        return False
+
     # -- mode toggles (nerf_downX_model.py:250-258) ------------------------------
     def train(self):
         self.randomized = bool(self.opt.randomized)
@@ -119,14 +139,20 @@ class NeRFDownXModel:
         return rgb, out[..., 3]
 
     # -- D3 ------------------------------------------------------------------------
-    def forward_rays(self, rays: torch.Tensor) -> Dict[str, torch.Tensor]:
-        """``opt.early_stop`` applies to the eval-mode forward only (the fine pass, include/nsr.h); ``train()`` mode ignores it."""
+    def forward_rays(self, rays: torch.Tensor, coarse_rgb: Optional[bool] = None) -> Dict[str, torch.Tensor]:
+        """``opt.early_stop`` applies to the eval-mode forward only (the fine pass, include/nsr.h); ``train()`` mode ignores it.
+        ``coarse_rgb`` (default: ``opt.coarse_rgb``) False is the test-time mode: eval only, no ``coarse_comp_rgbs`` in the
+        result; the randomized forward needs the coarse colour for its loss and raises."""
         opt = self.opt
+        with_rgb = self._check_coarse_rgb(coarse_rgb)
+        if not with_rgb and self.randomized:
+            raise ValueError("coarse_rgb=False is a test-time mode: the randomized (train()) forward feeds the coarse colour to its loss")
         if not self.randomized and self.fused:
             self._outs = ops.forward_rays(self.netCoarse, self.netFine if opt.N_importance > 0 else None, rays,
                                           opt.N_coarse, opt.N_importance, opt.white_bkgd, opt.lindisp,
                                           check=bool(getattr(opt, "check_numerics", True)),
-                                          sigma_activation=self.renderer.sigma_activation, early_stop=self._check_early_stop())
+                                          sigma_activation=self.renderer.sigma_activation, early_stop=self._check_early_stop(),
+                                          coarse_rgb=with_rgb)
             return self._outs
         # randomized (training-mode) forward, and every forward of a GenericMLP pair: same kernels, stage by stage, jitter
         # drawn with torch.rand
@@ -154,15 +180,21 @@ class NeRFDownXModel:
                 self.netFine.check("fine network")
         return out
 
-    def forward(self):
-        out = self.forward_rays(self.data_rays)
+    def forward(self, coarse_rgb: Optional[bool] = None):
+        """With ``coarse_rgb`` False (default: ``opt.coarse_rgb``) ``out_coarse_comp_rgbs`` is not set -- and one left by an
+        earlier forward is removed: the reference's loops test the ``out_*`` attributes with ``hasattr``."""
+        out = self.forward_rays(self.data_rays, coarse_rgb)
+        for name in ("out_coarse_comp_rgbs", "out_coarse_comp_rgbs_ori"):
+            if "coarse_comp_rgbs" not in out and hasattr(self, name):
+                delattr(self, name)
         for name, v in out.items():
             setattr(self, f"out_{name}", v)
 
     # -- A1 / A2 ---------------------------------------------------------------------
     def comp_low_res_output(self):
         s2 = self.opt.downscale ** 2
-        n_lr = self.data_rgbs.shape[0] if hasattr(self, "data_rgbs") else self.out_coarse_comp_rgbs.shape[0] // s2
+        any_out = self.out_coarse_comp_rgbs if hasattr(self, "out_coarse_comp_rgbs") else self.out_fine_comp_rgbs
+        n_lr = self.data_rgbs.shape[0] if hasattr(self, "data_rgbs") else any_out.shape[0] // s2
         for name in ("coarse_comp_rgbs", "coarse_depth", "fine_comp_rgbs", "fine_depth"):
             if hasattr(self, f"out_{name}"):
                 hr = getattr(self, f"out_{name}")
@@ -179,6 +211,9 @@ class NeRFDownXModel:
         ``data_rgbs_ori`` is set, of the rendered rays against it -- each a 0-d fp32 device tensor out of ``nsr_psnr`` (sums in
         double, no host read).  Like the reference's, it reduces the ``out_*`` of ONE ``forward()``: call it once per forward."""
         from . import metrics
+        if not hasattr(self, "out_coarse_comp_rgbs"):
+            raise ValueError("calculate_losses scores the coarse colour, which the last forward() did not compute: "
+                             "coarse_rgb=False (opt.coarse_rgb) is a test-time mode -- score with coarse_rgb=True")
         self.comp_low_res_output()
         fine = hasattr(self, "out_fine_comp_rgbs")
         mse_c, psnr_c = metrics.mse_psnr(self.out_coarse_comp_rgbs, self.data_rgbs)
@@ -228,6 +263,8 @@ class NeRFDownXModel:
         for k in names[2:]:
             if hasattr(self, k):
                 delattr(self, k)
+        if not bool(getattr(self.opt, "coarse_rgb", True)):
+            raise ValueError("validate scores the coarse colour: opt.coarse_rgb=False is a test-time mode -- validate with coarse_rgb=True")
         was, self.randomized = self.randomized, False
         sums, n = {}, 0
         try:
@@ -254,18 +291,20 @@ class NeRFDownXModel:
 
     # -- full image (test loop body, nerf_downX_model.py:621-669 without the savers) -----
     @torch.no_grad()
-    def render_image(self, c2w, focal: float, ndc: bool, near: float = 0.0, far: float = 1.0):
-        """Rays generated on the device -> forward -> LR means + HR image of one pose."""
+    def render_image(self, c2w, focal: float, ndc: bool, near: float = 0.0, far: float = 1.0, coarse_rgb: Optional[bool] = None):
+        """Rays generated on the device -> forward -> LR means + HR image of one pose.  ``coarse_rgb`` (default:
+        ``opt.coarse_rgb``) False: the coarse pass computes densities only; the frame is bit-identical."""
         rays = ops.subpixel_rays(c2w, self.opt.img_wh, focal, self.opt.downscale, ndc, near, far, self.device)
         self.set_input({"rays": rays})
-        self.forward()
+        self.forward(coarse_rgb)
         hr = self.unflatten_reshape(self.out_fine_comp_rgbs)
         self.comp_low_res_output()
         return {"hr_rgb": hr, "lr_rgb": self.out_fine_comp_rgbs, "lr_depth": self.out_fine_depth}
 
     @torch.no_grad()
     def render_image_sharded(self, c2w, focal: float, ndc: bool, near: float = 0.0, far: float = 1.0, group=None,
-                             lr_range=None, workspace=None, outs=None, gather: str = "lr", want_weights: bool = False):
+                             lr_range=None, workspace=None, outs=None, gather: str = "lr", want_weights: bool = False,
+                             coarse_rgb: Optional[bool] = None):
         """One frame rendered by all ranks of ``group`` together (BASELINE config #4): the LR-pixel range
         is cut into contiguous blocks (``dist.shard_bounds``; an LR pixel's s*s sub-rays stay on one GPU), every rank
         GENERATES its own ray block on its device (nothing is scattered), runs the eval-mode ``forward_rays`` on it, and
@@ -287,12 +326,15 @@ class NeRFDownXModel:
         ``want_weights`` (default False): a frame render does not use the per-sample ``weights`` arrays of the reference's
         8-entry dict; leaving them out saves 195 of the 261 MB the fine-pass launch moves through HBM on config #2
         (``forward_rays`` itself, the drop-in for the reference's method, still returns all eight).
+        ``coarse_rgb`` (default: ``opt.coarse_rgb``) False: the density-only coarse pass (same frame, bit for bit); it needs a
+        fine pass and the fused f16x3 networks.
         ``lr_range`` overrides this rank's block and skips the collective (single-process tests).  Returns the assembled
         arrays plus this rank's own outputs (``local``) and ``bytes_per_rank`` (payload of the collective)."""
         from . import dist as nsr_dist
         if gather not in ("lr", "hr"):
             raise ValueError("gather must be 'lr' or 'hr'")
         opt = self.opt
+        with_rgb = self._check_coarse_rgb(coarse_rgb)
         s, s2 = int(opt.downscale), int(opt.downscale) ** 2
         n_lr = (opt.img_wh[1] // s) * (opt.img_wh[0] // s)
         rank, world = nsr_dist._world(group)
@@ -302,11 +344,12 @@ class NeRFDownXModel:
         if self.fused:
             out = ops.forward_rays(self.netCoarse, self.netFine if fine else None, rays, opt.N_coarse, opt.N_importance,
                                    opt.white_bkgd, opt.lindisp, workspace=workspace, outs=outs, want_weights=want_weights,
-                                   sigma_activation=self.renderer.sigma_activation, early_stop=self._check_early_stop())
+                                   sigma_activation=self.renderer.sigma_activation, early_stop=self._check_early_stop(),
+                                   coarse_rgb=with_rgb)
         else:               # a GenericMLP pair: the eval-mode staged route
             was, self.randomized = self.randomized, False
             try:
-                out = self.forward_rays(rays)
+                out = self.forward_rays(rays, with_rgb)
             finally:
                 self.randomized = was
         tag = "fine" if fine else "coarse"

@@ -572,7 +572,7 @@ def render_rays_composited(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.
                            want_raw: bool = False, sigma_activation: str = "relu", early_stop: float = 0.0,
                            want_cut_count: bool = False):
     """``render_rays`` + ``VolumetricRenderer.forward`` in one launch (models/nerf_downX_model.py:289-291): 64 or 128
-    samples per ray, fp32 / f16x3.  Returns ``(comp_rgb (R,3), depth (R), opacity (R), weights (R,N))`` and, if
+    samples per ray, fp32 / f16x3; f16x3 also 192 or 256.  Returns ``(comp_rgb (R,3), depth (R), opacity (R), weights (R,N))`` and, if
     ``want_raw``, the (R, N, 4) network output as a fifth element.  Bit-identical to the two-call route.
 
     ``early_stop`` = eps > 0 (f16x3 only): early ray termination -- a group of four consecutive rays stops after a 32-sample
@@ -603,6 +603,39 @@ def render_rays_composited(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.
     return res + (cut,) if want_cut_count else res
 
 
+FUSED_SAMPLES_F16X3 = (64, 128, 192, 256)     # sample counts of the split-fp16 render + composite launch (include/nsr.h)
+
+
+def check_density_coarse(net, n_coarse: int, n_importance: Optional[int] = None) -> None:
+    """Validates the test-time mode (``coarse_rgb=False`` / ``render_rays_density``): a ``ValueError`` names the condition
+    that fails -- the option is never ignored silently.  ``n_importance`` None: a direct density launch (no fine pass)."""
+    if not isinstance(net, VanillaMLP) or net.precision != "f16x3":
+        raise ValueError(f"coarse_rgb=False (the density-only pass) needs precision 'f16x3' (the split-fp16 render kernel), "
+                         f"not {getattr(net, 'precision', None)!r}")
+    if int(n_coarse) not in FUSED_SAMPLES_F16X3:
+        raise ValueError(f"coarse_rgb=False (the density-only pass) needs 64, 128, 192 or 256 samples per ray, not {int(n_coarse)}")
+    if n_importance is not None and int(n_importance) <= 0:
+        raise ValueError("coarse_rgb=False needs a fine pass (N_importance > 0): without one the coarse colour is the image")
+
+
+def render_rays_density(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.Tensor, sigma_activation: str = "relu"):
+    """The density-only pass of ``render_rays_composited`` (f16x3; 64, 128, 192 or 256 samples per ray): trunk and density
+    head at every sample, no colour branch, then compositing.  Returns ``(depth (R), opacity (R), weights (R, N))``,
+    bit-identical to the same three outputs of ``render_rays_composited`` under either density: what a coarse pass that only
+    feeds the resampler needs (the reference's ``sigma_only``, models/networks.py:182-226)."""
+    rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
+    R, N = z_vals.shape
+    dev = rays.device
+    check_density_coarse(model, N)
+    flags = renderer_flags(False, sigma_activation)
+    depth = torch.empty(R, dtype=torch.float32, device=dev)
+    opac = torch.empty(R, dtype=torch.float32, device=dev)
+    w = torch.empty(R, N, dtype=torch.float32, device=dev)
+    _lib.check(_lib.load().nsr_render_rays_density(_p(model.packed), model._prec, _p(rays), _ray_stride(rays), _p(z_vals), R, N, flags,
+                                                   _p(depth), _p(opac), _p(w), _stream()), "nsr_render_rays_density")
+    return depth, opac, w
+
+
 OUT_KEYS = ("coarse_comp_rgbs", "coarse_depth", "coarse_opacity", "coarse_weights",
             "fine_comp_rgbs", "fine_depth", "fine_opacity", "fine_weights")
 
@@ -612,7 +645,7 @@ def forward_rays(coarse: VanillaMLP, fine: Optional[VanillaMLP], rays: torch.Ten
                  workspace: Optional[torch.Tensor] = None, outs: Optional[Dict[str, torch.Tensor]] = None,
                  want_weights: bool = True, events=None, check: bool = False,
                  sigma_activation: str = "relu", early_stop: float = 0.0,
-                 cut_count: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                 cut_count: Optional[torch.Tensor] = None, coarse_rgb: bool = True) -> Dict[str, torch.Tensor]:
     """Eval-mode forward_rays for the WHOLE batch in one enqueue sequence
     (models/nerf_downX_model.py:280-324; with 11-wide rays: the vanilla model's models/nerf_model.py:207-242):
     returns the reference's 8-entry dict.
@@ -624,7 +657,12 @@ def forward_rays(coarse: VanillaMLP, fine: Optional[VanillaMLP], rays: torch.Ten
     ``net.check()`` / ``net.status()`` (nothing is synchronised).
     ``early_stop`` = eps > 0 (f16x3 only): early ray termination in the LAST network pass (the fine one, or the coarse one when
     ``N_importance == 0``; the coarse pass that feeds the resampler is never cut), see ``render_rays_composited`` and
-    include/nsr.h; ``cut_count``: a 1-element int32 device tensor the launch ADDS the number of windows not run to."""
+    include/nsr.h; ``cut_count``: a 1-element int32 device tensor the launch ADDS the number of windows not run to.
+    ``coarse_rgb=False`` (f16x3, ``N_importance > 0``, ``N_coarse`` 64 / 128 / 192 / 256): test-time mode -- the coarse pass
+    runs the density-only launch (``render_rays_density``); the returned dict has no ``coarse_comp_rgbs`` (a caller's
+    ``outs["coarse_comp_rgbs"]`` is neither read nor written) and the seven other outputs are bit-identical."""
+    if not coarse_rgb:
+        check_density_coarse(coarse, N_coarse, N_importance)
     lib = _lib.load()
     rays = _f32(rays, "rays")
     rays = rays.reshape(-1, rays.shape[-1])
@@ -648,16 +686,19 @@ def forward_rays(coarse: VanillaMLP, fine: Optional[VanillaMLP], rays: torch.Ten
         outs = {}
     keys = OUT_KEYS if N_importance > 0 else OUT_KEYS[:4]
     for k in keys:
-        if k.endswith("weights") and not want_weights:
+        if (k.endswith("weights") and not want_weights) or (k == "coarse_comp_rgbs" and not coarse_rgb):
             continue
         if k not in outs or tuple(outs[k].shape) != shapes[k]:
             outs[k] = torch.empty(shapes[k], dtype=torch.float32, device=dev)
-    ptrs = (c_void_p * 8)(*[_p(outs.get(k)) for k in OUT_KEYS])
+    ptrs = (c_void_p * 8)(*[_p(outs.get(k)) if (coarse_rgb or k != "coarse_comp_rgbs") else c_void_p(0) for k in OUT_KEYS])
     ev = (c_void_p * 4)(*events) if events is not None else None
     args = (_p(coarse.packed), _p(fine.packed) if fine is not None else c_void_p(0), coarse._prec, _p(rays), stride, R, N_coarse,
             N_importance, renderer_flags(white_bkgd, sigma_activation), int(bool(lindisp)), ptrs, _p(workspace), workspace.numel(),
             _stream(), ev)
-    if eps > 0.0:
+    if not coarse_rgb:
+        _lib.check(lib.nsr_forward_rays_density_coarse(*args, eps, _p(cut_count) if eps > 0.0 else c_void_p(0)),
+                   "nsr_forward_rays_density_coarse")
+    elif eps > 0.0:
         _lib.check(lib.nsr_forward_rays_ert(*args, eps, _p(cut_count)), "nsr_forward_rays_ert")
     else:
         _lib.check(lib.nsr_forward_rays_profiled(*args), "nsr_forward_rays")
@@ -665,6 +706,8 @@ def forward_rays(coarse: VanillaMLP, fine: Optional[VanillaMLP], rays: torch.Ten
         coarse.check("coarse network")
         if fine is not None and N_importance > 0:
             fine.check("fine network")
+    if not coarse_rgb:     # the reference's dict minus the entry that was not computed (a caller's buffer stays the caller's)
+        return {k: v for k, v in outs.items() if k != "coarse_comp_rgbs"}
     return outs
 
 

@@ -36,7 +36,7 @@ def world_to_camera(c2w) -> np.ndarray:
 def render_warp_refine(model: NeRFDownXModel, net: refine.MaxPoolingModel, c2w, ref_c2w, ref_img: torch.Tensor,
                        focal: float, ndc: bool, near: float = 0.0, far: float = 1.0, patch_len: int = 64,
                        num_ref_patches: int = 8, batch: int = 32, events: Optional[list] = None,
-                       depth_kind: Optional[str] = None) -> Dict[str, torch.Tensor]:
+                       depth_kind: Optional[str] = None, coarse_rgb: Optional[bool] = None) -> Dict[str, torch.Tensor]:
     """One synthesised view through the whole of config #5.
 
     ``model``: the render path with its two networks loaded; ``net``: the refinement network; ``c2w``: pose of the
@@ -47,13 +47,15 @@ def render_warp_refine(model: NeRFDownXModel, net: refine.MaxPoolingModel, c2w, 
     ``'ray'`` (distance along the unit-norm ray: this build's definition for Blender scenes) otherwise; pass ``'metric'``
     to use the depth as it is, which is what the reference's ``warp.py:120-126`` does for ``spheric_poses`` LLFF scenes
     (needed to reproduce its ``{i}_locs.npz`` there).
+    ``coarse_rgb`` (default: ``model.opt.coarse_rgb``) False renders with the density-only coarse pass (test-time mode of
+    ``NeRFDownXModel.render_image``: same frame and depth, bit for bit).
     Returns the HR render (H, W, 3), the HR depth map (H, W), ``locs`` (H, W, 3) float64 and the refined image
     (3, H, W) in [0, 1]."""
     def mark(i):
         if events is not None:
             events[i].record()
     mark(0)
-    res = model.render_image(c2w, focal, ndc, near, far)
+    res = model.render_image(c2w, focal, ndc, near, far, coarse_rgb=coarse_rgb)
     depth_hw = model.unflatten_reshape(model.out_fine_depth_ori.reshape(-1, 1))[..., 0].contiguous()   # {i}-fine-depth-ori
     mark(1)
     if depth_kind is None:
