@@ -35,6 +35,18 @@ class NsrArch(ctypes.Structure):
     _fields_ = [("D", c_int), ("W", c_int), ("skips", c_uint), ("deg_pos", c_int), ("deg_dir", c_int), ("no_dir", c_int)]
 
 
+class NsrRayset(ctypes.Structure):
+    """``struct nsr_rayset`` (include/nsr_data.h): a scene as device pointers -- poses, 8-bit images, LR-pixel window."""
+    _fields_ = [("poses", c_void_p), ("n_views", c_int), ("H", c_int), ("W", c_int), ("s", c_int), ("focal", c_double),
+                ("ndc", c_int), ("near_", c_float), ("far_", c_float), ("options", c_uint),
+                ("x0", c_int), ("y0", c_int), ("w", c_int), ("h", c_int), ("hr", c_void_p), ("lr", c_void_p),
+                ("C", c_int), ("lr_mode", c_int), ("patch_w", c_int)]
+
+
+NSR_RAYS_NO_PIXEL_CENTERS, NSR_RAYS_UNIFIED_DIR = 1, 2     # include/nsr_data.h: option word of the ray directions
+NSR_LR_FROM_IMAGES, NSR_LR_MEAN_OF_HR = 0, 1               # include/nsr_data.h: where the LR targets come from
+NSR_FLAG_INPUT_RANGE = 2
+
 # symbol -> (restype, argtypes); must list every function of include/*.h
 SIGNATURES = {
     "nsr_version": (c_int, []),
@@ -146,6 +158,10 @@ SIGNATURES = {
     "nsr_split_weights": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "nsr_linear_f16x3": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_int,
                                  c_void_p]),
+    # ---- include/nsr_data.h
+    "nsr_rayset_batch": (c_int, [POINTER(NsrRayset), c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nsr_gen_rays_opt": (c_int, [POINTER(c_float), c_int, c_int, c_double, c_int, c_int, c_float, c_float, c_uint, c_int64, c_int64,
+                                 c_void_p, c_void_p]),
     # ---- include/nsr_metrics.h
     "nsr_ssim_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "nsr_ssim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_double, c_double,

@@ -3,17 +3,17 @@
 // and the HR un-flatten (A2).  All HBM-bound elementwise kernels: one thread per
 // output element / ray, coalesced stores, fp32 arithmetic in the reference's
 // operation order (compiled with -ffp-contract=off).
+#include <math.h>
 #include "nsr_common.h"
+#include "nsr_raygen.h"
+#include "../../include/nsr_data.h"
 
 // ---------------------------------------------------------------------------
 // R1-R4  (reference: models/utils.py:98-196, data/llff_downX_dataset.py:473-490)
 // ---------------------------------------------------------------------------
 struct GenRaysArgs {
   float c2w[12];
-  int H, W, s, ndc;
-  float focal, half_w, half_h;   // W/2, H/2 as fp32
-  float ndc_ax, ndc_ay;          // -1/(W/(2f)), -1/(H/(2f)) evaluated in double on the host
-  float near_, far_;
+  NsrRayCam cam;
 };
 
 // rays of the LR pixels [lr0, lr0 + n_rays / s^2): output row r holds ray  lr0 * s^2 + r  of the frame
@@ -21,45 +21,16 @@ __global__ void __launch_bounds__(256) gen_rays_kernel(GenRaysArgs a, float* __r
                                                        int64_t n_rays) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_rays) return;
-  const int s = a.s, s2 = s * s, w_lr = a.W / s;
+  const int s = a.cam.s, s2 = s * s, w_lr = a.cam.W / s;
   const int64_t lr = lr0 + r / s2;
   const int sub = (int)(r % s2);
   const int py = (int)(lr / w_lr) * s + sub / s;   // HR row  (h s1)
   const int px = (int)(lr % w_lr) * s + sub % s;   // HR col  (w s2)
-  // camera-space direction through the pixel centre
-  const float cx = __fdiv_rn(__fsub_rn((float)px + 0.5f, a.half_w), a.focal);
-  const float cy = -__fdiv_rn(__fsub_rn((float)py + 0.5f, a.half_h), a.focal);
-  const float cz = -1.0f;
-  // rotate into the world frame, normalise
-  float d[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-    d[k] = fmaf(cz, a.c2w[4 * k + 2], fmaf(cy, a.c2w[4 * k + 1], __fmul_rn(cx, a.c2w[4 * k + 0])));
-  const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
-  d[0] = __fdiv_rn(d[0], nrm); d[1] = __fdiv_rn(d[1], nrm); d[2] = __fdiv_rn(d[2], nrm);
-  float o[3] = {a.c2w[3], a.c2w[7], a.c2w[11]};
-  float nr = a.near_, fr = a.far_;
-  if (a.ndc) {
-    // shift the origin to the near plane (near = 1.0), then project
-    const float t = __fdiv_rn(-__fadd_rn(1.0f, o[2]), d[2]);
-    o[0] = __fadd_rn(o[0], __fmul_rn(t, d[0]));
-    o[1] = __fadd_rn(o[1], __fmul_rn(t, d[1]));
-    o[2] = __fadd_rn(o[2], __fmul_rn(t, d[2]));
-    const float ox_oz = __fdiv_rn(o[0], o[2]);
-    const float oy_oz = __fdiv_rn(o[1], o[2]);
-    const float o0 = __fmul_rn(a.ndc_ax, ox_oz);
-    const float o1 = __fmul_rn(a.ndc_ay, oy_oz);
-    const float o2 = __fadd_rn(1.0f, __fdiv_rn(2.0f, o[2]));
-    const float d0 = __fmul_rn(a.ndc_ax, __fsub_rn(__fdiv_rn(d[0], d[2]), ox_oz));
-    const float d1 = __fmul_rn(a.ndc_ay, __fsub_rn(__fdiv_rn(d[1], d[2]), oy_oz));
-    const float d2 = __fsub_rn(1.0f, o2);
-    o[0] = o0; o[1] = o1; o[2] = o2;
-    d[0] = d0; d[1] = d1; d[2] = d2;
-    nr = 0.0f; fr = 1.0f;
-  }
+  float4 q0, q1;
+  nsr_raygen_pixel(a.cam, a.c2w, px, py, q0, q1);   // nsr_raygen.h: shared with the batch kernel of nsr_data.hip
   float4* out = reinterpret_cast<float4*>(rays + r * 8);
-  out[0] = make_float4(o[0], o[1], o[2], d[0]);
-  out[1] = make_float4(d[1], d[2], nr, fr);
+  out[0] = q0;
+  out[1] = q1;
 }
 
 extern "C" int nsr_gen_rays(const float* c2w, int H, int W, double focal, int s, int ndc, float near_, float far_,
@@ -70,20 +41,18 @@ extern "C" int nsr_gen_rays(const float* c2w, int H, int W, double focal, int s,
 
 extern "C" int nsr_gen_rays_range(const float* c2w, int H, int W, double focal, int s, int ndc, float near_, float far_,
                                   int64_t lr_lo, int64_t lr_hi, float* rays_dev, void* stream) {
-  if (!c2w || H <= 0 || W <= 0 || s <= 0 || !(focal > 0.0)) return NSR_ERR_INVALID_ARG;
-  if (H % s != 0 || W % s != 0) return NSR_ERR_INVALID_ARG;
+  return nsr_gen_rays_opt(c2w, H, W, focal, s, ndc, near_, far_, 0u, lr_lo, lr_hi, rays_dev, stream);
+}
+
+// ... plus the direction options of the datasets (include/nsr_data.h): bit 0 no pixel centres, bit 1 unified direction
+extern "C" int nsr_gen_rays_opt(const float* c2w, int H, int W, double focal, int s, int ndc, float near_, float far_,
+                                unsigned options, int64_t lr_lo, int64_t lr_hi, float* rays_dev, void* stream) {
+  GenRaysArgs a;
+  if (!c2w || !nsr_ray_cam(a.cam, H, W, focal, s, ndc, near_, far_, options)) return NSR_ERR_INVALID_ARG;
   if (lr_lo < 0 || lr_hi < lr_lo || lr_hi > (int64_t)(H / s) * (W / s)) return NSR_ERR_INVALID_ARG;
   if (lr_hi == lr_lo) return NSR_OK;   // empty shard: nothing to write (the pointer may be null)
   if (!rays_dev || (reinterpret_cast<uintptr_t>(rays_dev) & 15) != 0) return NSR_ERR_INVALID_ARG;
-  GenRaysArgs a;
   for (int i = 0; i < 12; ++i) a.c2w[i] = c2w[i];
-  a.H = H; a.W = W; a.s = s; a.ndc = ndc;
-  a.focal = (float)focal;
-  a.half_w = (float)(W / 2.0);
-  a.half_h = (float)(H / 2.0);
-  a.ndc_ax = (float)(-1.0 / (W / (2.0 * focal)));
-  a.ndc_ay = (float)(-1.0 / (H / (2.0 * focal)));
-  a.near_ = near_; a.far_ = far_;
   const int64_t n = (lr_hi - lr_lo) * s * s;
   const int threads = 256;
   const int64_t blocks = (n + threads - 1) / threads;

@@ -7,6 +7,7 @@ Host-side, numpy only (the reference's versions are host-side Python too):
     src/base/reconstruction.cc) and the LLFF pose pipeline built on them (data/llff_downX_dataset.py read_meta,
     identical in warp.py:35-92): focal rescale, camera-to-world, near/far bounds from the visible points,
     'right down front' -> 'right up back', centring on the average pose, rescaling so the nearest depth is 1 / 0.75
+  * the test split's camera paths (data/llff_downX_dataset.py:86-159): ``spiral_path`` / ``spheric_path``
   * Blender ``transforms_{split}.json`` (data/blender_downX_dataset.py:60-95): focal from ``camera_angle_x``, 4x4 poses
   * LR training targets (data/llff_downX_dataset.py:312-329): Pillow's 8-bit LANCZOS resize to the HR and LR sizes,
     ``/ 255`` and the sub-pixel regroup -- these run ON THE DEVICE (include/nsr_image.h), bit-identical to Pillow;
@@ -211,6 +212,34 @@ def llff_scene_from_colmap(sparse_dir: str, img_w: int) -> Dict[str, object]:
     return {"focal": float(cam.params[0] * img_w / cam.width), "names": [images[i].name for i in order], "poses": poses,
             "bounds": bounds / scale, "val_idx": int(np.argmin(np.linalg.norm(poses[:, :, 3], axis=1))),
             "scale_factor": float(scale)}
+
+
+def spiral_path(radii, focus_depth: float, n: int = 120) -> np.ndarray:
+    """The forward-facing test path (``create_spiral_poses``, data/llff_downX_dataset.py:86-118): two turns of a spiral with
+    per-axis ``radii`` whose cameras look at the plane z = -focus_depth -> (n, 3, 4) float64.  The `test` split uses
+    ``radii = percentile(|poses[..., 3]|, 90, axis=0)`` and ``focus_depth = 3.5`` (:379-383)."""
+    radii = np.asarray(radii, dtype=np.float64)
+    poses = []
+    for t in np.linspace(0, 4 * np.pi, n + 1)[:-1]:
+        centre = np.array([np.cos(t), -np.sin(t), -np.sin(0.5 * t)]) * radii
+        z = _unit(centre - np.array([0, 0, -focus_depth]))
+        x = _unit(np.cross(np.array([0, 1, 0]), z))
+        poses.append(np.stack([x, np.cross(z, x), z, centre], 1))
+    return np.stack(poses, 0)
+
+
+def spheric_path(radius: float, n: int = 120) -> np.ndarray:
+    """The inward-facing test path (``create_spheric_poses``, data/llff_downX_dataset.py:121-159): a circle around the z axis
+    looking 36 degrees downwards -> (n, 3, 4) float64.  The `test` split uses ``radius = 1.1 * bounds.min()`` (:385-386)."""
+    phi = -np.pi / 5
+    trans = np.array([[1, 0, 0, 0], [0, 1, 0, -0.9 * radius], [0, 0, 1, radius], [0, 0, 0, 1]])
+    rot_phi = np.array([[1, 0, 0, 0], [0, np.cos(phi), -np.sin(phi), 0], [0, np.sin(phi), np.cos(phi), 0], [0, 0, 0, 1]])
+    flip = np.array([[-1, 0, 0, 0], [0, 0, 1, 0], [0, 1, 0, 0], [0, 0, 0, 1]])
+    poses = []
+    for th in np.linspace(0, 2 * np.pi, n + 1)[:-1]:
+        rot_theta = np.array([[np.cos(th), 0, -np.sin(th), 0], [0, 1, 0, 0], [np.sin(th), 0, np.cos(th), 0], [0, 0, 0, 1]])
+        poses.append((flip @ (rot_theta @ rot_phi @ trans))[:3])
+    return np.stack(poses, 0)
 
 
 # ------------------------------------------------------------------------------------------------ Blender scenes
