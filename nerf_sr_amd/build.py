@@ -133,6 +133,12 @@ TEST_HOOKS_SRCS = [TEST_HOOKS_SRC, os.path.join(os.path.dirname(HERE), "tests", 
 TEST_HOOKS_SRCS.append(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_ert.hip"))
 # ... and the render launch's counter at 192 and 256 samples, which the wrapper above refuses (tests/test_gpu_testtime.py)
 TEST_HOOKS_SRCS.append(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_testtime.hip"))
+# ... and the kernel choice of gemm_f16x3 as a value, and the explicit im2col (tests/test_gpu_conv_units.py)
+# (linked only where tests/ carries it: tests/hooks.py binds its two symbols by name, so a tests/ directory that uses them
+# without the unit fails when the library is loaded, and one from before the unit existed builds as it always did)
+_CONV_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_conv.hip")
+if os.path.exists(_CONV_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_CONV_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -79,7 +79,33 @@ struct GemmF16Args {
   const unsigned short* Bs;
 };
 NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st);
-// v = kSplitScale * w[i];  hi[i] = fp16(v), lo[i] = fp16(v - hi[i])   (round to nearest)
+// The kernel instantiation gemm_f16x3 launches for `a` (host arithmetic only, no device needed): a negative NSR_ERR_* exactly
+// where gemm_f16x3 refuses the arguments, else one of the enumerators below.  conv_halo_kernel<BN, BM, GROUPED, S[, MULTI]>
+// first, then gemm_f16x3_kernel<WN, APL, TK, BN, FULLN>; the values are part of the unit tests (tests/hooks.py).
+enum GemmF16Route {
+  kRouteNone = 0,               // M == 0: nothing is launched
+  kRouteHaloTail = 1,           // <2, 2, false, 1>: 64 padded columns, tanh, fp32 NHWC output
+  kRouteMultiS1 = 2,            // <4, 2, true, 1, true>: eight plain images of width 8 per block
+  kRouteMultiS2 = 3,            // <4, 2, true, 2, true>
+  kRouteHalfS1 = 4,             // <4, 2, false, 1>: 256 x 128 outputs per workgroup
+  kRouteHalfGroupedS1 = 5,      // <4, 2, true, 1>
+  kRouteHalfS2 = 6,             // <4, 2, false, 2>
+  kRouteHalfGroupedS2 = 7,      // <4, 2, true, 2>
+  kRouteBig82S1 = 8,            // <8, 2, false, 1>: 256 x 256
+  kRouteBig82GroupedS1 = 9,     // <8, 2, true, 1>
+  kRouteBig44S1 = 10,           // <4, 4, false, 1>: 512 x 128
+  kRouteBig44GroupedS1 = 11,    // <4, 4, true, 1>
+  kRouteBig82S2 = 12,           // <8, 2, false, 2>
+  kRouteBig82GroupedS2 = 13,    // <8, 2, true, 2>
+  kRouteStagedWide = 14,        // <2, true, 32, 4>: 128 x 256 staged tile
+  kRouteStagedK64Full = 15,     // <2, true, 64, 2, true>
+  kRouteStagedK64 = 16,         // <2, true, 64>
+  kRouteStagedK32Full = 17,     // <2, true, 32, 2, true>
+  kRouteStagedK32 = 18,         // <2, true>
+  kRouteStagedF32A = 19,        // <2, false>: fp32 A, split while it is staged
+};
+NSR_INTERNAL int gemm_f16x3_route(const GemmF16Args& a);
+// v =kSplitScale * w[i];  hi[i] = fp16(v), lo[i] = fp16(v - hi[i])   (round to nearest)
 NSR_INTERNAL int split_f16(const float* w, int64_t n, unsigned short* hi, unsigned short* lo, hipStream_t st);
 
 // ---- weight gradient from two training panels on the fp16 MFMA (nsr_wgrad_f16.hip): partial[z] (M x N) =

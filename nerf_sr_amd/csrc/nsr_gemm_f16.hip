@@ -842,7 +842,7 @@ NSR_INTERNAL int split_f16(const float* w, int64_t n, unsigned short* hi, unsign
   return NSR_OK;
 }
 
-NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
+NSR_INTERNAL int gemm_f16x3_route(const GemmF16Args& a) {
   const GemmArgs& g = a.g;
   if (g.M < 0 || g.N <= 0 || g.K <= 0 || (g.K % 16) != 0 || g.n_valid > g.N) return NSR_ERR_INVALID_ARG;   // the staged tiles: K % 32, below
   if (!a.Bh || !a.Bl || g.Ct || g.splits > 1 || g.a_kmajor || g.b_kmajor) return NSR_ERR_INVALID_ARG;
@@ -864,7 +864,7 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
         (reinterpret_cast<uintptr_t>(a.Mh) & 3))
       return NSR_ERR_INVALID_ARG;
   }
-  if (g.M == 0) return NSR_OK;
+  if (g.M == 0) return kRouteNone;
   // Tile choice (one MI355X box, 800 x 800 refinement pass, profiles/r3_refine_tiles.txt): two 4-wave workgroups per CU
   // beat one 8-wave workgroup whatever they compute -- they run out of phase, so one stages and waits at its barriers
   // while the other feeds the matrix pipe (8-wave 128 x 256: 41.4 ms; 4-wave 128 x 128 everywhere: 40.0).  Of the 4-wave
@@ -886,11 +886,7 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
       (reinterpret_cast<uintptr_t>(a.Bs) & 15) == 0 && a.conv.Ho == a.conv.Hs && a.conv.Wo == a.conv.Ws && (a.conv.Ho % 16) == 0 &&
       (a.conv.Wo % 16) == 0 && (g.M % ((int64_t)a.conv.Ho * a.conv.Wo)) == 0 &&
       (a.a_plane + (g.M / ((int64_t)a.conv.Ho * a.conv.Wo)) * a.conv.Hs * a.conv.Ws * g.lda) * 2 < ((int64_t)1 << 32)) {
-    const int64_t n_blk = g.M / 256;
-    const dim3 hgrid((unsigned)(((n_blk + 7) / 8) * 8));
-    hipLaunchKernelGGL((conv_halo_kernel<2, 2, false, 1>), hgrid, dim3(256), 0, st, a, 1, n_blk);
-    if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
-    return NSR_OK;
+    return kRouteHaloTail;
   }
   if (a.Ah && a.Ch && a.Bs && a.conv.cin > 0 && (a.conv.stride == 1 || a.conv.stride == 2) && (a.conv.cin % 16) == 0 && (g.N % 128) == 0 &&
       g.n_valid == g.N && !g.mask && !g.col_sums && g.act == kActRelu && g.acc_scale != 0.0f && g.acc_scale != 1.0f &&
@@ -932,58 +928,86 @@ NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
     // third of the matrix pipe (340 workgroups of 144 K tiles: 1.33 CU-rounds, nine-fold re-reads of the activations).  A
     // matter of the image SHAPE only: any number of images (the last block is masked).
     if (!grouped && common && a.conv.Wo == 8 && (a.conv.Ho % 4) == 0 && 16 * per_img * g.ldc < ((int64_t)1 << 32)) {
-      const int64_t n_img = g.M / per_img;
-      const int64_t m_blk = ((n_img + 7) / 8) * (a.conv.Ho / 4) * (g.N / 128);
-      const dim3 mgrid((unsigned)(((m_blk + 7) / 8) * 8));
-      if (s2) hipLaunchKernelGGL((conv_halo_kernel<4, 2, true, 2, true>), mgrid, dim3(256), 0, st, a, g.N / 128, m_blk);
-      else hipLaunchKernelGGL((conv_halo_kernel<4, 2, true, 1, true>), mgrid, dim3(256), 0, st, a, g.N / 128, m_blk);
-      if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
-      return NSR_OK;
+      return s2 ? kRouteMultiS2 : kRouteMultiS1;
     }
     const bool paired = !wide && !grouped && !s2 && half_ok;
     const bool use_half = half_ok && (paired || !big_ok || 0.5 * 1.05 * rounds(half_blk) < rounds(big_blk));
     const bool use_big = !use_half && big_ok;
-    if (use_half || use_big) {
-      const int64_t n_blk = use_half ? half_blk : big_blk;
-      const int n_ct = use_half ? g.N / 128 : g.N / (wide ? 256 : 128);
-      const dim3 hgrid((unsigned)(((n_blk + 7) / 8) * 8));
-#define NSR_HALO_LAUNCH(BN_, BM_, S_)                                                                                         \
-  do {                                                                                                                        \
-    if (grouped) hipLaunchKernelGGL((conv_halo_kernel<BN_, BM_, true, S_>), hgrid, dim3(256), 0, st, a, n_ct, n_blk);       \
-    else hipLaunchKernelGGL((conv_halo_kernel<BN_, BM_, false, S_>), hgrid, dim3(256), 0, st, a, n_ct, n_blk);               \
-  } while (0)
-      if (s2) {
-        if (use_half) NSR_HALO_LAUNCH(4, 2, 2); else NSR_HALO_LAUNCH(8, 2, 2);
-      } else if (use_half) {
-        NSR_HALO_LAUNCH(4, 2, 1);
-      } else if (wide) {
-        NSR_HALO_LAUNCH(8, 2, 1);
-      } else {
-        NSR_HALO_LAUNCH(4, 4, 1);
-      }
-#undef NSR_HALO_LAUNCH
-      if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
-      return NSR_OK;
+    if (use_half) return s2 ? (grouped ? kRouteHalfGroupedS2 : kRouteHalfS2) : (grouped ? kRouteHalfGroupedS1 : kRouteHalfS1);
+    if (use_big) {
+      if (s2) return grouped ? kRouteBig82GroupedS2 : kRouteBig82S2;
+      if (wide) return grouped ? kRouteBig82GroupedS1 : kRouteBig82S1;
+      return grouped ? kRouteBig44GroupedS1 : kRouteBig44S1;
     }
   }
   if ((g.K % kTK) != 0 || (a.conv.cin > 0 && (a.conv.cin % kTK) != 0)) return NSR_ERR_INVALID_ARG;   // staged tiles: K tiles of 32 inside a tap
   const int64_t row_tiles = (g.M + kTM - 1) / kTM;
   // 128 x 256 tile on four waves (64 x 128 each) where there are enough row tiles to fill the chip with it
   const bool wide = g.N >= 256 && (g.N % 256) == 0 && a.Ah && a.Ch && row_tiles * (g.N / 256) >= 1024;
-  const int tn = wide ? 256 : 128;
+  if (!a.Ah) return kRouteStagedF32A;    // fp32 A: the 128 x 128 tile (the wide tile wants plane A)
+  const bool k64 = (g.K % 64) == 0 && (a.conv.cin <= 0 || (a.conv.cin % 64) == 0);
+  const bool fulln = (g.N % 128) == 0;   // 128 x 128 tiles only
+  if (wide) return kRouteStagedWide;
+  if (k64) return fulln ? kRouteStagedK64Full : kRouteStagedK64;
+  return fulln ? kRouteStagedK32Full : kRouteStagedK32;
+}
+
+NSR_INTERNAL int gemm_f16x3(const GemmF16Args& a, hipStream_t st) {
+  const GemmArgs& g = a.g;
+  const int route = gemm_f16x3_route(a);
+  if (route < 0) return route;
+  if (route == kRouteNone) return NSR_OK;
+  if (route < kRouteStagedWide) {     // conv_halo_kernel: workgroups of 256 x 64 (tail), 256 x 128 (MULTI, half), 256 x 256 / 512 x 128 (big)
+    const bool wide = (g.N % 256) == 0;
+    int64_t n_blk;
+    int n_ct;
+    switch (route) {
+      case kRouteHaloTail: n_ct = 1; n_blk = g.M / 256; break;
+      case kRouteMultiS1: case kRouteMultiS2: {
+        const int64_t n_img = g.M / ((int64_t)a.conv.Ho * a.conv.Wo);
+        n_ct = g.N / 128; n_blk = ((n_img + 7) / 8) * (a.conv.Ho / 4) * (g.N / 128);
+      } break;
+      case kRouteHalfS1: case kRouteHalfGroupedS1: case kRouteHalfS2: case kRouteHalfGroupedS2:
+        n_ct = g.N / 128; n_blk = (g.M / 256) * (g.N / 128); break;
+      default:
+        n_ct = g.N / (wide ? 256 : 128); n_blk = (g.M / (wide ? 256 : 512)) * n_ct; break;
+    }
+    const dim3 hgrid((unsigned)(((n_blk + 7) / 8) * 8));
+#define NSR_HALO_LAUNCH(R_, ...) \
+  case R_: hipLaunchKernelGGL((conv_halo_kernel<__VA_ARGS__>), hgrid, dim3(256), 0, st, a, n_ct, n_blk); break
+    switch (route) {
+      NSR_HALO_LAUNCH(kRouteHaloTail, 2, 2, false, 1);
+      NSR_HALO_LAUNCH(kRouteMultiS1, 4, 2, true, 1, true);
+      NSR_HALO_LAUNCH(kRouteMultiS2, 4, 2, true, 2, true);
+      NSR_HALO_LAUNCH(kRouteHalfS1, 4, 2, false, 1);
+      NSR_HALO_LAUNCH(kRouteHalfGroupedS1, 4, 2, true, 1);
+      NSR_HALO_LAUNCH(kRouteHalfS2, 4, 2, false, 2);
+      NSR_HALO_LAUNCH(kRouteHalfGroupedS2, 4, 2, true, 2);
+      NSR_HALO_LAUNCH(kRouteBig82S1, 8, 2, false, 1);
+      NSR_HALO_LAUNCH(kRouteBig82GroupedS1, 8, 2, true, 1);
+      NSR_HALO_LAUNCH(kRouteBig44S1, 4, 4, false, 1);
+      NSR_HALO_LAUNCH(kRouteBig44GroupedS1, 4, 4, true, 1);
+      NSR_HALO_LAUNCH(kRouteBig82S2, 8, 2, false, 2);
+      NSR_HALO_LAUNCH(kRouteBig82GroupedS2, 8, 2, true, 2);
+      default: return NSR_ERR_INVALID_ARG;
+    }
+#undef NSR_HALO_LAUNCH
+    if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
+    return NSR_OK;
+  }
+  const int64_t row_tiles = (g.M + kTM - 1) / kTM;
+  const int tn = route == kRouteStagedWide ? 256 : 128;
   const int n_col_tiles = (g.N + tn - 1) / tn;
   const int64_t n_blocks = row_tiles * n_col_tiles;
   const dim3 grid((unsigned)(((n_blocks + 7) / 8) * 8));
-  if (a.Ah) {
-    const bool k64 = (g.K % 64) == 0 && (a.conv.cin <= 0 || (a.conv.cin % 64) == 0);
-    const bool fulln = (g.N % 128) == 0;   // 128 x 128 tiles only
-    if (wide) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 32, 4>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
-    else if (k64 && fulln) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 64, 2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
-    else if (k64) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 64>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
-    else if (fulln) hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 32, 2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
-    else hipLaunchKernelGGL((gemm_f16x3_kernel<2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
-  } else {   // fp32 A: the 128 x 128 tile (the wide tile wants plane A)
-    hipLaunchKernelGGL((gemm_f16x3_kernel<2, false>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks);
+  switch (route) {
+    case kRouteStagedWide: hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 32, 4>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks); break;
+    case kRouteStagedK64Full: hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 64, 2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks); break;
+    case kRouteStagedK64: hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 64>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks); break;
+    case kRouteStagedK32Full: hipLaunchKernelGGL((gemm_f16x3_kernel<2, true, 32, 2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks); break;
+    case kRouteStagedK32: hipLaunchKernelGGL((gemm_f16x3_kernel<2, true>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks); break;
+    case kRouteStagedF32A: hipLaunchKernelGGL((gemm_f16x3_kernel<2, false>), grid, dim3(256), 0, st, a, n_col_tiles, n_blocks); break;
+    default: return NSR_ERR_INVALID_ARG;
   }
   if (hipGetLastError() != hipSuccess) return NSR_ERR_LAUNCH;
   return NSR_OK;

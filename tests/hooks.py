@@ -71,7 +71,17 @@ SIGNATURES = {
     "nsr_test_wgrad_jobs": (c_int, [POINTER(WgradJobs), c_int, c_void_p]),
     "nsr_test_layout": (c_int, [c_int, POINTER(c_int64), c_int]),
     "nsr_test_pack_panel": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    # tests/csrc/nsr_test_hooks_conv.hip
+    "nsr_test_gemm_f16x3_route": (c_int, [POINTER(GemmF16Args)]),
+    "nsr_test_im2col": (c_int, [c_void_p, c_int, c_int64] + [c_int] * 9 + [c_void_p, c_void_p]),
 }
+
+# nsr::GemmF16Route (csrc/nsr_gemm.h): the instantiation gemm_f16x3 launches
+(ROUTE_NONE, ROUTE_HALO_TAIL, ROUTE_MULTI_S1, ROUTE_MULTI_S2, ROUTE_HALF_S1, ROUTE_HALF_GROUPED_S1, ROUTE_HALF_S2,
+ ROUTE_HALF_GROUPED_S2, ROUTE_BIG82_S1, ROUTE_BIG82_GROUPED_S1, ROUTE_BIG44_S1, ROUTE_BIG44_GROUPED_S1, ROUTE_BIG82_S2,
+ ROUTE_BIG82_GROUPED_S2, ROUTE_STAGED_WIDE, ROUTE_STAGED_K64_FULL, ROUTE_STAGED_K64, ROUTE_STAGED_K32_FULL, ROUTE_STAGED_K32,
+ ROUTE_STAGED_F32A) = range(20)
+ROUTE_NAMES = {v: k for k, v in list(globals().items()) if k.startswith("ROUTE_") and isinstance(v, int)}
 
 _lib = None
 

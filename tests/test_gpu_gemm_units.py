@@ -1,5 +1,7 @@
 """Unit layer under the training step: the matrix kernels on their own (csrc/nsr_gemm.hip + nsr_gemm_epilogue.h,
-nsr_gemm_f16.hip without the convolution gather, nsr_wgrad_f16.hip), reached through the test-hook library (tests/hooks.py).
+nsr_gemm_f16.hip as a plain linear layer, nsr_wgrad_f16.hip), reached through the test-hook library (tests/hooks.py).  The
+convolution gather of nsr_gemm_f16.hip -- conv_halo_kernel and the staged gather, every instantiation the dispatch can pick --
+has its own unit layer built on the same method: tests/test_gpu_conv_units.py (reference and cases: tests/conv_ref.py).
 
 Method.  The exact-input cases feed operands for which EVERY product and EVERY partial sum is exactly representable in
 fp32: small integers (|a|, |b| <= 4, integer bias), for the fp16 kernels times powers of two.  The result then does not
