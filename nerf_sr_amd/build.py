@@ -139,6 +139,10 @@ TEST_HOOKS_SRCS.append(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr
 _CONV_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_conv.hip")
 if os.path.exists(_CONV_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_CONV_HOOKS_SRC)
+# ... and the backward chain's packer, launch and size queries (tests/test_gpu_chain_units.py); linked on the same condition
+_CHAIN_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_chain.hip")
+if os.path.exists(_CHAIN_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_CHAIN_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -74,6 +74,13 @@ SIGNATURES = {
     # tests/csrc/nsr_test_hooks_conv.hip
     "nsr_test_gemm_f16x3_route": (c_int, [POINTER(GemmF16Args)]),
     "nsr_test_im2col": (c_int, [c_void_p, c_int, c_int64] + [c_int] * 9 + [c_void_p, c_void_p]),
+    # tests/csrc/nsr_test_hooks_chain.hip
+    "nsr_test_chain_bwd_pack": (c_int, [POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p]),
+    "nsr_test_chain_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int,
+                                   c_int, c_void_p]),
+    "nsr_test_chain_bwd_packed_bytes": (c_int64, []),
+    "nsr_test_train_panel_bytes": (c_int64, [c_int64]),
+    "nsr_test_train_sign_words": (c_int64, [c_int64]),
 }
 
 # nsr::GemmF16Route (csrc/nsr_gemm.h): the instantiation gemm_f16x3 launches
