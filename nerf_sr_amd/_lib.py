@@ -47,6 +47,17 @@ NSR_RAYS_NO_PIXEL_CENTERS, NSR_RAYS_UNIFIED_DIR = 1, 2     # include/nsr_data.h:
 NSR_LR_FROM_IMAGES, NSR_LR_MEAN_OF_HR = 0, 1               # include/nsr_data.h: where the LR targets come from
 NSR_FLAG_INPUT_RANGE = 2
 
+
+class NsrRefinePatchset(ctypes.Structure):
+    """``struct nsr_refine_patchset`` (include/nsr_refine_data.h): 8-bit images, coefficient and box tables as device pointers."""
+    _fields_ = [("gt", c_void_p), ("sr", c_void_p), ("ref", c_void_p), ("coeffs", c_void_p), ("bboxs", c_void_p),
+                ("n_img", c_int), ("n_aug", c_int), ("H", c_int), ("W", c_int), ("patch_len", c_int), ("num_ref_patches", c_int),
+                ("ref_offset", c_int), ("with_gt_patch", c_int), ("mode", c_int)]
+
+
+NSR_PATCHES_TRAIN, NSR_PATCHES_VAL = 0, 1                  # include/nsr_refine_data.h: which split's ranges the kernel applies
+NSR_REFINE_MAX_REF_PATCHES = 64
+
 # symbol -> (restype, argtypes); must list every function of include/*.h
 SIGNATURES = {
     "nsr_version": (c_int, []),
@@ -162,6 +173,11 @@ SIGNATURES = {
     "nsr_rayset_batch": (c_int, [POINTER(NsrRayset), c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nsr_gen_rays_opt": (c_int, [POINTER(c_float), c_int, c_int, c_double, c_int, c_int, c_float, c_float, c_uint, c_int64, c_int64,
                                  c_void_p, c_void_p]),
+    # ---- include/nsr_refine_data.h
+    "nsr_refine_patch_batch": (c_int, [POINTER(NsrRefinePatchset), c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "nsr_refine_aug_bbox": (c_int, [POINTER(NsrRefinePatchset), c_void_p, c_void_p]),
+    "nsr_refine_warp_image": (c_int, [POINTER(NsrRefinePatchset), c_int, c_int, c_void_p, c_void_p]),
     # ---- include/nsr_metrics.h
     "nsr_ssim_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "nsr_ssim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_double, c_double,

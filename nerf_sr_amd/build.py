@@ -38,6 +38,7 @@ UNITS = [
     ("nsr_image.hip", ["-ffp-contract=off"]),
     ("nsr_metrics.hip", ["-ffp-contract=off"]),
     ("nsr_data.hip", ["-ffp-contract=off"]),
+    ("nsr_refine_data.hip", ["-ffp-contract=off"]),
     ("nsr_api.hip", []),
 ]
 VARIANT_UNITS = {}   # -D flag -> (extra source, flags): experiment kernels of an ablation build (none at present)
