@@ -144,6 +144,11 @@ if os.path.exists(_CONV_HOOKS_SRC):
 _CHAIN_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_chain.hip")
 if os.path.exists(_CHAIN_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_CHAIN_HOOKS_SRC)
+# ... and the launchers of the compositing backward, the loss head, the density noise and the per-sample gamma
+# (tests/test_gpu_train_heads.py); linked on the same condition
+_HEADS_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_heads.hip")
+if os.path.exists(_HEADS_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_HEADS_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

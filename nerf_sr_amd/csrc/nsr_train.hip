@@ -358,6 +358,13 @@ template <bool FULL> CompositeBwdFn composite_bwd_for(int K) {   // K: samples p
     default: return nullptr;
   }
 }
+
+}  // namespace
+
+// ---- the launchers of the kernels above (nsr_train_work.h): what the passes below call, and what the unit tests reach
+// through tests/csrc/nsr_test_hooks_heads.hip
+namespace nsr {
+
 // (P, 4) rows into d4 from the pass's rgb / sig / z; gmax, bias_part: the chain path's, else null.  g_opacity / g_weights
 // (the backward entry points only): non-null selects the FULL instantiation
 int composite_bwd(hipStream_t st, const float* rgb, const float* sig, const float* z, const float* g_comp, int64_t R, int N, int white,
@@ -370,6 +377,39 @@ int composite_bwd(hipStream_t st, const float* rgb, const float* sig, const floa
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
+
+int sigma_noise(hipStream_t st, const float* sigma, int sigma_stride, const float* noise, float std_, int64_t P, float* out) {
+  hipLaunchKernelGGL(sigma_noise_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, sigma, sigma_stride, noise, std_, P, out);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
+int gamma_points(hipStream_t st, float* rgb4, int64_t P) {
+  hipLaunchKernelGGL(gamma_points_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, rgb4, P);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
+int lr_loss(hipStream_t st, const float* comp, const float* target, int64_t n_lr, int s2, double scale, float lambda, float* lr_out,
+            float* g_comp, double* block_sums, float lambda_var, float lambda_dvar, float far, const float* depth, float* g_depth) {
+  const int nblk = (int)((n_lr + 255) / 256);
+  hipLaunchKernelGGL(lr_loss_kernel, dim3(nblk), dim3(256), 0, st, comp, target, n_lr, s2, scale, lambda, lr_out, g_comp, block_sums,
+                     lambda_var, lambda_dvar, far, depth, g_depth);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
+int loss_finish(hipStream_t st, const double* block_sums, int n, double scale, float lambda, float* losses, int slot, double* carry,
+                float lambda_var, float lambda_dvar, float* var_losses) {
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, block_sums, n, scale, lambda, losses, slot, carry, lambda_var,
+                     lambda_dvar, var_losses);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
+}  // namespace nsr
+
+namespace {
 
 // ---- the opening the drivers share ---------------------------------------------------------------------------------------
 // the shape rules: sample counts and precision (NSR_ERR_UNSUPPORTED), R and the chunk multiples of s2
@@ -473,13 +513,9 @@ int pass_sample(const Run& c, const Pass& q, const float* rays, const float* u, 
 // compositing
 int pass_finish(hipStream_t st, const Run& c, const Pass& q, const float* noise, float* rgb4, float* sig, const float* z, float* comp,
                 float* depth, float* opac, float* wts, void* stream) {
-  hipLaunchKernelGGL(sigma_noise_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, st, rgb4 + 3, 4,
-                     c.noise_std > 0.0f ? rows_of(noise, q, q.N) : nullptr, c.noise_std, q.P, sig);
-  NSR_CHECK_LAUNCH();
-  if (c.flags & NSR_TRAIN_GAMMA_CORRECT) {   // render_rays: out_rgbs = pow(out_rgbs, 1 / 2.2) per sample, in training too (nerf_downX_model.py:271-276)
-    hipLaunchKernelGGL(gamma_points_kernel, dim3((unsigned)((q.P + 255) / 256)), dim3(256), 0, st, rgb4, q.P);
-    NSR_CHECK_LAUNCH();
-  }
+  NSR_TRY(sigma_noise(st, rgb4 + 3, 4, c.noise_std > 0.0f ? rows_of(noise, q, q.N) : nullptr, c.noise_std, q.P, sig));
+  if (c.flags & NSR_TRAIN_GAMMA_CORRECT)     // render_rays: out_rgbs = pow(out_rgbs, 1 / 2.2) per sample, in training too (nerf_downX_model.py:271-276)
+    NSR_TRY(gamma_points(st, rgb4, q.P));
   return nsr_composite(rgb4, 4, sig, 1, z, q.rc, q.N, c.flags & (NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS), comp, depth, opac, wts, stream);
 }
 // forward half of pass q: sampling into z, the network (what its backward reads stays in k.kept), density noise,
@@ -729,13 +765,9 @@ extern "C" int nsr_train_loss_and_grads_var(const float* const* w_coarse, const 
     const int nblk = (int)((n_lr + 255) / 256);
     const float l_var = net ? var->lambda_fine_var : var->lambda_coarse_var;
     const float l_dvar = net ? var->lambda_fine_depth_var : var->lambda_coarse_depth_var;
-    hipLaunchKernelGGL(lr_loss_kernel, dim3(nblk), dim3(256), 0, st, comp, target_lr + lr0 * 3, n_lr, s2, mse_scale,
-                       lambda, (net ? lr_fine : lr_coarse) + lr0 * 3, k.g_comp, k.block_sums, l_var, l_dvar,
-                       var->far, depth_var ? depth : nullptr, depth_var ? k.g_depth : nullptr);
-    NSR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, st, k.block_sums, nblk, mse_scale, lambda, losses, net,
-                       k.carry, l_var, l_dvar, var_losses);
-    NSR_CHECK_LAUNCH();
+    NSR_TRY(lr_loss(st, comp, target_lr + lr0 * 3, n_lr, s2, mse_scale, lambda, (net ? lr_fine : lr_coarse) + lr0 * 3, k.g_comp,
+                    k.block_sums, l_var, l_dvar, var->far, depth_var ? depth : nullptr, depth_var ? k.g_depth : nullptr));
+    NSR_TRY(loss_finish(st, k.block_sums, nblk, mse_scale, lambda, losses, net, k.carry, l_var, l_dvar, var_losses));
     return pass_backward(st, k, c, q, w, z, k.g_comp, depth_var ? k.g_depth : nullptr, nullptr, nullptr,
                          net ? g_fine : g_coarse, stream);
   });

@@ -185,6 +185,26 @@ NSR_INTERNAL int net_forward(hipStream_t st, const Shape& S, const float* rays, 
 // backward of the network from k.d4 (composite_bwd's rows); g: its 2 D + 8 gradient tensors
 NSR_INTERNAL int net_backward(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, const Work& k, int64_t P,
                               float* const* g, int acc, int stop_grad);
+// ---- nsr_train.hip: the launchers of the kernels between the rendered colours and the network's backward
+// compositing backward: (P, 4) rows d4 = (d rgb_pre 0..2, d sigma) of R rays x N samples (N <= 256, else NSR_ERR_UNSUPPORTED);
+// `white`: the training option word; gmax (10 words, cleared), bias_part (R, 4), g_depth (R), g_opacity (R), g_weights (R, N)
+// may be null; g_opacity or g_weights non-null selects the FULL instantiation
+NSR_INTERNAL int composite_bwd(hipStream_t st, const float* rgb, const float* sig, const float* z, const float* g_comp, int64_t R,
+                               int N, int white, float* d4, unsigned* gmax, float* bias_part, const float* g_depth,
+                               const float* g_opacity, const float* g_weights);
+// out[p] = sigma[p * sigma_stride] + noise[p] * std (noise null: a copy)
+NSR_INTERNAL int sigma_noise(hipStream_t st, const float* sigma, int sigma_stride, const float* noise, float std_, int64_t P,
+                             float* out);
+// columns 0..2 of the (P, 4) rows become pow(c, 1 / 2.2)
+NSR_INTERNAL int gamma_points(hipStream_t st, float* rgb4, int64_t P);
+// s2 mean of the n_lr x s2 composited colours, loss partials of ceil(n_lr / 256) blocks into block_sums [q * nblk + block],
+// dL/d(comp) per sub-ray and (g_depth non-null) dL/d(depth)
+NSR_INTERNAL int lr_loss(hipStream_t st, const float* comp, const float* target, int64_t n_lr, int s2, double scale, float lambda,
+                         float* lr_out, float* g_comp, double* block_sums, float lambda_var, float lambda_dvar, float far,
+                         const float* depth, float* g_depth);
+// carry[slot], [2 + slot], [4 + slot] += the three sums of n block partials; losses[slot] (and var_losses, may be null) from them
+NSR_INTERNAL int loss_finish(hipStream_t st, const double* block_sums, int n, double scale, float lambda, float* losses, int slot,
+                             double* carry, float lambda_var, float lambda_dvar, float* var_losses);
 // ---- nsr_train_wgrad.hip: weight and bias gradients of the chain path from the panels
 NSR_INTERNAL int chain_weight_grads(hipStream_t st, const Work& k, int64_t P, int64_t n_rays, float* const* g, int acc);
 

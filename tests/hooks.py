@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import shutil
-from ctypes import POINTER, Structure, c_float, c_int, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int64, c_void_p
 
 import torch  # noqa: F401  -- FIRST: see the load-order note in nerf_sr_amd/_lib.py::load
 
@@ -81,6 +81,14 @@ SIGNATURES = {
     "nsr_test_chain_bwd_packed_bytes": (c_int64, []),
     "nsr_test_train_panel_bytes": (c_int64, [c_int64]),
     "nsr_test_train_sign_words": (c_int64, [c_int64]),
+    # tests/csrc/nsr_test_hooks_heads.hip
+    "nsr_test_composite_bwd": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int] + [c_void_p] * 7),
+    "nsr_test_lr_loss": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_double, c_float, c_void_p, c_void_p, c_void_p, c_float,
+                                 c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "nsr_test_loss_finish": (c_int, [c_void_p, c_int, c_double, c_float, c_void_p, c_int, c_void_p, c_float, c_float, c_void_p,
+                                     c_void_p]),
+    "nsr_test_sigma_noise": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int64, c_void_p, c_void_p]),
+    "nsr_test_gamma_points": (c_int, [c_void_p, c_int64, c_void_p]),
 }
 
 # nsr::GemmF16Route (csrc/nsr_gemm.h): the instantiation gemm_f16x3 launches
