@@ -37,6 +37,26 @@ int nsr_ssim(const float* output, const float* target, int B, int C, int H, int 
              int kw, double c1, double c2, double* ssim, float* ssim_map, void* workspace, size_t workspace_bytes,
              void* stream);
 
+/* Gradient of nsr_ssim with respect to its two images: one launch, no workspace, nothing per pixel in device memory.
+ * Same images, sizes, `layout`, window and constants as the forward call (the forward's outputs are not needed: every
+ * window sum is recomputed, in double).  Upstream gradients, fp32, either may be null (= 0) but not both:
+ *   g_ssim (B): of the per-image values; g_map (B, C, H, W), always this order: of the map.
+ * An output pixel q then weighs G_q = g_ssim[b] / (C H W) + g_map[b, c, q].
+ * grad_output / grad_target: fp32 in `layout` order, either may be null (not computed) but not both; every element of a
+ * requested gradient is overwritten, so the buffers may be uninitialised.  The bits of one gradient do not depend on
+ * whether the other is requested.  Products and sums are double, only the final store rounds to fp32: the result agrees
+ * with fp64 autograd of the reference's `SSIM.__call__` to 2^-24 of the gradient's largest magnitude.  No atomics: an
+ * image's gradient has the same bits alone, at any batch size, in any slot of the batch and in both layouts.
+ * A workgroup owns a 16 x 32 (rows x columns) tile of input pixels and keeps in LDS
+ *   8 (kh + 8) kw + 2 * 4 (16 + 2 (kh - 1)) (32 + 2 (kw - 1)) + 4 * 8 (16 + kh - 1) (32 + kw - 1) bytes
+ * (window as double between four zero rows above and below; x and y over the tile +- 2 pad; four double coefficient maps
+ * over the tile +- pad): 51 592 bytes for the 11 x 11 window.  NSR_ERR_UNSUPPORTED: a window for which this exceeds 64 KB
+ * (13 x 13 is the largest square one).
+ * B == 0 is a no-op. */
+int nsr_ssim_backward(const float* output, const float* target, int B, int C, int H, int W, int layout,
+                      const float* window, int kh, int kw, double c1, double c2, const float* g_ssim, const float* g_map,
+                      float* grad_output, float* grad_target, void* stream);
+
 /* Bytes of workspace nsr_psnr needs: two doubles per 4096-element block of every segment. */
 size_t nsr_psnr_workspace_bytes(int n_seg, int64_t n);
 

@@ -182,6 +182,8 @@ SIGNATURES = {
     "nsr_ssim_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "nsr_ssim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_double, c_double,
                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nsr_ssim_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_double, c_double,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nsr_psnr_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "nsr_psnr": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }

@@ -3,13 +3,15 @@
 ``SSIM`` mirrors ``models/criterions.py:190-284`` (same constructor, same argument checks and exception types, same window
 table) and ``PSNR`` ``:27-36`` (``value[valid_mask]`` with an element mask or a row mask).  Both run as one kernel plus a
 fixed-order reduction with every product and sum in double, so the values agree with the reference evaluated in fp64 and
-a frame gives the same bits whatever batch it is part of.  All arithmetic runs in libnsr.so; there is no CPU path.
+a frame gives the same bits whatever batch it is part of.  ``SSIM`` is differentiable as the reference's is: with an input
+that requires grad it back-propagates through ``nsr_ssim_backward``.  All arithmetic runs in libnsr.so; there is no CPU path.
 """
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .ops import _f32, _p, _stream
@@ -52,7 +54,12 @@ class SSIM:
 
     ``layout='BHWC'`` reads (B, H, W, C) frames (the NeRF side's images) without a permute; ``return_map=True`` also returns
     the (B, C, H, W) fp32 map the means are taken over.  Returns a tensor of the inputs' dtype: the per-image values for
-    ``reduction='none'``, their mean or sum otherwise."""
+    ``reduction='none'``, their mean or sum otherwise.
+
+    As the reference's chain of torch ops does, the result back-propagates: when ``output`` or ``target`` requires grad, the
+    values (and the map) carry a ``grad_fn`` whose backward is ``nsr_ssim_backward`` (double arithmetic, fp32 gradients in the
+    inputs' layout, only those autograd asks for; not differentiable twice), so ``1 - ssim(pred, gt)`` is a loss.  The forward
+    values are the same bits with and without grad."""
 
     def __init__(self, data_range=(0, 1), kernel_size=(11, 11), sigma=(1.5, 1.5), k1=0.01, k2=0.03, gaussian=True):
         self.kernel_size = tuple(kernel_size)
@@ -96,6 +103,18 @@ class SSIM:
             raise ValueError(f"SSIM: a {H} x {W} image with {C} channels is not larger than the reflect padding "
                              f"({self.pad_h}, {self.pad_w}) of the window")
         output, target = _f32(output, "output"), _f32(target, "target")
+        if torch.is_grad_enabled() and (output.requires_grad or target.requires_grad):
+            # the same launches under a torch.autograd.Function whose backward is nsr_ssim_backward; mean / sum stay torch ops
+            outs = _SSIMFunction.apply(self, (B, C, H, W), layout, return_map, output, target)
+            _ssim, smap = outs if return_map else (outs, None)
+        else:
+            _ssim, smap = self._forward(output, target, (B, C, H, W), layout, return_map)
+        res = _ssim if reduction == "none" else (_ssim.mean() if reduction == "mean" else _ssim.sum())
+        return (res, smap) if return_map else res
+
+    def _forward(self, output, target, dims, layout, return_map):
+        """The per-image values (B,) in the inputs' dtype and the map (or None): nsr_ssim."""
+        B, C, H, W = dims
         dev = output.device
         lib = _lib.load()
         vals = torch.empty(B, dtype=torch.float64, device=dev)
@@ -106,9 +125,42 @@ class SSIM:
             _lib.check(lib.nsr_ssim(_p(output), _p(target), B, C, H, W, LAYOUTS[layout], _p(self._window(dev)), self.kernel_size[0],
                                     self.kernel_size[1], self.c1, self.c2, _p(vals), _p(smap), _p(ws), ws.numel(), _stream()),
                        "nsr_ssim")
-        _ssim = vals.to(output.dtype)
-        res = _ssim if reduction == "none" else (_ssim.mean() if reduction == "mean" else _ssim.sum())
-        return (res, smap) if return_map else res
+        return vals.to(output.dtype), smap
+
+    def _backward(self, output, target, dims, layout, g_ssim, g_map, want_output, want_target):
+        """(grad_output, grad_target) in the inputs' memory order, None where not wanted: nsr_ssim_backward."""
+        B, C, H, W = dims
+        grads = [torch.empty_like(output) if want_output else None, torch.empty_like(target) if want_target else None]
+        if g_ssim is None and g_map is None:
+            return [None if g is None else g.zero_() for g in grads]
+        if B > 0:
+            g_ssim = None if g_ssim is None else g_ssim.to(torch.float32).contiguous()
+            g_map = None if g_map is None else g_map.to(torch.float32).contiguous()
+            dev = output.device
+            _lib.check(_lib.load().nsr_ssim_backward(_p(output), _p(target), B, C, H, W, LAYOUTS[layout], _p(self._window(dev)),
+                                                     self.kernel_size[0], self.kernel_size[1], self.c1, self.c2, _p(g_ssim), _p(g_map),
+                                                     _p(grads[0]), _p(grads[1]), _stream()), "nsr_ssim_backward")
+        return grads
+
+
+class _SSIMFunction(torch.autograd.Function):
+    """Outputs: the per-image values (B,), and the map (B, C, H, W) with ``return_map``.  Saves the two images only: the
+    backward recomputes the window sums.  Not differentiable twice."""
+
+    @staticmethod
+    def forward(ctx, ssim, dims, layout, return_map, output, target):
+        vals, smap = ssim._forward(output, target, dims, layout, return_map)
+        ctx.save_for_backward(output, target)
+        ctx.ssim, ctx.dims, ctx.layout = ssim, dims, layout
+        ctx.set_materialize_grads(False)           # an output nothing was computed from arrives as None: a null pointer
+        return (vals, smap) if return_map else vals
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ssim, g_map=None):
+        output, target = ctx.saved_tensors
+        grads = ctx.ssim._backward(output, target, ctx.dims, ctx.layout, g_ssim, g_map, ctx.needs_input_grad[4], ctx.needs_input_grad[5])
+        return (None, None, None, None) + tuple(grads)
 
 
 def _mask_bytes(valid_mask: Optional[torch.Tensor], shape, lead: int) -> Tuple[Optional[torch.Tensor], int]:

@@ -346,12 +346,16 @@ class RefineTrainer:
     """``RefineModel``'s training protocol (models/refine_model.py:84-175) for the ``MaxPoolingModel`` with reference patches,
     fp32: ``set_input`` -> ``forward`` -> ``calculate_losses`` -> ``backward`` -> ``optimizer_step`` (``optimize_parameters``
     does the four), Adam(lr, betas=(beta1, 0.999)) over the 72 parameters.  ``sd``: the reference's ``state_dict`` (tensors or
-    arrays).  Losses other than L1 / MSE are not built in: compose them in torch over ``forward_train``."""
+    arrays).  ``refine_with_ssim`` / ``lambda_refine_ssim`` are this build's addition, not the reference's: they add
+    ``lambda_refine_ssim * (1 - SSIM(data_range=(-1, 1))(pred, gt_patch))`` -- the score ``evaluate_image`` reports, as a loss --
+    to ``loss_tot`` (``metrics.SSIM`` under autograd; patches must be larger than the window's padding, 5 pixels).  Other
+    losses are not built in: compose them in torch over ``forward_train``."""
 
     def __init__(self, sd, lr: float = 5e-4, beta1: float = 0.9, refine_with_l1: bool = True, refine_with_mse: bool = False,
                  lambda_refine_l1: float = 1.0, lambda_refine_mse: float = 10.0, device="cuda", *, refine_with_vgg: bool = False,
                  refine_with_grad: bool = False, refine_as_gan: bool = False, precision: str = "fp32", not_use_ref: bool = False,
-                 momentum: float = 0.1, img_chunk: Optional[int] = None, beta2: float = 0.999, eps: float = 1e-8):
+                 momentum: float = 0.1, img_chunk: Optional[int] = None, beta2: float = 0.999, eps: float = 1e-8,
+                 refine_with_ssim: bool = False, lambda_refine_ssim: float = 1.0):
         # every option is checked before a device is touched
         for name, on in (("refine_with_vgg", refine_with_vgg), ("refine_with_grad", refine_with_grad), ("refine_as_gan", refine_as_gan)):
             if on:
@@ -361,8 +365,8 @@ class RefineTrainer:
             raise ValueError(f"RefineTrainer: precision must be 'fp32' (got {precision!r}): the refinement network trains in fp32 only")
         if not_use_ref:
             raise NotImplementedError("RefineTrainer: --not_use_ref training is not supported (inference is: MaxPoolingModel(not_use_ref=True))")
-        if not (refine_with_l1 or refine_with_mse):
-            raise ValueError("RefineTrainer: no loss selected (refine_with_l1 / refine_with_mse)")
+        if not (refine_with_l1 or refine_with_mse or refine_with_ssim):
+            raise ValueError("RefineTrainer: no loss selected (refine_with_l1 / refine_with_mse / refine_with_ssim)")
         missing = [k for k in REFINE_SPEC if k not in sd]
         if missing:
             raise KeyError(f"state_dict lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
@@ -370,6 +374,7 @@ class RefineTrainer:
         self.lr, self.beta1, self.beta2, self.eps = float(lr), float(beta1), float(beta2), float(eps)
         self.refine_with_l1, self.refine_with_mse = bool(refine_with_l1), bool(refine_with_mse)
         self.lambda_refine_l1, self.lambda_refine_mse = float(lambda_refine_l1), float(lambda_refine_mse)
+        self.refine_with_ssim, self.lambda_refine_ssim = bool(refine_with_ssim), float(lambda_refine_ssim)
         self.momentum, self.img_chunk = float(momentum), img_chunk
         dev = OrderedDict()
         for k, shape in REFINE_SPEC.items():
@@ -384,6 +389,7 @@ class RefineTrainer:
         self.exp_avg_sq = OrderedDict((k, torch.zeros_like(v)) for k, v in self.params.items())
         self.step = 0
         self.pred = None
+        self._ssim = None
 
     def set_input(self, input):
         for name in ("sr_patch", "ref_patches", "gt_patch"):
@@ -394,11 +400,19 @@ class RefineTrainer:
         return self.pred
 
     def calculate_losses(self):
-        """refine_model.py:151-168: lambda-weighted L1 / MSE (reduction 'mean'), their sum, PSNR of the input and the output."""
+        """refine_model.py:151-168: lambda-weighted L1 / MSE (reduction 'mean'), their sum, PSNR of the input and the output;
+        with ``refine_with_ssim`` also ``loss_ssim = lambda_refine_ssim * (1 - SSIM)`` (this build's addition), added to the sum."""
         zero = torch.zeros((), device=self.device)
         self.loss_l1 = torch.nn.functional.l1_loss(self.pred, self.data_gt_patch) * self.lambda_refine_l1 if self.refine_with_l1 else zero
         self.loss_mse = torch.nn.functional.mse_loss(self.pred, self.data_gt_patch) * self.lambda_refine_mse if self.refine_with_mse else zero
         self.loss_tot = self.loss_mse + self.loss_l1
+        self.loss_ssim = zero
+        if self.refine_with_ssim:
+            from . import metrics
+            if self._ssim is None:
+                self._ssim = metrics.SSIM(data_range=(-1, 1))
+            self.loss_ssim = self.lambda_refine_ssim * (1 - self._ssim(self.pred, self.data_gt_patch))
+            self.loss_tot = self.loss_tot + self.loss_ssim
         with torch.no_grad():
             psnr = lambda a, b: -10.0 * torch.log10(torch.mean((a - b) ** 2))
             self.loss_psnr_input = psnr(self.data_sr_patch, self.data_gt_patch)
