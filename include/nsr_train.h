@@ -241,6 +241,35 @@ int nsr_train_arch_backward(const nsr_arch* arch, const float* const* w_coarse, 
 int nsr_adam_step_n(int n, const int64_t* numel, float* const* w, const float* const* g, float* const* m, float* const* v,
                     int step, float lr, float beta1, float beta2, float eps, void* stream);
 
+/* ---- Fused inference of a non-default architecture under split-fp16 (csrc/nsr_mlp_arch_f16.hip; opt-in: ops.GenericMLP(fused=True)).
+ * ONE launch takes encoded rows x (P, in_xyz + in_dir; in_xyz = 3 + 6 deg_pos, in_dir = 3 + 6 deg_dir) to out (P, 4) = [rgb, sigma],
+ * or, under NSR_ARCH_FUSED_SIGMA_ONLY, x (P, >= in_xyz) to out (P, 1) = sigma; no activation leaves the chip between two layers.
+ * The arithmetic is nsr_linear_f16x3's, layer by layer (weights pre-split as RNE_f16(64 w) / RNE_f16(64 w - hi), every layer's
+ * input split into fp16 (hi, lo), three v_mfma_f32_32x32x16_f16 per product, fp32 accumulation, bias and activation), in another
+ * summation order.  A row's output bits depend on that row and the weights only.
+ * Supported set -- narrower than the layer-by-layer limits above: 1 <= D <= 8, even W with 2 <= W <= 256, any skip set inside
+ * 1 .. D-1, 0 <= deg_pos <= 10, 0 <= deg_dir <= 4, no_dir 0 / 1.  A descriptor beyond it is NSR_ERR_UNSUPPORTED (packed_bytes: 0),
+ * a malformed one NSR_ERR_INVALID_ARG (0), both before anything is enqueued.
+ *   nsr_arch_fused_pack     splits and re-lays the 2 D + 8 state tensors (DEVICE pointers, state_dict order) once into `packed`
+ *                           (nsr_arch_fused_packed_bytes, 16-byte aligned).  A non-finite weight or bias, or |w| >= 1023.75 (2^6 w
+ *                           leaves fp16), ORs NSR_FLAG_WEIGHT_RANGE into *status; the blob is written all the same.
+ *   nsr_arch_fused_forward  flags: NSR_ARCH_FUSED_SIGMA_ONLY | NSR_ARCH_FUSED_COLOR_NONE (--color_activation none); any other bit
+ *                           is NSR_ERR_INVALID_ARG.  ldx / ldo: row strides in floats.  P >= 0, any value (a tail tile forms no
+ *                           out-of-range address).  ORs the sticky NSR_FLAG_INPUT_RANGE (a non-finite input or |x| > 65504),
+ *                           NSR_FLAG_ACTIVATION_RANGE (a hidden activation >= 65520) and NSR_FLAG_OUTPUT_NONFINITE into *status
+ *                           (a DEVICE word the caller owns and clears; NULL: not reported).  `packed` must be what
+ *                           nsr_arch_fused_pack wrote for the same descriptor. */
+#define NSR_ARCH_FUSED_SIGMA_ONLY 1
+#define NSR_ARCH_FUSED_COLOR_NONE 2
+#define NSR_ARCH_FUSED_MAX_D 8
+#define NSR_ARCH_FUSED_MAX_W 256
+#define NSR_ARCH_FUSED_MAX_DEG_POS 10
+#define NSR_ARCH_FUSED_MAX_DEG_DIR 4
+size_t nsr_arch_fused_packed_bytes(const nsr_arch* arch);
+int nsr_arch_fused_pack(const nsr_arch* arch, const float* const* w, void* packed, unsigned* status, void* stream);
+int nsr_arch_fused_forward(const nsr_arch* arch, const void* packed, const float* x, int64_t ldx, int64_t P, int flags, float* out,
+                           int64_t ldo, unsigned* status, void* stream);
+
 /* One nn.Linear (+ activation) on the training GEMM, exposed for testing the kernel on its own:
  *   y (P, N) = act(x (P, K) · w (N, K)^T + b),  act: 0 none, 1 relu, 2 sigmoid;  y_t (N, P) optional transpose.
  * K % 32 == 0, ldx % 4 == 0, ldw % 4 == 0, 16-byte aligned pointers (the training step pads its operands). */

@@ -20,6 +20,9 @@ NSR_ERR_RANGE = -5
 FLAGS = {1: "WEIGHT_RANGE", 2: "INPUT_RANGE", 4: "ACTIVATION_RANGE", 8: "OUTPUT_NONFINITE"}
 NSR_FLAG_OUTPUT_NONFINITE = 8
 NSR_F16X3_GEMM = 18   # include/nsr_train.h: training entry points only
+NSR_ARCH_FUSED_SIGMA_ONLY, NSR_ARCH_FUSED_COLOR_NONE = 1, 2      # include/nsr_train.h: flags of nsr_arch_fused_forward
+# include/nsr_train.h: the architectures nsr_arch_fused_* cover (D, W, deg_pos, deg_dir)
+NSR_ARCH_FUSED_MAX_D, NSR_ARCH_FUSED_MAX_W, NSR_ARCH_FUSED_MAX_DEG_POS, NSR_ARCH_FUSED_MAX_DEG_DIR = 8, 256, 10, 4
 NSR_OPT_GAMMA, NSR_OPT_COLOR_NONE = 1, 2     # include/nsr.h: colour-head option word (nsr_weights_set_options)
 NSR_WHITE_BKGD, NSR_SIGMA_SOFTPLUS = 1, 2    # include/nsr.h: renderer option word (the `white_bkgd` argument)
 NSR_LAYOUT_BCHW, NSR_LAYOUT_BHWC = 0, 1      # include/nsr_metrics.h: memory order of nsr_ssim's images
@@ -134,6 +137,10 @@ SIGNATURES = {
                                         POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "nsr_adam_step_n": (c_int, [c_int, POINTER(c_int64), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                 c_int, c_float, c_float, c_float, c_float, c_void_p]),
+    "nsr_arch_fused_packed_bytes": (c_size_t, [POINTER(NsrArch)]),
+    "nsr_arch_fused_pack": (c_int, [POINTER(NsrArch), POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
+    "nsr_arch_fused_forward": (c_int, [POINTER(NsrArch), c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p,
+                                       c_void_p]),
     # ---- include/nsr_warp.h
     "nsr_depth_warp": (c_int, [c_void_p, c_int, c_int, c_double, POINTER(c_float), POINTER(c_double), c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p]),

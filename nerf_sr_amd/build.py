@@ -25,6 +25,7 @@ UNITS = [
     ("nsr_mlp.hip", ["-ffp-contract=off"]),
     ("nsr_mlp_f16.hip", ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     ("nsr_mlp_h1.hip", ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
+    ("nsr_mlp_arch_f16.hip", ["-ffp-contract=off"]),      # accumulators in AGPRs: at W = 256 a wave holds 380 registers
     ("nsr_gemm.hip", ["-ffp-contract=off"]),
     ("nsr_gemm_f16.hip", ["-ffp-contract=off"]),
     ("nsr_wgrad_f16.hip", ["-ffp-contract=off"]),
@@ -179,7 +180,8 @@ def build_test_hooks(force: bool = False, verbose: bool = True) -> str:
 #    SGPRs with v_readlane, a VMEM read of a VALU-written SGPR needs five wait states, and the hazard pass cannot see through
 #    inline asm: every global_load_lds / global_store inside an asm block must read a pair written by an s_mov_b64 inside the
 #    SAME block.
-ISA_UNITS = ["nsr_mlp_f16.hip", "nsr_train_chain.hip", "nsr_gemm_f16.hip", "nsr_wgrad_f16.hip", "nsr_mlp.hip", "nsr_mlp_h1.hip"]
+ISA_UNITS = ["nsr_mlp_f16.hip", "nsr_train_chain.hip", "nsr_gemm_f16.hip", "nsr_wgrad_f16.hip", "nsr_mlp.hip", "nsr_mlp_h1.hip",
+             "nsr_mlp_arch_f16.hip"]
 ISA_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-S",
              "--cuda-device-only"]
 

@@ -30,9 +30,12 @@ def default_options(**kw) -> SimpleNamespace:
         check_numerics=True,    # forward() raises on NaN / out-of-range values (the reference: pdb, nerf_downX_model.py:273-274)
         early_stop=0.0,         # eval mode, precision 'f16x3': early ray termination at this transmittance (0 = off; include/nsr.h)
         coarse_rgb=True,        # False: test-time mode, eval + 'f16x3' -- the coarse pass computes densities only (include/nsr.h)
+        arch_fused=False,       # True: a non-default D / W / skips / degrees runs in ONE fused launch under 'f16x3' (ops.GenericMLP(fused=True))
     )
     for k, v in kw.items():
         setattr(opt, k, v)
+    if opt.arch_fused and not ops.is_default_arch(ops.arch_of(opt)):      # refused here, on the host, not at the first launch
+        ops.check_arch_fused(ops.arch_of(opt), opt.precision)
     return opt
 
 

@@ -326,9 +326,15 @@ class GenericMLP:
 
     POINT_CHUNK = 262144          # rows per pass (the reference's point_chunk, options/base_options.py:70): bounds the buffers
 
-    def __init__(self, opt=None, device="cuda", precision: str = "fp32", **arch):
+    def __init__(self, opt=None, device="cuda", precision: str = "fp32", fused: bool = False, **arch):
         self.arch = {**arch_of(opt), **arch}
         self.spec = arch_spec(**self.arch)                  # validates
+        # fused=True (opt-in, precision 'f16x3'): the whole network in ONE launch per POINT_CHUNK, activations never leave the
+        # chip (nsr_arch_fused_forward, include/nsr_train.h) -- the arithmetic of the layer-by-layer route in another summation
+        # order.  Refused, before a device is touched, for a precision or an architecture the kernel does not cover.
+        self.fused = bool(fused)
+        if self.fused:
+            check_arch_fused(self.arch, precision)
         self.color_activation = getattr(opt, "color_activation", "sigmoid") if opt is not None else "sigmoid"
         if self.color_activation not in ("sigmoid", "none"):
             raise ValueError(f"color_activation={self.color_activation!r}: 'sigmoid' or 'none' (models/networks.py:173-180)")
@@ -372,6 +378,8 @@ class GenericMLP:
             v = sd[k]
             v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
             dev[k] = v.to(device=self.device, dtype=torch.float32).contiguous()
+        if self.fused:
+            return self._load_fused(dev)
         W, ix, Kx, Wp = a["W"], self.in_xyz, self.Kx, self.Wp
         self._layers = []                       # (weight, bias, first input column, K): the trunk, inputs = slots [pe | h]
         for i in range(a["D"]):
@@ -400,6 +408,26 @@ class GenericMLP:
                 self._split[w.data_ptr()] = hl
         return self
 
+    def _load_fused(self, dev):
+        """The fused route's weights: split and re-laid once into the kernel's stream (nsr_arch_fused_pack)."""
+        lib, arch = _lib.load(), _arch_struct(self.arch)
+        nbytes = lib.nsr_arch_fused_packed_bytes(ctypes.byref(arch))
+        if nbytes == 0:
+            raise _lib.NsrError(f"nsr_arch_fused_packed_bytes refuses {self.arch}")
+        self._packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)       # the kernel's sticky NSR_FLAG_* word
+        ptrs = (c_void_p * len(dev))(*[c_void_p(dev[k].data_ptr()) for k in self.spec])
+        _lib.check(lib.nsr_arch_fused_pack(ctypes.byref(arch), ptrs, _p(self._packed), _p(self._status), _stream()),
+                   "nsr_arch_fused_pack")
+        if int(self._status.item()) & 1:
+            self._sd = None             # the stream holds the out-of-range network: nothing usable is loaded
+            self._status.zero_()
+            raise _lib.NsrNumericsError(
+                "state_dict cannot be carried at precision 'f16x3': a weight or bias is non-finite or |w| >= 1023.75 (the "
+                "split-fp16 stream holds 2^6 w in fp16); load it with precision='fp32'", 1)
+        self._sd = dev
+        return self
+
     def state_dict(self):
         if self._sd is None:
             raise RuntimeError("no weights loaded")
@@ -407,6 +435,13 @@ class GenericMLP:
 
     # -- numerics status: the reference drops into pdb on NaN colours (models/nerf_downX_model.py:273-274) ---------------------------
     def status(self, clear: bool = False) -> int:
+        if self.fused:                  # the kernel's own status word; waits for the device
+            if self._sd is None:
+                raise RuntimeError("GenericMLP.status called before load_state_dict")
+            flags = int(self._status.item()) & 0xF
+            if clear:
+                self._status.zero_()
+            return flags
         flags = _lib.NSR_FLAG_OUTPUT_NONFINITE if (self._bad is not None and bool(self._bad)) else 0
         if clear and self._bad is not None:
             self._bad.zero_()
@@ -414,6 +449,10 @@ class GenericMLP:
 
     def check(self, what: str = "network"):
         flags = self.status(clear=True)
+        if flags and self.fused:
+            hint = " -- values left the split-fp16 operand range: re-run with precision='fp32'" if flags & 6 else ""
+            raise _lib.NsrNumericsError(f"{what} (fused f16x3): numerics status {flags:#x} = {' | '.join(_lib.flag_names(flags))}{hint}",
+                                        flags)
         if flags:
             raise _lib.NsrNumericsError(f"{what} (layer-by-layer fp32): non-finite network output", flags)
         return self
@@ -439,6 +478,17 @@ class GenericMLP:
             raise ValueError(f"x must be (B, {n_in}), got {tuple(x.shape)}")
         a, B = self.arch, x.shape[0]
         out = torch.empty(B, 1 if sigma_only else a["dim_rgb"] + 1, dtype=torch.float32, device=x.device)
+        if self.fused:                  # one launch per POINT_CHUNK, no intermediate buffers
+            lib, arch = _lib.load(), _arch_struct(a)
+            flags = (_lib.NSR_ARCH_FUSED_SIGMA_ONLY if sigma_only else 0) | \
+                (_lib.NSR_ARCH_FUSED_COLOR_NONE if self.color_activation == "none" else 0)
+            ldx, ldo = x.shape[1], out.shape[1]
+            for r0 in range(0, B, self.POINT_CHUNK):
+                P = min(self.POINT_CHUNK, B - r0)
+                _lib.check(lib.nsr_arch_fused_forward(ctypes.byref(arch), _p(self._packed), c_void_p(x.data_ptr() + 4 * r0 * ldx), ldx,
+                                                      P, flags, c_void_p(out.data_ptr() + 4 * r0 * ldo), ldo, _p(self._status),
+                                                      _stream()), "nsr_arch_fused_forward")
+            return out
         Kx, Wp, Ls = self.Kx, self.Wp, self.Kx + self.Wp
         for r0 in range(0, B, self.POINT_CHUNK):
             xb = x[r0:r0 + self.POINT_CHUNK]
@@ -471,11 +521,42 @@ class GenericMLP:
     __call__ = forward
 
 
-def make_mlp(opt=None, precision: str = "fp32", device="cuda"):
+def _arch_struct(a: dict) -> "_lib.NsrArch":
+    skips = 0
+    for i in a["skips"]:
+        skips |= 1 << int(i)
+    return _lib.NsrArch(a["D"], a["W"], skips, a["deg_pos"], a["deg_dir"], int(bool(a["no_dir"])))
+
+
+def check_arch_fused(arch: dict, precision: str) -> None:
+    """``ValueError`` unless the fused split-fp16 kernel for non-default architectures (nsr_arch_fused_forward,
+    include/nsr_train.h) covers ``arch`` at ``precision``; the message names the limit that is exceeded.  Host only."""
+    if precision != "f16x3":
+        raise ValueError(f"the fused route for non-default architectures is built for precision 'f16x3' only, not {precision!r} "
+                         "(leave fused / arch_fused off to run layer by layer)")
+    arch_spec(**arch)                   # malformed descriptors: D < 1, odd W, a skip outside 1 .. D - 1
+    bad = []
+    for name, lim in (("D", _lib.NSR_ARCH_FUSED_MAX_D), ("W", _lib.NSR_ARCH_FUSED_MAX_W),
+                      ("deg_pos", _lib.NSR_ARCH_FUSED_MAX_DEG_POS), ("deg_dir", _lib.NSR_ARCH_FUSED_MAX_DEG_DIR)):
+        if int(arch[name]) > lim:
+            bad.append(f"{name}={arch[name]} (limit: {name} <= {lim})")
+    if int(arch.get("dim_rgb", 3)) != 3:
+        bad.append(f"dim_rgb={arch['dim_rgb']} (limit: dim_rgb == 3)")
+    if bad:
+        raise ValueError("architecture outside the fused split-fp16 kernel's set: " + ", ".join(bad)
+                         + " (leave fused / arch_fused off to run layer by layer)")
+
+
+def make_mlp(opt=None, precision: str = "fp32", device="cuda", arch_fused: Optional[bool] = None):
     """The network class for an options object: the fused-kernel ``VanillaMLP`` for the architecture every script of the
-    reference uses, ``GenericMLP`` for other ``--D --W --skips`` / degrees / ``dim_rgb``."""
+    reference uses, ``GenericMLP`` for other ``--D --W --skips`` / degrees / ``dim_rgb`` -- layer by layer, or, with
+    ``arch_fused`` (default: ``opt.arch_fused``, off) under precision 'f16x3', in one fused launch (``GenericMLP(fused=True)``)."""
+    if arch_fused is None:
+        arch_fused = bool(getattr(opt, "arch_fused", False)) if opt is not None else False
     if is_default_arch(arch_of(opt)):
         return VanillaMLP(opt, precision=precision, device=device)
+    if arch_fused:
+        return GenericMLP(opt, device=device, precision=precision, fused=True)
     warn_generic_mlp(arch_of(opt), precision)
     return GenericMLP(opt, device=device, precision="f16x3" if precision == "f16x3" else "fp32")
 
