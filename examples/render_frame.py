@@ -40,7 +40,10 @@ def main():
                          "(precision f16x3; the frame is bit-identical)")
     ap.add_argument("--arch", default="", help="'D,W,skips' of a non-default network, skips joined by '+' (e.g. 6,192,1+3)")
     ap.add_argument("--arch-fused", action="store_true",
-                    help="run a non-default --arch in one fused launch per chunk instead of layer by layer (precision f16x3)")
+                    help="run a non-default --arch in one fused launch per pass, encodings computed in the kernel, instead of "
+                         "layer by layer (precision f16x3)")
+    ap.add_argument("--arch-fused-rows", action="store_true",
+                    help="with --arch-fused: the encoded-rows route (posenc + cat, then the same kernel per chunk); same frame")
     a = ap.parse_args()
     arch = {}
     if a.arch:
@@ -55,7 +58,8 @@ def main():
     else:
         sd_c, sd_f = make_state_dict(99), make_state_dict(100)
     opt = default_options(img_wh=tuple(a.wh), downscale=a.downscale, white_bkgd=False, precision=a.precision,
-                          early_stop=a.early_stop, coarse_rgb=a.coarse == "rgb", arch_fused=a.arch_fused, **arch)
+                          early_stop=a.early_stop, coarse_rgb=a.coarse == "rgb", arch_fused=a.arch_fused,
+                          arch_fused_rays=not a.arch_fused_rows, **arch)
     model = NeRFDownXModel(opt, device="cuda").load_networks(sd_c, sd_f).eval()
     res = model.render_image(cameras.spiral_pose(a.pose_t), cameras.llff_focal(a.wh[0]), ndc=True)
     torch.cuda.synchronize()

@@ -258,7 +258,17 @@ int nsr_adam_step_n(int n, const int64_t* numel, float* const* w, const float* c
  *                           out-of-range address).  ORs the sticky NSR_FLAG_INPUT_RANGE (a non-finite input or |x| > 65504),
  *                           NSR_FLAG_ACTIVATION_RANGE (a hidden activation >= 65520) and NSR_FLAG_OUTPUT_NONFINITE into *status
  *                           (a DEVICE word the caller owns and clears; NULL: not reported).  `packed` must be what
- *                           nsr_arch_fused_pack wrote for the same descriptor. */
+ *                           nsr_arch_fused_pack wrote for the same descriptor.
+ *   nsr_arch_fused_render_rays  the same launch on rays and depths, the encodings computed in the kernel: rays (R, ray_stride),
+ *                           stride 8 [o, d, near, far] (the direction that is encoded is d; 16-byte aligned) or 11 (the encoded
+ *                           direction in columns 8:11), z (R, n_samples) -> out (R n_samples, ldo) = [rgb, sigma] per sample point
+ *                           (sigma alone under NSR_ARCH_FUSED_SIGMA_ONLY).  Point k of ray r is o + z[r, k] d (separate multiply and
+ *                           add, as nsr_sample_along_rays writes it); its encodings are nsr_posenc's values, so the output and the
+ *                           status bits are those of nsr_arch_fused_forward on the rows cat([posenc(points), posenc(direction)
+ *                           repeated]), bit for bit, without those rows ever being written.  Any n_samples >= 1, any R >= 0 (R == 0:
+ *                           NSR_OK, nothing enqueued).  NSR_ERR_INVALID_ARG, before anything is enqueued: another flag bit, a stride
+ *                           other than 8 or 11, misaligned rays at stride 8, n_samples <= 0, R < 0, a NULL packed / rays / z / out,
+ *                           ldo < 4 (< 1 under sigma-only), more than 2^31 - 1 tiles of 128 points.  flags, packed, status: as above. */
 #define NSR_ARCH_FUSED_SIGMA_ONLY 1
 #define NSR_ARCH_FUSED_COLOR_NONE 2
 #define NSR_ARCH_FUSED_MAX_D 8
@@ -269,6 +279,8 @@ size_t nsr_arch_fused_packed_bytes(const nsr_arch* arch);
 int nsr_arch_fused_pack(const nsr_arch* arch, const float* const* w, void* packed, unsigned* status, void* stream);
 int nsr_arch_fused_forward(const nsr_arch* arch, const void* packed, const float* x, int64_t ldx, int64_t P, int flags, float* out,
                            int64_t ldo, unsigned* status, void* stream);
+int nsr_arch_fused_render_rays(const nsr_arch* arch, const void* packed, const float* rays, int ray_stride, const float* z, int64_t R,
+                               int n_samples, int flags, float* out, int64_t ldo, unsigned* status, void* stream);
 
 /* One nn.Linear (+ activation) on the training GEMM, exposed for testing the kernel on its own:
  *   y (P, N) = act(x (P, K) · w (N, K)^T + b),  act: 0 none, 1 relu, 2 sigmoid;  y_t (N, P) optional transpose.

@@ -141,6 +141,8 @@ SIGNATURES = {
     "nsr_arch_fused_pack": (c_int, [POINTER(NsrArch), POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
     "nsr_arch_fused_forward": (c_int, [POINTER(NsrArch), c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p,
                                        c_void_p]),
+    "nsr_arch_fused_render_rays": (c_int, [POINTER(NsrArch), c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                           c_int64, c_void_p, c_void_p]),
     # ---- include/nsr_warp.h
     "nsr_depth_warp": (c_int, [c_void_p, c_int, c_int, c_double, POINTER(c_float), POINTER(c_double), c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p]),

@@ -21,6 +21,12 @@
 // 0 .. D-1, sigma, xyz_encoding_final, dir_encoding, rgb.  A workgroup is four waves = 128 points sharing the chunks through a
 // two-slot LDS ring: while chunk j is consumed, every wave's LDS-DMA of its quarter of chunk j+1 is in flight; one
 // (wait for the own DMA, barrier) per chunk publishes j+1 and frees the slot of j.
+//
+// Input modes (template parameter MODE, as encode_point<MODE> of nsr_mlp_encode.h): 0 reads the encoded rows x; 1
+// (nsr_arch_fused_render_rays) takes rays (R, 8 | 11) and z (R, n_samples) -- point p is sample p % n_samples of ray
+// p / n_samples, a tile may straddle rays -- forms o + z d and computes, in registers, exactly the encoded columns the lane
+// would have loaded in mode 0, by the expression of the stand-alone encoder (nsr_posenc), so both modes feed the same bits to
+// the same network code.
 #include "nsr_f16x3_core.h"
 #include "../../include/nsr_train.h"
 
@@ -127,6 +133,9 @@ struct FusedArgs {
   int D;
   unsigned skips;
   int in_xyz, in_dir, kxb, no_dir, sigma_only, color_none;
+  const float* rays;      // MODE 1: (R, ray_stride) ray records and (R, n_samples) depths instead of x; P = R * n_samples
+  const float* z;
+  int ray_stride, n_samples;
 };
 
 template <int N>
@@ -259,7 +268,44 @@ __device__ __forceinline__ void load_block(const float* __restrict__ row, int kb
     }
 }
 
-template <int NB>
+// MODE 1: column c of [v, sin(2^0 v), cos(2^0 v), sin(2^1 v), ...] for the 3-vector v.  This is posenc_kernel's expression
+// (nsr_rays.hip: sinf / cosf of the exact ldexpf argument, NOT nsr_sincos, whose values differ from it in the last bits): the
+// row route feeds the network what that kernel wrote, and the two routes promise the same bits.  Both functions are
+// evaluated and one is selected: the halves of a wave hold columns 4 apart, which mix sines and cosines, and the two share
+// their argument reduction.
+__device__ __forceinline__ float encoded_column(float v0, float v1, float v2, int c) {
+  const int u = c < 3 ? c : c - 3;
+  const int f = u / 6, r = u - 6 * f, comp = r < 3 ? r : r - 3;
+  const float x = comp == 0 ? v0 : (comp == 1 ? v1 : v2);
+  if (c < 3) return x;
+  const float arg = ldexpf(x, f);                      // 2^f * x, exact
+  const float sn = sinf(arg), cs = cosf(arg);
+  return r < 3 ? sn : cs;
+}
+
+// load_block without the row: the same 32 columns of the encoding of v, in the same registers, under the same range test
+__device__ __forceinline__ void encode_block(float v0, float v1, float v2, int kb, int n_cols, int h, u32x4 (&hi)[2], u32x4 (&lo)[2],
+                                             bool& ok) {
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int c0 = 32 * kb + 16 * s + 8 * (jj >> 1) + 2 * (jj & 1);                // the column of lane half 0: wave-uniform
+      const int c = c0 + 4 * h;
+      float f0 = 0.0f, f1 = 0.0f;
+      if (c0 < n_cols) {                               // a pair past the encoding in both halves costs nothing
+        f0 = c < n_cols ? encoded_column(v0, v1, v2, c) : 0.0f;
+        f1 = c + 1 < n_cols ? encoded_column(v0, v1, v2, c + 1) : 0.0f;
+      }
+      ok = ok && fabsf(f0) <= 65504.0f && fabsf(f1) <= 65504.0f;                    // false for NaN
+      unsigned a, b;
+      split2_pk(f0, f1, a, b);
+      hi[s][jj] = a;
+      lo[s][jj] = b;
+    }
+}
+
+template <int NB, int MODE>
 __global__ void __launch_bounds__(256) arch_fused_kernel(FusedArgs a) {
   constexpr int HB = (NB + 1) / 2;
   constexpr int kSlot = chunk_pieces(NB + 2) * 1024;
@@ -277,16 +323,29 @@ __global__ void __launch_bounds__(256) arch_fused_kernel(FusedArgs a) {
 
   const int64_t p = (int64_t)blockIdx.x * kFusedTile + 32 * ring.wave + m;
   const bool valid = p < a.P;
-  const float* xr = a.x + (valid ? p : a.P - 1) * a.ldx;      // a tail lane re-reads the last row; its results are dropped
   unsigned flags = 0u;
   Act<2> pe;
   Act<1> de;
-  {
+  if (MODE == 0) {
+    const float* xr = a.x + (valid ? p : a.P - 1) * a.ldx;      // a tail lane re-reads the last row; its results are dropped
     bool ok = true;
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) load_block(xr, kb, a.in_xyz, h, pe.hi[kb], pe.lo[kb], ok);
     const bool with_dir = !a.sigma_only && !a.no_dir;
     load_block(xr + a.in_xyz, 0, with_dir ? a.in_dir : 0, h, de.hi[0], de.lo[0], ok);
+    if (!ok) flags |= NSR_FLAG_INPUT_RANGE;
+  } else {
+    const int64_t pc = valid ? p : a.P - 1;                     // a tail lane re-reads the last point (its ray and its z)
+    const NsrRay rq = nsr_load_ray(a.rays, pc / a.n_samples, a.ray_stride);
+    const float zk = a.z[pc];
+    // cast_rays with a separate multiply and add, as sample_kernel / resample_kernel write the points of the row route
+    const float v0 = __fadd_rn(rq.o[0], __fmul_rn(zk, rq.d[0])), v1 = __fadd_rn(rq.o[1], __fmul_rn(zk, rq.d[1])),
+                v2 = __fadd_rn(rq.o[2], __fmul_rn(zk, rq.d[2]));
+    bool ok = true;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb) encode_block(v0, v1, v2, kb, a.in_xyz, h, pe.hi[kb], pe.lo[kb], ok);
+    const bool with_dir = !a.sigma_only && !a.no_dir;
+    encode_block(rq.v[0], rq.v[1], rq.v[2], 0, with_dir ? a.in_dir : 0, h, de.hi[0], de.lo[0], ok);   // the direction that is ENCODED
     if (!ok) flags |= NSR_FLAG_INPUT_RANGE;
   }
   ring_advance(ring, chunk_pieces(a.kxb));
@@ -376,10 +435,19 @@ __global__ void __launch_bounds__(256) arch_fused_kernel(FusedArgs a) {
   }
 }
 
-template <int NB>
-void launch_fused(const FusedArgs& a, hipStream_t st) {
-  const unsigned grid = (unsigned)((a.P + kFusedTile - 1) / kFusedTile);
-  hipLaunchKernelGGL(arch_fused_kernel<NB>, dim3(grid), dim3(256), 0, st, a);
+template <int MODE>
+void launch_fused(int NB, const FusedArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)((a.P + kFusedTile - 1) / kFusedTile)), block(256);
+  switch (NB) {
+    case 1: hipLaunchKernelGGL((arch_fused_kernel<1, MODE>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((arch_fused_kernel<2, MODE>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((arch_fused_kernel<3, MODE>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((arch_fused_kernel<4, MODE>), grid, block, 0, st, a); break;
+    case 5: hipLaunchKernelGGL((arch_fused_kernel<5, MODE>), grid, block, 0, st, a); break;
+    case 6: hipLaunchKernelGGL((arch_fused_kernel<6, MODE>), grid, block, 0, st, a); break;
+    case 7: hipLaunchKernelGGL((arch_fused_kernel<7, MODE>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((arch_fused_kernel<8, MODE>), grid, block, 0, st, a); break;
+  }
 }
 
 }  // namespace
@@ -448,17 +516,34 @@ extern "C" int nsr_arch_fused_forward(const nsr_arch* arch, const void* packed, 
   a.D = S.D; a.skips = S.skips; a.in_xyz = S.in_xyz; a.in_dir = S.in_dir; a.kxb = S.KXB; a.no_dir = S.no_dir;
   a.sigma_only = sigma_only ? 1 : 0;
   a.color_none = (flags & NSR_ARCH_FUSED_COLOR_NONE) ? 1 : 0;
-  hipStream_t st = nsr_stream(stream);
-  switch (S.NB) {
-    case 1: launch_fused<1>(a, st); break;
-    case 2: launch_fused<2>(a, st); break;
-    case 3: launch_fused<3>(a, st); break;
-    case 4: launch_fused<4>(a, st); break;
-    case 5: launch_fused<5>(a, st); break;
-    case 6: launch_fused<6>(a, st); break;
-    case 7: launch_fused<7>(a, st); break;
-    default: launch_fused<8>(a, st); break;
-  }
+  a.rays = nullptr; a.z = nullptr; a.ray_stride = 0; a.n_samples = 0;
+  launch_fused<0>(S.NB, a, nsr_stream(stream));
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
+extern "C" int nsr_arch_fused_render_rays(const nsr_arch* arch, const void* packed, const float* rays, int ray_stride, const float* z,
+                                          int64_t R, int n_samples, int flags, float* out, int64_t ldo, unsigned* status,
+                                          void* stream) {
+  FusedShape S;
+  const int rc = fused_shape(arch, S);
+  if (rc != NSR_OK) return rc;
+  if ((flags & ~(NSR_ARCH_FUSED_SIGMA_ONLY | NSR_ARCH_FUSED_COLOR_NONE)) != 0) return NSR_ERR_INVALID_ARG;
+  const bool sigma_only = (flags & NSR_ARCH_FUSED_SIGMA_ONLY) != 0;
+  if (!nsr_ray_stride_ok(ray_stride) || n_samples <= 0 || R < 0) return NSR_ERR_INVALID_ARG;
+  if (!packed || (reinterpret_cast<uintptr_t>(packed) & 15) != 0 || !rays || !z || !out || ldo < (sigma_only ? 1 : 4))
+    return NSR_ERR_INVALID_ARG;
+  if (ray_stride == 8 && (reinterpret_cast<uintptr_t>(rays) & 15) != 0) return NSR_ERR_INVALID_ARG;      // nsr_load_ray's float4 loads
+  if (R > (0x7fffffffLL * kFusedTile) / n_samples) return NSR_ERR_INVALID_ARG;      // more than 2^31 - 1 tiles (and no overflow below)
+  if (R == 0) return NSR_OK;
+  FusedArgs a;
+  a.stream = static_cast<const char*>(packed);
+  a.x = nullptr; a.ldx = 0; a.P = R * n_samples; a.out = out; a.ldo = ldo; a.status = status;
+  a.D = S.D; a.skips = S.skips; a.in_xyz = S.in_xyz; a.in_dir = S.in_dir; a.kxb = S.KXB; a.no_dir = S.no_dir;
+  a.sigma_only = sigma_only ? 1 : 0;
+  a.color_none = (flags & NSR_ARCH_FUSED_COLOR_NONE) ? 1 : 0;
+  a.rays = rays; a.z = z; a.ray_stride = ray_stride; a.n_samples = n_samples;
+  launch_fused<1>(S.NB, a, nsr_stream(stream));
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }

@@ -31,6 +31,8 @@ def default_options(**kw) -> SimpleNamespace:
         early_stop=0.0,         # eval mode, precision 'f16x3': early ray termination at this transmittance (0 = off; include/nsr.h)
         coarse_rgb=True,        # False: test-time mode, eval + 'f16x3' -- the coarse pass computes densities only (include/nsr.h)
         arch_fused=False,       # True: a non-default D / W / skips / degrees runs in ONE fused launch under 'f16x3' (ops.GenericMLP(fused=True))
+        arch_fused_rays=True,   # with arch_fused: that launch takes (rays, z) and encodes in the kernel (ops.render_rays); False: the
+                                # encoded-rows route (posenc + cat in HBM, then the same kernel) -- the same bits, kept for A/B runs
     )
     for k, v in kw.items():
         setattr(opt, k, v)
@@ -56,6 +58,8 @@ class NeRFDownXModel:
         self.netCoarse = ops.make_mlp(self.opt, precision=self.opt.precision, device=self.device)
         self.netFine = ops.make_mlp(self.opt, precision=self.opt.precision, device=self.device)
         self.fused = isinstance(self.netCoarse, VanillaMLP)
+        # a GenericMLP pair on the fused descriptor kernel: its network passes can take (rays, z) too (opt.arch_fused_rays)
+        self.arch_fused = isinstance(self.netCoarse, GenericMLP) and self.netCoarse.fused and self.netFine.fused
         self.models = {"coarse": self.netCoarse, "fine": self.netFine}
         self.embeddings = {"pos": PositionalEncoding(3, self.opt.deg_pos), "dir": PositionalEncoding(3, self.opt.deg_dir)}
         self.randomized = False
@@ -141,6 +145,14 @@ class NeRFDownXModel:
             rgb = torch.pow(rgb, 1.0 / 2.2)
         return rgb, out[..., 3]
 
+    def _render_by_rays(self, model, rays: torch.Tensor, z: torch.Tensor):
+        """``ops.render_rays`` -- no encoded row exists on this route -- plus, for a ``GenericMLP``, the ``pow(rgb, 1 / 2.2)``
+        of ``gamma_correct`` that ``render_rays`` above applies (its fused kernel has no colour-head option for it)."""
+        rgb, sig = ops.render_rays(model, rays, z)
+        if isinstance(model, GenericMLP) and model.gamma_correct:
+            rgb = torch.pow(rgb, 1.0 / 2.2)
+        return rgb, sig
+
     # -- D3 ------------------------------------------------------------------------
     def forward_rays(self, rays: torch.Tensor, coarse_rgb: Optional[bool] = None) -> Dict[str, torch.Tensor]:
         """``opt.early_stop`` applies to the eval-mode forward only (the fine pass, include/nsr.h); ``train()`` mode ignores it.
@@ -162,9 +174,12 @@ class NeRFDownXModel:
         o, d, near, far = rays[:, 0:3], rays[:, 3:6], rays[:, 6:7], rays[:, 7:8]
         rnd = self.randomized
         z, xyz = ops.sample_along_rays(o, d, near, far, opt.N_coarse, rnd, opt.lindisp)
-        if not self.fused:
+        # the ray-level launch (encodings in the kernel): the default pair, and a fused GenericMLP pair unless the option
+        # asks for the encoded-rows route; read at call time, so both routes can be timed in one process
+        by_rays = self.fused or (self.arch_fused and bool(getattr(opt, "arch_fused_rays", True)))
+        if not by_rays:
             dir_emb = self.embeddings["dir"]((rays[:, 8:11] if rays.shape[1] == 11 else d).contiguous())
-        rgb, sig = ops.render_rays(self.netCoarse, rays, z) if self.fused else self.render_rays(self.netCoarse, xyz, dir_emb)
+        rgb, sig = self._render_by_rays(self.netCoarse, rays, z) if by_rays else self.render_rays(self.netCoarse, xyz, dir_emb)
         rgb, sig = rgb.contiguous(), sig.contiguous()
         if rnd and opt.noise_std > 0:          # add_gaussian_noise (models/utils.py:199-212): only when randomized
             sig = sig + torch.randn_like(sig) * opt.noise_std
@@ -172,7 +187,7 @@ class NeRFDownXModel:
         out = dict(zip(ops.OUT_KEYS[:4], c))
         if opt.N_importance > 0:
             z2, xyz2 = ops.resample_along_rays(o, d, z, c[3], opt.N_importance, rnd)
-            rgb2, sig2 = ops.render_rays(self.netFine, rays, z2) if self.fused else self.render_rays(self.netFine, xyz2, dir_emb)
+            rgb2, sig2 = self._render_by_rays(self.netFine, rays, z2) if by_rays else self.render_rays(self.netFine, xyz2, dir_emb)
             rgb2, sig2 = rgb2.contiguous(), sig2.contiguous()
             if rnd and opt.noise_std > 0:
                 sig2 = sig2 + torch.randn_like(sig2) * opt.noise_std

@@ -20,7 +20,7 @@ from .weights import (STATE_DICT_SPEC, check_state_dict, pad_no_dir, DIR_W, IN_C
 
 __all__ = [
     "subpixel_rays", "PositionalEncoding", "sample_along_rays", "resample_along_rays", "cast_rays",
-    "VanillaMLP", "VolumetricRenderer", "check_mlp_options", "render_rays", "render_rays_composited", "forward_rays", "sr_mean", "unflatten_reshape",
+    "VanillaMLP", "VolumetricRenderer", "check_mlp_options", "render_rays", "render_rays_sigma", "render_rays_composited", "forward_rays", "sr_mean", "unflatten_reshape",
 ]
 
 
@@ -616,10 +616,43 @@ class VolumetricRenderer:
 
 
 # ----------------------------------------------------------------------------- D2 / D3
-def render_rays(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.Tensor):
+def _arch_render_rays(model: "GenericMLP", rays: torch.Tensor, z_vals: torch.Tensor, sigma_only: bool) -> torch.Tensor:
+    """One ``nsr_arch_fused_render_rays`` launch over all R * N sample points (not chunked: there are no encoded rows whose
+    size a chunk would bound) -> the (R, N, 4) buffer, or (R, N, 1) under ``sigma_only``."""
+    if not isinstance(model, GenericMLP):
+        raise TypeError(f"render_rays takes a VanillaMLP or a GenericMLP built with fused=True, not {type(model).__name__}")
+    if not model.fused:
+        raise ValueError("render_rays needs the fused kernels: this GenericMLP runs layer by layer (built without fused=True) -- "
+                         "use the explicit route, model(cat([PositionalEncoding(points), PositionalEncoding(dirs) repeated]))")
+    if model._sd is None:
+        raise RuntimeError("render_rays called before load_state_dict")
+    rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
+    stride = _ray_stride(rays)
+    if z_vals.ndim != 2 or z_vals.shape[0] != rays.shape[0] or z_vals.shape[1] < 1:
+        raise ValueError(f"z_vals must be (R, N >= 1) with R = {rays.shape[0]} rays, got {tuple(z_vals.shape)}")
+    R, N = z_vals.shape
+    raw = torch.empty(R, N, 1 if sigma_only else 4, dtype=torch.float32, device=rays.device)
+    flags = (_lib.NSR_ARCH_FUSED_SIGMA_ONLY if sigma_only else 0) | \
+        (_lib.NSR_ARCH_FUSED_COLOR_NONE if model.color_activation == "none" else 0)
+    arch = _arch_struct(model.arch)
+    _lib.check(_lib.load().nsr_arch_fused_render_rays(ctypes.byref(arch), _p(model._packed), _p(rays), stride, _p(z_vals), R, N, flags,
+                                                      _p(raw), raw.shape[2], _p(model._status), _stream()),
+               "nsr_arch_fused_render_rays")
+    return raw
+
+
+def render_rays(model, rays: torch.Tensor, z_vals: torch.Tensor):
     """Fused render_rays (models/nerf_downX_model.py:260-278): MLP at every sample of
     every ray, positional encodings computed in-kernel.  rays (R,8), z (R,N) ->
-    ``(rgbs (R,N,3), sigmas (R,N))`` as views of one (R,N,4) buffer."""
+    ``(rgbs (R,N,3), sigmas (R,N))`` as views of one (R,N,4) buffer.
+
+    ``model``: a ``VanillaMLP``, or a ``GenericMLP`` built with ``fused=True`` (nsr_arch_fused_render_rays: one launch for
+    all R * N points, bit-identical to the network on the explicitly encoded rows, ``color_activation none`` and the
+    network's status word as there; ``gamma_correct`` stays the caller's, as on the explicit route).  A layer-by-layer
+    ``GenericMLP`` has no ray-level kernel: ``ValueError``."""
+    if isinstance(model, GenericMLP):
+        raw = _arch_render_rays(model, rays, z_vals, False)
+        return raw[..., :3], raw[..., 3]
     rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
     R, N = z_vals.shape
     stride = _ray_stride(rays)
@@ -627,6 +660,13 @@ def render_rays(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.Tensor):
     _lib.check(_lib.load().nsr_render_rays(_p(model.packed), model._prec, _p(rays), stride, _p(z_vals), R, N, _p(raw),
                                            _stream()), "nsr_render_rays")
     return raw[..., :3], raw[..., 3]
+
+
+def render_rays_sigma(model: "GenericMLP", rays: torch.Tensor, z_vals: torch.Tensor) -> torch.Tensor:
+    """The density-only form of ``render_rays`` for a fused ``GenericMLP`` (the reference's ``sigma_only``,
+    models/networks.py:182-226): trunk and density head, no colour branch, no direction encoding -> sigmas (R, N), the
+    bits of ``render_rays(...)[1]``."""
+    return _arch_render_rays(model, rays, z_vals, True)[..., 0]
 
 
 def check_early_stop(early_stop: float, net, n_last: int, sigma_activation: str = "relu") -> float:
