@@ -26,6 +26,7 @@ NSR_ARCH_FUSED_MAX_D, NSR_ARCH_FUSED_MAX_W, NSR_ARCH_FUSED_MAX_DEG_POS, NSR_ARCH
 NSR_OPT_GAMMA, NSR_OPT_COLOR_NONE = 1, 2     # include/nsr.h: colour-head option word (nsr_weights_set_options)
 NSR_WHITE_BKGD, NSR_SIGMA_SOFTPLUS = 1, 2    # include/nsr.h: renderer option word (the `white_bkgd` argument)
 NSR_LAYOUT_BCHW, NSR_LAYOUT_BHWC = 0, 1      # include/nsr_metrics.h: memory order of nsr_ssim's images
+NSR_LOSS_TV, NSR_LOSS_GRADIENT, NSR_LOSS_LAPLACIAN = 0, 1, 2     # include/nsr_losses.h: `kind` of nsr_loss_workspace_bytes
 NSR_TRAIN_GAMMA_CORRECT, NSR_TRAIN_COLOR_NONE, NSR_TRAIN_STOP_GRAD = 4, 8, 16    # include/nsr_train.h: the training entry points' own bits of that word
 PRECISIONS = {"fp32": NSR_FP32, "bf16": NSR_BF16, "f16x3": NSR_F16X3, "f16": NSR_F16}
 NSR_F16X3_BWD3, NSR_F16X3_BWD2, NSR_F16X3_BWD1, NSR_F16X3_BWDM = 19, 20, 21, 22   # chain path, MFMAs per product of the backward chain named explicitly
@@ -195,6 +196,14 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nsr_psnr_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "nsr_psnr": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ---- include/nsr_losses.h
+    "nsr_loss_workspace_bytes": (c_size_t, [c_int, c_int64, c_int, c_int, c_int]),
+    "nsr_tv_loss": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nsr_tv_loss_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "nsr_gradient_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nsr_gradient_loss_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nsr_laplacian_loss": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nsr_laplacian_loss_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -38,6 +38,7 @@ UNITS = [
     ("nsr_refine_train.hip", ["-ffp-contract=off"]),
     ("nsr_image.hip", ["-ffp-contract=off"]),
     ("nsr_metrics.hip", ["-ffp-contract=off"]),
+    ("nsr_losses.hip", ["-ffp-contract=off"]),
     ("nsr_data.hip", ["-ffp-contract=off"]),
     ("nsr_refine_data.hip", ["-ffp-contract=off"]),
     ("nsr_api.hip", []),

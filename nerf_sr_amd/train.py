@@ -599,15 +599,21 @@ class Trainer:
         torch._foreach_mul_(grads, coef)
         return total
 
-    def regularize_patch(self, patch_rays: torch.Tensor, patch_len: int, reg_lambda_tv: float = 1.0, draws=None):
+    def regularize_patch(self, patch_rays: torch.Tensor, patch_len: int, reg_lambda_tv: float = 1.0, draws=None,
+                         fused_tv: bool = False):
         """The reference's patch regulariser iteration (``regularize_patch``, models/nerf_downX_model.py:596-618, called from
         train.py when --reg_patch is on): render a (patch_len * downscale)^2 HR patch (rays in raster order), total-variation
         loss of its coarse and fine colours (``tv_loss``) times ``reg_lambda_tv``, backward, its own Adam step.  Returns the
-        device tensor [tv_coarse, tv_fine] (before the lambda)."""
+        device tensor [tv_coarse, tv_fine] (before the lambda).  ``fused_tv``: the two losses and their gradients through
+        ``losses.TVLoss`` (two launches forward, one backward, double arithmetic) instead of the chain of torch ops."""
         side = int(patch_len) * int(round(self.s2 ** 0.5))
         out = self.forward(draws, rays=patch_rays)
-        loss_c = tv_loss(out["coarse_comp_rgbs"].view(side, side, -1))
-        loss_f = tv_loss(out["fine_comp_rgbs"].view(side, side, -1))
+        tv = tv_loss
+        if fused_tv:
+            from .losses import TVLoss
+            tv = TVLoss()
+        loss_c = tv(out["coarse_comp_rgbs"].view(side, side, -1))
+        loss_f = tv(out["fine_comp_rgbs"].view(side, side, -1))
         self.backward((loss_c + loss_f) * reg_lambda_tv)
         self.all_reduce_grads()
         self.optimizer_step()
