@@ -151,6 +151,11 @@ if os.path.exists(_CHAIN_HOOKS_SRC):
 _HEADS_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_heads.hip")
 if os.path.exists(_HEADS_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_HEADS_HOOKS_SRC)
+# ... and the launchers of the refinement network's train-mode kernels, csrc/nsr_refine_train_work.h
+# (tests/test_gpu_refine_units.py); linked on the same condition
+_REFINE_TRAIN_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_train.hip")
+if os.path.exists(_REFINE_TRAIN_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_REFINE_TRAIN_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -22,6 +22,7 @@
 // dZ carries 32 zeroed rows behind its last one, D.conv9's dZ is 32 columns wide (3 real) and the re-laid weight has
 // pad32(Cout) rows, the padding ones zero.
 #include "nsr_refine_conv.h"
+#include "nsr_refine_train_work.h"
 
 using namespace nsr;
 
@@ -31,7 +32,7 @@ constexpr int kNL = NSR_REFINE_N_LAYERS;
 constexpr int kNSites = 26;              // 7 (encoder, synthesised) + 7 (encoder, references) + 12 (decoder)
 constexpr int kKpMax = 13824;            // 9 x 1536: D.conv3
 constexpr int kCMax = 512;
-constexpr int kMaxParts = 256;           // row partitions of a per-channel reduction
+constexpr int kMaxParts = kRefineMaxParts;   // row partitions of a per-channel reduction
 constexpr int kMaxSplits = 64;
 constexpr int kFwdKChunk = 32;          // forward: K summed by the MFMA in chains of 32 (one K tile), the chains added in double
 constexpr int64_t kPartFloats = (int64_t)8 * kCMax * kKpMax;   // split-K partials of one weight gradient
@@ -76,18 +77,7 @@ __device__ __forceinline__ float bn_act(float z, float mean, float rstd, float g
   return nsr_relu_nan(__fadd_rn(__fmul_rn(__fmul_rn(__fsub_rn(z, mean), rstd), g), b));
 }
 
-// Per-channel sums over the rows of a (rows x C) matrix, partition `blockIdx.y` of `nparts`: part[(v * nparts + p) * C + c].
-//   MODE 0: sum of x                      (x: ld = ldx)
-//   MODE 1: sum of (x - mean[c])^2
-//   MODE 2: v = 0: sum of dy, v = 1: sum of dy * xhat, dy = dA * [bn_act(x) > 0]   (BatchNorm backward)
-struct ReduceArgs {
-  const float* x; int64_t ldx;
-  const float* da; int64_t ldda;
-  const float* stat;                 // mean[C], rstd[C]
-  const float *gamma, *beta;
-  int64_t rows; int C, nparts;
-  float* part;
-};
+// Per-channel sums over the rows of a (rows x C) matrix (ReduceArgs and its three modes: nsr_refine_train_work.h)
 template <int MODE>
 __global__ void __launch_bounds__(256) col_reduce_kernel(ReduceArgs a) {
   __shared__ float sh[2][4][64];
@@ -333,6 +323,111 @@ __global__ void header_kernel(Header h, unsigned* __restrict__ dst) {
 
 inline dim3 blocks(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------
+// launchers (nsr_refine_train_work.h): the only places the kernels above are launched from
+// ---------------------------------------------------------------------------------------------------------------
+namespace nsr {
+
+int refine_col_reduce(hipStream_t st, int mode, ReduceArgs a) {
+  a.nparts = refine_reduce_parts(a.rows);
+  const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)a.nparts);
+  if (mode == 0) hipLaunchKernelGGL(col_reduce_kernel<0>, grid, dim3(256), 0, st, a);
+  else if (mode == 1) hipLaunchKernelGGL(col_reduce_kernel<1>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(col_reduce_kernel<2>, grid, dim3(256), 0, st, a);
+  NSR_CHECK_LAUNCH();
+  return a.nparts;
+}
+int refine_fin_mean(hipStream_t st, const float* part, int nparts, int C, int64_t rows, float momentum, float* stat, float* run_mean) {
+  hipLaunchKernelGGL(fin_mean_kernel, dim3((C + 255) / 256), dim3(256), 0, st, part, nparts, C, rows, momentum, stat, run_mean);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_fin_var(hipStream_t st, const float* part, int nparts, int C, int64_t rows, float momentum, float eps, float* stat,
+                   float* run_var) {
+  hipLaunchKernelGGL(fin_var_kernel, dim3((C + 255) / 256), dim3(256), 0, st, part, nparts, C, rows, momentum, eps, stat, run_var);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_fin_bn_bwd(hipStream_t st, const float* part, int nparts, int C, int64_t rows, int acc, float* g_gamma, float* g_beta,
+                      float* m) {
+  hipLaunchKernelGGL(fin_bn_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, part, nparts, C, rows, acc, g_gamma, g_beta, m);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_fin_bias(hipStream_t st, const float* part, int nparts, int C, int n_valid, int acc, float* g_bias) {
+  hipLaunchKernelGGL(fin_bias_kernel, dim3((C + 255) / 256), dim3(256), 0, st, part, nparts, C, n_valid, acc, g_bias);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_bn_relu(hipStream_t st, const float* z, const float* stat, const float* gamma, const float* beta, int64_t rows, int C,
+                   float* dst, int64_t ld) {
+  hipLaunchKernelGGL(bn_relu_kernel, blocks(rows * (C / 4)), dim3(256), 0, st, z, stat, gamma, beta, rows, C, dst, ld);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_bn_bwd(hipStream_t st, const float* z, const float* da, int64_t ldda, const float* stat, const float* gamma,
+                  const float* beta, const float* m, int64_t rows, int C, float* dz) {
+  hipLaunchKernelGGL(bn_bwd_kernel, blocks(rows * (C / 4)), dim3(256), 0, st, z, da, ldda, stat, gamma, beta, m, rows, C, dz);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_relu_bwd(hipStream_t st, const float* a, const float* da, int64_t n, float* dz) {
+  hipLaunchKernelGGL(relu_bwd_kernel, blocks(n), dim3(256), 0, st, a, da, n, dz);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_tanh_bwd(hipStream_t st, const float* y, const float* g_out, int64_t px_per_img, int64_t rows, float* dz) {
+  hipLaunchKernelGGL(tanh_bwd_kernel, blocks(rows * 32), dim3(256), 0, st, y, g_out, px_per_img, rows, dz);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_max_idx(hipStream_t st, const float* src, int C, int R, int64_t px_per_img, int B, float* dst, int64_t ld,
+                   unsigned char* win) {
+  const int64_t n = (int64_t)B * px_per_img * C;
+  hipLaunchKernelGGL(max_idx_kernel, blocks(n), dim3(256), 0, st, src, C, R, px_per_img, n, dst, ld, win);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_route(hipStream_t st, const float* g_max, int64_t ld, const unsigned char* win, int C, int R, int64_t px_per_img, int B,
+                 float* g_fc) {
+  const int64_t n = (int64_t)B * px_per_img * C;
+  hipLaunchKernelGGL(route_kernel, blocks(n), dim3(256), 0, st, g_max, ld, win, C, R, px_per_img, n, g_fc);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_col2im(hipStream_t st, const float* dcol, int kp, int cin, int n_img, int Hs, int Ws, int stride, int up, int Ho, int Wo,
+                  int acc, float* dst, int64_t ld) {
+  const int64_t n = (int64_t)n_img * Hs * Ws * (cin / 4);
+  hipLaunchKernelGGL(col2im_kernel, blocks(n), dim3(256), 0, st, dcol, kp, cin, n_img, Hs, Ws, stride, up, Ho, Wo, acc, dst, ld);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_wgrad_reduce(hipStream_t st, const float* part, int splits, int64_t split_stride, int kp, int cin, int cout, int acc,
+                        float* g) {
+  hipLaunchKernelGGL(wgrad_reduce_kernel, blocks((int64_t)cout * cin * 9), dim3(256), 0, st, part, splits, split_stride, kp, cin, cout,
+                     acc, g);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_fwd_reduce(hipStream_t st, const float* part, int splits, int64_t split_stride, int np, int cout, const float* bias, int act,
+                      int64_t M, float* dst, int64_t ld) {
+  hipLaunchKernelGGL(fwd_reduce_kernel, blocks(M * cout), dim3(256), 0, st, part, splits, split_stride, np, cout, bias, act, M, dst, ld);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int refine_nhwc3_to_nchw(hipStream_t st, const float* src, int64_t px_per_img, int B, float* dst) {
+  const int64_t n = (int64_t)B * 3 * px_per_img;
+  hipLaunchKernelGGL(nhwc3_to_nchw_kernel, blocks(n), dim3(256), 0, st, src, px_per_img, n, dst);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
+}  // namespace nsr
+
+namespace {
+
 // ---------------------------------------------------------------------------------------------------------------
 // layouts
 // ---------------------------------------------------------------------------------------------------------------
@@ -540,19 +635,9 @@ int im2col(hipStream_t st, const Site& s, const Geo& g, const float* x_nchw, int
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
-int reduce(hipStream_t st, int mode, ReduceArgs a) {
-  const int64_t want = (a.rows + 63) / 64;
-  a.nparts = (int)(want > kMaxParts ? kMaxParts : want);
-  const dim3 grid((unsigned)((a.C + 63) / 64), (unsigned)a.nparts);
-  if (mode == 0) hipLaunchKernelGGL(col_reduce_kernel<0>, grid, dim3(256), 0, st, a);
-  else if (mode == 1) hipLaunchKernelGGL(col_reduce_kernel<1>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(col_reduce_kernel<2>, grid, dim3(256), 0, st, a);
-  NSR_CHECK_LAUNCH();
-  return a.nparts;
-}
 #define NSR_REDUCE(np_, ...)          \
   do {                                \
-    np_ = reduce(__VA_ARGS__);        \
+    np_ = refine_col_reduce(__VA_ARGS__); \
     if (np_ < 0) return np_;          \
   } while (0)
 
@@ -580,9 +665,8 @@ int site_forward(hipStream_t st, const Site& s, const float* const* t, float* co
       a.A = w.col + m0 * g.kp; a.lda = g.kp; a.B = w.wr; a.ldb = g.kp; a.C = w.dcol; a.ldc = g.np;
       a.M = mb; a.N = g.np; a.K = g.kp; a.n_valid = L.cout; a.act = kActNone; a.splits = splits; a.split_stride = mb * g.np;
       NSR_TRY(gemm(a, st));
-      hipLaunchKernelGGL(fwd_reduce_kernel, blocks(mb * L.cout), dim3(256), 0, st, w.dcol, splits, a.split_stride, g.np, L.cout,
-                         w.wr + (int64_t)g.np * g.kp, L.bn ? (int)kActNone : L.act, mb, dst + m0 * ld, ld);
-      NSR_CHECK_LAUNCH();
+      NSR_TRY(refine_fwd_reduce(st, w.dcol, splits, a.split_stride, g.np, L.cout, w.wr + (int64_t)g.np * g.kp,
+                                L.bn ? (int)kActNone : L.act, mb, dst + m0 * ld, ld));
     }
   }
   if (!L.bn) return NSR_OK;
@@ -595,16 +679,12 @@ int site_forward(hipStream_t st, const Site& s, const float* const* t, float* co
   r.x = s.Z; r.ldx = C; r.stat = s.stat; r.rows = rows; r.C = C; r.part = w.red;
   int np;
   NSR_REDUCE(np, st, 0, r);
-  hipLaunchKernelGGL(fin_mean_kernel, dim3((C + 255) / 256), dim3(256), 0, st, w.red, np, C, rows, momentum, s.stat, rm);
-  NSR_CHECK_LAUNCH();
+  NSR_TRY(refine_fin_mean(st, w.red, np, C, rows, momentum, s.stat, rm));
   NSR_REDUCE(np, st, 1, r);
-  hipLaunchKernelGGL(fin_var_kernel, dim3((C + 255) / 256), dim3(256), 0, st, w.red, np, C, rows, momentum, kBnEps, s.stat, rv);
-  NSR_CHECK_LAUNCH();
+  NSR_TRY(refine_fin_var(st, w.red, np, C, rows, momentum, kBnEps, s.stat, rv));
   const float* gamma = t[t_of(s.l) + 2];
   const float* beta = t[t_of(s.l) + 3];
-  hipLaunchKernelGGL(bn_relu_kernel, blocks(rows * (C / 4)), dim3(256), 0, st, s.Z, s.stat, gamma, beta, rows, C, at(s.dst), s.dst.ld);
-  NSR_CHECK_LAUNCH();
-  return NSR_OK;
+  return refine_bn_relu(st, s.Z, s.stat, gamma, beta, rows, C, at(s.dst), s.dst.ld);
 }
 
 // `acc`: this site adds to the parameter gradients (the encoder's second call)
@@ -623,24 +703,17 @@ int site_backward(hipStream_t st, const Site& s, const float* const* t, float* c
     r.x = s.Z; r.ldx = C; r.da = at(s.gdst); r.ldda = s.gdst.ld; r.stat = s.stat; r.gamma = gamma; r.beta = beta;
     r.rows = rows; r.C = C; r.part = w.red;
     NSR_REDUCE(np, st, 2, r);
-    hipLaunchKernelGGL(fin_bn_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, w.red, np, C, rows, acc, grads[p + 2], grads[p + 3], w.m);
-    NSR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_bwd_kernel, blocks(rows * (C / 4)), dim3(256), 0, st, s.Z, at(s.gdst), s.gdst.ld, s.stat, gamma, beta, w.m, rows,
-                       C, w.gz);
-    NSR_CHECK_LAUNCH();
+    NSR_TRY(refine_fin_bn_bwd(st, w.red, np, C, rows, acc, grads[p + 2], grads[p + 3], w.m));
+    NSR_TRY(refine_bn_bwd(st, s.Z, at(s.gdst), s.gdst.ld, s.stat, gamma, beta, w.m, rows, C, w.gz));
     // the bias in front of a BatchNorm is cancelled by the mean subtraction: its gradient is exactly zero
     if (!acc && hipMemsetAsync(grads[p + 1], 0, (size_t)C * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
   } else {
-    if (L.act == kActTanh)
-      hipLaunchKernelGGL(tanh_bwd_kernel, blocks(rows * 32), dim3(256), 0, st, s.dst.p, g_out, g.rows_img, rows, w.gz);
-    else
-      hipLaunchKernelGGL(relu_bwd_kernel, blocks(rows * C), dim3(256), 0, st, s.dst.p, s.gdst.p, rows * C, w.gz);
-    NSR_CHECK_LAUNCH();
+    if (L.act == kActTanh) NSR_TRY(refine_tanh_bwd(st, s.dst.p, g_out, g.rows_img, rows, w.gz));
+    else NSR_TRY(refine_relu_bwd(st, s.dst.p, s.gdst.p, rows * C, w.gz));
     ReduceArgs r{};
     r.x = w.gz; r.ldx = ldz; r.rows = rows; r.C = ldz; r.part = w.red;
     NSR_REDUCE(np, st, 0, r);
-    hipLaunchKernelGGL(fin_bias_kernel, dim3((ldz + 255) / 256), dim3(256), 0, st, w.red, np, ldz, C, acc, grads[p + 1]);
-    NSR_CHECK_LAUNCH();
+    NSR_TRY(refine_fin_bias(st, w.red, np, ldz, C, acc, grads[p + 1]));
   }
   // 32 zeroed rows behind dZ: the K padding of the last chunk's weight-gradient product
   if (hipMemsetAsync(w.gz + rows * ldz, 0, (size_t)32 * ldz * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
@@ -661,19 +734,15 @@ int site_backward(hipStream_t st, const Site& s, const float* const* t, float* c
     a.C = w.part; a.ldc = g.kp; a.M = Mw; a.N = g.kp; a.K = Kp; a.n_valid = g.kp; a.act = kActNone;
     a.splits = (int)splits; a.split_stride = (int64_t)Mw * g.kp;
     NSR_TRY(gemm(a, st));
-    hipLaunchKernelGGL(wgrad_reduce_kernel, blocks((int64_t)C * L.cin * 9), dim3(256), 0, st, w.part, (int)splits, a.split_stride, g.kp,
-                       L.cin, C, (acc || i0 > 0) ? 1 : 0, grads[p]);
-    NSR_CHECK_LAUNCH();
+    NSR_TRY(refine_wgrad_reduce(st, w.part, (int)splits, a.split_stride, g.kp, L.cin, C, (acc || i0 > 0) ? 1 : 0, grads[p]));
     if (s.l == 0) continue;               // no gradient with respect to the input images
     // ---- input gradient: dcol = dZ W, then every input pixel gathers its taps
     GemmArgs d{};
     d.A = dz; d.lda = ldz; d.B = w.wr; d.ldb = g.kp; d.b_kmajor = 1; d.C = w.dcol; d.ldc = g.kp;
     d.M = M; d.N = g.kp; d.K = g.np; d.n_valid = g.kp; d.act = kActNone; d.splits = 1;
     NSR_TRY(gemm(d, st));
-    const int64_t n = (int64_t)nc * s.Hs * s.Ws * (L.cin / 4);
-    hipLaunchKernelGGL(col2im_kernel, blocks(n), dim3(256), 0, st, w.dcol, g.kp, L.cin, nc, s.Hs, s.Ws, L.stride, L.up, g.Ho, g.Wo, s.gacc,
-                       at(s.gsrc) + (int64_t)i0 * s.Hs * s.Ws * s.gsrc.ld, s.gsrc.ld);
-    NSR_CHECK_LAUNCH();
+    NSR_TRY(refine_col2im(st, w.dcol, g.kp, L.cin, nc, s.Hs, s.Ws, L.stride, L.up, g.Ho, g.Wo, s.gacc,
+                          at(s.gsrc) + (int64_t)i0 * s.Hs * s.Ws * s.gsrc.ld, s.gsrc.ld));
   }
   return NSR_OK;
 }
@@ -734,16 +803,9 @@ extern "C" int nsr_refine_train_forward(const float* const* tensors, float* cons
   const int64_t px[4] = {px0, px0 / 4, px0 / 16, px0 / 64};
   const int fcw[4] = {128, 256, 512, 512};
   const Act mx[4] = {{k.cat7, 384, 256}, {k.cat5, 768, 512}, {k.cat3, 1536, 1024}, {k.cat1, 1024, 512}};
-  for (int i = 0; i < 4; ++i) {
-    const int64_t n = (int64_t)B * px[i] * fcw[i];
-    hipLaunchKernelGGL(max_idx_kernel, blocks(n), dim3(256), 0, st, k.fc[i], fcw[i], R, px[i], n, at(mx[i]), mx[i].ld, k.win[i]);
-    NSR_CHECK_LAUNCH();
-  }
+  for (int i = 0; i < 4; ++i) NSR_TRY(refine_max_idx(st, k.fc[i], fcw[i], R, px[i], B, at(mx[i]), mx[i].ld, k.win[i]));
   for (int i = 14; i < kNSites; ++i) NSR_TRY(site_forward(st, s[i], tensors, running, momentum, nullptr, chunk, w));
-  const int64_t n = (int64_t)B * 3 * px0;
-  hipLaunchKernelGGL(nhwc3_to_nchw_kernel, blocks(n), dim3(256), 0, st, k.rgb, px0, n, out);
-  NSR_CHECK_LAUNCH();
-  return NSR_OK;
+  return refine_nhwc3_to_nchw(st, k.rgb, px0, B, out);
 }
 
 extern "C" int nsr_refine_train_backward(const float* const* tensors, const float* g_out, float* const* grads, void* workspace,
@@ -781,11 +843,7 @@ extern "C" int nsr_refine_train_backward(const float* const* tensors, const floa
   const int64_t px[4] = {px0, px0 / 4, px0 / 16, px0 / 64};
   const int fcw[4] = {128, 256, 512, 512};
   const Act gmx[4] = {{w.gcat7, 384, 256}, {w.gcat5, 768, 512}, {w.gcat3, 1536, 1024}, {w.gcat1, 1024, 512}};
-  for (int i = 0; i < 4; ++i) {
-    const int64_t n = (int64_t)B * px[i] * fcw[i];
-    hipLaunchKernelGGL(route_kernel, blocks(n), dim3(256), 0, st, at(gmx[i]), gmx[i].ld, k.win[i], fcw[i], R, px[i], n, w.gfc[i]);
-    NSR_CHECK_LAUNCH();
-  }
+  for (int i = 0; i < 4; ++i) NSR_TRY(refine_route(st, at(gmx[i]), gmx[i].ld, k.win[i], fcw[i], R, px[i], B, w.gfc[i]));
   for (int i = 13; i >= 7; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[1], chunk, w, 1));
   return NSR_OK;
 }

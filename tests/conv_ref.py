@@ -198,6 +198,23 @@ def conv64(x_nhwc: torch.Tensor, w_nk: torch.Tensor, stride: int, up: int) -> to
     return y.permute(0, 2, 3, 1).reshape(-1, w.shape[0])
 
 
+def im2col_numpy(src, nchw, cin, n_img, Hs, Ws, stride, up, Ho, Wo, kp):
+    """col[(img, oy, ox)][tap * cin + c] = source pixel (oy stride + ky - 1, ox stride + kx - 1) of the (upsampled) image, zero
+    outside it; columns >= 9 cin zero.  src: (n_img, Hs, Ws, >= cin) or (n_img, cin, Hs, Ws)."""
+    col = np.zeros((n_img, Ho, Wo, kp), dtype=np.float32)
+    Hin, Win = (2 * Hs, 2 * Ws) if up else (Hs, Ws)
+    oy, ox = np.arange(Ho), np.arange(Wo)
+    for tap in range(9):
+        iy, ix = oy * stride + tap // 3 - 1, ox * stride + tap % 3 - 1
+        vy, vx = (iy >= 0) & (iy < Hin), (ix >= 0) & (ix < Win)
+        sy, sx = (iy >> 1 if up else iy)[vy], (ix >> 1 if up else ix)[vx]
+        for c in range(cin):
+            plane = src[:, c] if nchw else src[..., c]                     # (n_img, Hs, Ws)
+            block = col[:, :, :, tap * cin + c]
+            block[np.ix_(np.arange(n_img), oy[vy], ox[vx])] = plane[np.ix_(np.arange(n_img), sy, sx)]
+    return col.reshape(n_img * Ho * Wo, kp)
+
+
 def accumulator(o: Operands, four_terms: bool = False) -> torch.Tensor:
     c = o.case
     acc = conv64(o.ah, o.bh, c.stride, c.up) + conv64(o.ah, o.bl, c.stride, c.up) + conv64(o.al, o.bh, c.stride, c.up)

@@ -89,6 +89,25 @@ SIGNATURES = {
                                      c_void_p]),
     "nsr_test_sigma_noise": (c_int, [c_void_p, c_int, c_void_p, c_float, c_int64, c_void_p, c_void_p]),
     "nsr_test_gamma_points": (c_int, [c_void_p, c_int64, c_void_p]),
+    # tests/csrc/nsr_test_hooks_refine_train.hip (the last argument of each but reduce_parts is the stream)
+    "nsr_test_refine_col_reduce": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                           c_void_p, POINTER(c_int), c_void_p]),
+    "nsr_test_refine_reduce_parts": (c_int, [c_int64]),
+    "nsr_test_refine_fin_mean": (c_int, [c_void_p, c_int, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
+    "nsr_test_refine_fin_var": (c_int, [c_void_p, c_int, c_int, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p]),
+    "nsr_test_refine_fin_bn_bwd": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "nsr_test_refine_fin_bias": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "nsr_test_refine_bn_relu": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "nsr_test_refine_bn_bwd": (c_int, [c_void_p, c_void_p, c_int64] + [c_void_p] * 4 + [c_int64, c_int, c_void_p, c_void_p]),
+    "nsr_test_refine_relu_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "nsr_test_refine_tanh_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "nsr_test_refine_max_idx": (c_int, [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
+    "nsr_test_refine_route": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p]),
+    "nsr_test_refine_col2im": (c_int, [c_void_p] + [c_int] * 10 + [c_void_p, c_int64, c_void_p]),
+    "nsr_test_refine_wgrad_reduce": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "nsr_test_refine_fwd_reduce": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_void_p, c_int64,
+                                           c_void_p]),
+    "nsr_test_refine_nhwc3_to_nchw": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
 }
 
 # nsr::GemmF16Route (csrc/nsr_gemm.h): the instantiation gemm_f16x3 launches

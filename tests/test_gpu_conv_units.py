@@ -21,7 +21,7 @@ import torch
 
 from tests import conv_ref as cr
 from tests import hooks
-from tests.conv_ref import Case
+from tests.conv_ref import Case, im2col_numpy
 from tests.test_gpu_gemm_units import _ulp32, derived_bound, split_weights
 
 pytestmark = pytest.mark.gpu
@@ -308,23 +308,6 @@ def test_real_inputs_within_derived_bound(hk, nsr):
 # ------------------------------------------------------------------------------------------------------------------------
 # explicit im2col
 # ------------------------------------------------------------------------------------------------------------------------
-def im2col_numpy(src, nchw, cin, n_img, Hs, Ws, stride, up, Ho, Wo, kp):
-    """col[(img, oy, ox)][tap * cin + c] = source pixel (oy stride + ky - 1, ox stride + kx - 1) of the (upsampled) image, zero
-    outside it; columns >= 9 cin zero.  src: (n_img, Hs, Ws, >= cin) or (n_img, cin, Hs, Ws)."""
-    col = np.zeros((n_img, Ho, Wo, kp), dtype=np.float32)
-    Hin, Win = (2 * Hs, 2 * Ws) if up else (Hs, Ws)
-    oy, ox = np.arange(Ho), np.arange(Wo)
-    for tap in range(9):
-        iy, ix = oy * stride + tap // 3 - 1, ox * stride + tap % 3 - 1
-        vy, vx = (iy >= 0) & (iy < Hin), (ix >= 0) & (ix < Win)
-        sy, sx = (iy >> 1 if up else iy)[vy], (ix >> 1 if up else ix)[vx]
-        for c in range(cin):
-            plane = src[:, c] if nchw else src[..., c]                     # (n_img, Hs, Ws)
-            block = col[:, :, :, tap * cin + c]
-            block[np.ix_(np.arange(n_img), oy[vy], ox[vx])] = plane[np.ix_(np.arange(n_img), sy, sx)]
-    return col.reshape(n_img * Ho * Wo, kp)
-
-
 @pytest.mark.parametrize("nchw,cin,ld,ch0,n_img,Hs,Ws,stride,up", [
     (1, 3, 0, 0, 2, 6, 10, 1, 0),          # the first layer: kp = 32, five zero tail columns
     (1, 3, 0, 0, 3, 16, 16, 1, 0),
