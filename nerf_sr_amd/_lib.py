@@ -38,6 +38,14 @@ class NsrArch(ctypes.Structure):
     """``struct nsr_arch`` (include/nsr_train.h): the architecture flags of a VanillaMLP."""
     _fields_ = [("D", c_int), ("W", c_int), ("skips", c_uint), ("deg_pos", c_int), ("deg_dir", c_int), ("no_dir", c_int)]
 
+    @classmethod
+    def from_arch(cls, arch: dict) -> "NsrArch":
+        """From the dict ``weights.normalize_arch`` returns: the skip layers become a bit mask."""
+        skips = 0
+        for i in arch["skips"]:
+            skips |= 1 << int(i)
+        return cls(arch["D"], arch["W"], skips, arch["deg_pos"], arch["deg_dir"], int(bool(arch["no_dir"])))
+
 
 class NsrRayset(ctypes.Structure):
     """``struct nsr_rayset`` (include/nsr_data.h): a scene as device pointers -- poses, 8-bit images, LR-pixel window."""

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .weights import (STATE_DICT_SPEC, check_state_dict, pad_no_dir, DIR_W, IN_CH, arch_of, arch_spec, is_default_arch,
-                      check_state_dict_arch)
+                      check_state_dict_arch, normalize_arch, arch_key)
 
 __all__ = [
     "subpixel_rays", "PositionalEncoding", "sample_along_rays", "resample_along_rays", "cast_rays",
@@ -69,6 +69,18 @@ def _pack_rays(ori, dir, near, far) -> torch.Tensor:
     near = near.reshape(R, 1) if isinstance(near, torch.Tensor) else torch.full((R, 1), float(near), device=ori.device)
     far = far.reshape(R, 1) if isinstance(far, torch.Tensor) else torch.full((R, 1), float(far), device=ori.device)
     return torch.cat([ori, dir, near, far], 1).contiguous()
+
+
+def state_dict_to_device(sd, spec, device, own: bool = False) -> Dict[str, torch.Tensor]:
+    """The tensors of ``sd`` (numpy arrays or torch tensors, detached) that ``spec`` names, as contiguous fp32 tensors on
+    ``device`` in ``spec`` order.  ``own``: cloned, so that the caller may update them in place."""
+    out = {}
+    for k in spec:
+        v = sd[k]
+        v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
+        v = v.to(device=device, dtype=torch.float32).contiguous()
+        out[k] = v.clone() if own else v
+    return out
 
 
 # ----------------------------------------------------------------------------- R1-R4
@@ -233,12 +245,10 @@ class VanillaMLP:
 
     def load_state_dict(self, sd: Dict[str, "np.ndarray | torch.Tensor"]):
         check_state_dict(sd, self.no_dir)
-        dev, packed_from = {}, {}
-        for k in STATE_DICT_SPEC:
-            v = sd[k]
-            v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
-            dev[k] = v.to(device=self.device, dtype=torch.float32).contiguous()
-            packed_from[k] = pad_no_dir(dev[k]).contiguous() if (self.no_dir and k == DIR_W) else dev[k]
+        dev = state_dict_to_device(sd, STATE_DICT_SPEC, self.device)
+        packed_from = dict(dev)
+        if self.no_dir:
+            packed_from[DIR_W] = pad_no_dir(dev[DIR_W]).contiguous()
         ptrs = (c_void_p * len(dev))(*[c_void_p(t.data_ptr()) for t in packed_from.values()])
         rc = _lib.load().nsr_pack_weights(ptrs, _p(self.packed), self._prec, _stream())
         if rc == _lib.NSR_ERR_RANGE:
@@ -327,8 +337,8 @@ class GenericMLP:
     POINT_CHUNK = 262144          # rows per pass (the reference's point_chunk, options/base_options.py:70): bounds the buffers
 
     def __init__(self, opt=None, device="cuda", precision: str = "fp32", fused: bool = False, **arch):
-        self.arch = {**arch_of(opt), **arch}
-        self.spec = arch_spec(**self.arch)                  # validates
+        self.arch = normalize_arch(opt, **arch)             # validates
+        self.spec = arch_spec(**self.arch)
         # fused=True (opt-in, precision 'f16x3'): the whole network in ONE launch per POINT_CHUNK, activations never leave the
         # chip (nsr_arch_fused_forward, include/nsr_train.h) -- the arithmetic of the layer-by-layer route in another summation
         # order.  Refused, before a device is touched, for a precision or an architecture the kernel does not cover.
@@ -344,10 +354,7 @@ class GenericMLP:
         self.gamma_correct = bool(getattr(opt, "gamma_correct", False)) if opt is not None else False
         self.device = torch.device(device)
         _check_device(self.device, "GenericMLP device")
-        a = self.arch
-        self.in_xyz, self.in_dir = 3 + 6 * a["deg_pos"], 3 + 6 * a["deg_dir"]
-        r32 = lambda n: (n + 31) // 32 * 32
-        self.Kx, self.Wp, self.Hp, self.Dp, self.Rp = r32(self.in_xyz), r32(a["W"]), r32(a["W"] // 2), r32(self.in_dir), r32(a["dim_rgb"])
+        self.in_xyz, self.in_dir = 3 + 6 * self.arch["deg_pos"], 3 + 6 * self.arch["deg_dir"]
         # "fp32": every nn.Linear on the fp32 MFMA (nsr_linear); "f16x3" (round 6): on the split-fp16 MFMA, three terms per
         # product, products exact to ~2^-21 (nsr_linear_f16x3: the weights are split once at load time) -- the arithmetic of
         # the fused kernels' default precision, layer by layer.  The single-operand fast precisions have no layer-by-layer form.
@@ -355,10 +362,65 @@ class GenericMLP:
             raise ValueError(f"GenericMLP precision {precision!r}: 'fp32' or 'f16x3' (the layer-by-layer route has no single-operand fast path)")
         self.precision = precision
         self._sd = None
-        self._bad = None
-        self._split = {}
+        color_none = self.color_activation == "none"
+        self._route = _FusedRoute(self.arch, self.device, color_none) if self.fused else \
+            _LayerRoute(self.arch, self.device, precision, color_none)
 
-    # -- weights ------------------------------------------------------------------------------------------------------
+    @property
+    def _split(self):
+        """The linears that carry split-fp16 halves: all of them under 'f16x3' layer by layer, none otherwise."""
+        return [rec for rec in getattr(self._route, "linears", ()) if rec[2] is not None]
+
+    def load_state_dict(self, sd):
+        check_state_dict_arch(sd, **self.arch)
+        dev = state_dict_to_device(sd, self.spec, self.device)
+        self._sd = None                 # a load that raises leaves nothing usable behind
+        self._route.load(dev)
+        self._sd = dev
+        return self
+
+    def state_dict(self):
+        if self._sd is None:
+            raise RuntimeError("no weights loaded")
+        return {k: v.clone() for k, v in self._sd.items()}
+
+    # -- numerics status: the reference drops into pdb on NaN colours (models/nerf_downX_model.py:273-274) ---------------------------
+    def status(self, clear: bool = False) -> int:
+        return self._route.status(clear)
+
+    def check(self, what: str = "network"):
+        flags = self.status(clear=True)
+        if flags:
+            raise _lib.NsrNumericsError(f"{what} {self._route.describe(flags)}", flags)
+        return self
+
+    def forward(self, x: torch.Tensor, sigma_only: bool = False) -> torch.Tensor:
+        if self._sd is None:
+            raise RuntimeError("GenericMLP.forward called before load_state_dict")
+        x = _f32(x, "x")
+        n_in = self.in_xyz + (0 if sigma_only else self.in_dir)
+        if x.ndim != 2 or x.shape[1] < n_in:
+            raise ValueError(f"x must be (B, {n_in}), got {tuple(x.shape)}")
+        out = torch.empty(x.shape[0], 1 if sigma_only else self.arch["dim_rgb"] + 1, dtype=torch.float32, device=x.device)
+        for r0 in range(0, x.shape[0], self.POINT_CHUNK):
+            self._route.forward(x[r0:r0 + self.POINT_CHUNK], out[r0:r0 + self.POINT_CHUNK], sigma_only)
+        return out
+
+    __call__ = forward
+
+
+class _LayerRoute:
+    """``GenericMLP`` layer by layer: the zero-padded operands of every ``nn.Linear`` as one record ``(w, b, hi, lo)`` -- ``hi``
+    / ``lo`` the fp16 halves of 64 w under 'f16x3', None under 'fp32' -- and the sticky non-finite-output flag."""
+
+    def __init__(self, arch: dict, device, precision: str, color_none: bool):
+        self.arch, self.device, self.precision, self.color_none = arch, device, precision, color_none
+        self.in_xyz, self.in_dir = 3 + 6 * arch["deg_pos"], 3 + 6 * arch["deg_dir"]
+        r32 = lambda n: (n + 31) // 32 * 32
+        self.Kx, self.Wp, self.Hp, self.Dp, self.Rp = r32(self.in_xyz), r32(arch["W"]), r32(arch["W"] // 2), r32(self.in_dir), r32(arch["dim_rgb"])
+        self.linears = []
+        self._bad = None
+
     def _padded(self, w, rows, col_map, cols):
         """(rows, cols) zero matrix with w's column ranges placed by col_map = [(src0, n, dst0), ...]."""
         out = torch.zeros(rows, cols, dtype=torch.float32, device=self.device)
@@ -371,161 +433,135 @@ class GenericMLP:
         out[: b.shape[0]] = b
         return out
 
-    def load_state_dict(self, sd):
-        check_state_dict_arch(sd, **self.arch)
-        a, dev = self.arch, {}
-        for k in self.spec:
-            v = sd[k]
-            v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
-            dev[k] = v.to(device=self.device, dtype=torch.float32).contiguous()
-        if self.fused:
-            return self._load_fused(dev)
-        W, ix, Kx, Wp = a["W"], self.in_xyz, self.Kx, self.Wp
-        self._layers = []                       # (weight, bias, first input column, K): the trunk, inputs = slots [pe | h]
+    def _linear(self, w, b):
+        hi = lo = None
+        if self.precision == "f16x3":       # (hi, lo) fp16 halves of 64 w, made once
+            hi, lo = torch.empty(2, w.numel(), dtype=torch.int16, device=self.device)
+            _lib.check(_lib.load().nsr_split_weights(_p(w), w.numel(), _p(hi), _p(lo), _stream()), "nsr_split_weights")
+        self.linears.append((w, b, hi, lo))
+        return self.linears[-1]
+
+    def load(self, dev):
+        a, W, ix, Kx, Wp = self.arch, self.arch["W"], self.in_xyz, self.Kx, self.Wp
+        self.linears = []
+        self._trunk = []                        # (linear, first input column, K): inputs = slots [pe | h]
         for i in range(a["D"]):
             w, b = dev[f"xyz_encoding_{i + 1}.0.weight"], self._padded_bias(dev[f"xyz_encoding_{i + 1}.0.bias"], Wp)
             if i == 0:
-                self._layers.append((self._padded(w, Wp, [(0, ix, 0)], Kx), b, 0, Kx))
+                self._trunk.append((self._linear(self._padded(w, Wp, [(0, ix, 0)], Kx), b), 0, Kx))
             elif i in a["skips"]:               # cat([input_xyz, h]): pe at columns 0.., h at columns Kx..
-                self._layers.append((self._padded(w, Wp, [(0, ix, 0), (ix, W, Kx)], Kx + Wp), b, 0, Kx + Wp))
+                self._trunk.append((self._linear(self._padded(w, Wp, [(0, ix, 0), (ix, W, Kx)], Kx + Wp), b), 0, Kx + Wp))
             else:
-                self._layers.append((self._padded(w, Wp, [(0, W, 0)], Wp), b, Kx, Wp))
-        self._sigma = (self._padded(dev["sigma.weight"], 32, [(0, W, 0)], Wp), self._padded_bias(dev["sigma.bias"], 32))
-        self._final = (self._padded(dev["xyz_encoding_final.weight"], Wp, [(0, W, 0)], Wp), self._padded_bias(dev["xyz_encoding_final.bias"], Wp))
+                self._trunk.append((self._linear(self._padded(w, Wp, [(0, W, 0)], Wp), b), Kx, Wp))
+        self._sigma = self._linear(self._padded(dev["sigma.weight"], 32, [(0, W, 0)], Wp), self._padded_bias(dev["sigma.bias"], 32))
+        self._final = self._linear(self._padded(dev["xyz_encoding_final.weight"], Wp, [(0, W, 0)], Wp),
+                                   self._padded_bias(dev["xyz_encoding_final.bias"], Wp))
         dmap = [(0, W, 0)] + ([] if a["no_dir"] else [(W, self.in_dir, Wp)])
-        self._dir = (self._padded(dev["dir_encoding.0.weight"], self.Hp, dmap, Wp + (0 if a["no_dir"] else self.Dp)),
-                     self._padded_bias(dev["dir_encoding.0.bias"], self.Hp))
-        self._rgb = (self._padded(dev["rgb.0.weight"], self.Rp, [(0, W // 2, 0)], self.Hp), self._padded_bias(dev["rgb.0.bias"], self.Rp))
-        self._sd = dev
+        self._dir = self._linear(self._padded(dev["dir_encoding.0.weight"], self.Hp, dmap, Wp + (0 if a["no_dir"] else self.Dp)),
+                                 self._padded_bias(dev["dir_encoding.0.bias"], self.Hp))
+        self._rgb = self._linear(self._padded(dev["rgb.0.weight"], self.Rp, [(0, W // 2, 0)], self.Hp), self._padded_bias(dev["rgb.0.bias"], self.Rp))
         self._bad = torch.zeros((), dtype=torch.bool, device=self.device)
-        self._split = {}
-        if self.precision == "f16x3":       # (hi, lo) fp16 halves of 64 w for every padded weight, made once
-            lib = _lib.load()
-            for w, *_ in list(self._layers) + [self._sigma, self._final, self._dir, self._rgb]:
-                hl = torch.empty(2, w.numel(), dtype=torch.int16, device=self.device)
-                _lib.check(lib.nsr_split_weights(_p(w), w.numel(), c_void_p(hl[0].data_ptr()), c_void_p(hl[1].data_ptr()), _stream()),
-                           "nsr_split_weights")
-                self._split[w.data_ptr()] = hl
-        return self
 
-    def _load_fused(self, dev):
-        """The fused route's weights: split and re-laid once into the kernel's stream (nsr_arch_fused_pack)."""
-        lib, arch = _lib.load(), _arch_struct(self.arch)
-        nbytes = lib.nsr_arch_fused_packed_bytes(ctypes.byref(arch))
-        if nbytes == 0:
-            raise _lib.NsrError(f"nsr_arch_fused_packed_bytes refuses {self.arch}")
-        self._packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)       # the kernel's sticky NSR_FLAG_* word
-        ptrs = (c_void_p * len(dev))(*[c_void_p(dev[k].data_ptr()) for k in self.spec])
-        _lib.check(lib.nsr_arch_fused_pack(ctypes.byref(arch), ptrs, _p(self._packed), _p(self._status), _stream()),
-                   "nsr_arch_fused_pack")
-        if int(self._status.item()) & 1:
-            self._sd = None             # the stream holds the out-of-range network: nothing usable is loaded
-            self._status.zero_()
-            raise _lib.NsrNumericsError(
-                "state_dict cannot be carried at precision 'f16x3': a weight or bias is non-finite or |w| >= 1023.75 (the "
-                "split-fp16 stream holds 2^6 w in fp16); load it with precision='fp32'", 1)
-        self._sd = dev
-        return self
-
-    def state_dict(self):
-        if self._sd is None:
-            raise RuntimeError("no weights loaded")
-        return {k: v.clone() for k, v in self._sd.items()}
-
-    # -- numerics status: the reference drops into pdb on NaN colours (models/nerf_downX_model.py:273-274) ---------------------------
-    def status(self, clear: bool = False) -> int:
-        if self.fused:                  # the kernel's own status word; waits for the device
-            if self._sd is None:
-                raise RuntimeError("GenericMLP.status called before load_state_dict")
-            flags = int(self._status.item()) & 0xF
-            if clear:
-                self._status.zero_()
-            return flags
+    def status(self, clear: bool) -> int:
         flags = _lib.NSR_FLAG_OUTPUT_NONFINITE if (self._bad is not None and bool(self._bad)) else 0
         if clear and self._bad is not None:
             self._bad.zero_()
         return flags
 
-    def check(self, what: str = "network"):
-        flags = self.status(clear=True)
-        if flags and self.fused:
-            hint = " -- values left the split-fp16 operand range: re-run with precision='fp32'" if flags & 6 else ""
-            raise _lib.NsrNumericsError(f"{what} (fused f16x3): numerics status {flags:#x} = {' | '.join(_lib.flag_names(flags))}{hint}",
-                                        flags)
-        if flags:
-            raise _lib.NsrNumericsError(f"{what} (layer-by-layer fp32): non-finite network output", flags)
-        return self
+    def describe(self, flags: int) -> str:
+        return "(layer-by-layer fp32): non-finite network output"
 
-    # -- forward ------------------------------------------------------------------------------------------------------
-    def _gemm(self, x, col0, ldx, K, w, b, act, y, ycol0, ldy, P):
+    def _gemm(self, x, col0, ldx, K, linear, act, y, ycol0, ldy, P):
         lib, esz = _lib.load(), 4
-        hl = self._split.get(w.data_ptr())
-        if hl is not None:
-            _lib.check(lib.nsr_linear_f16x3(c_void_p(x.data_ptr() + col0 * esz), ldx, c_void_p(hl[0].data_ptr()), c_void_p(hl[1].data_ptr()),
+        w, b, hi, lo = linear
+        if hi is not None:
+            _lib.check(lib.nsr_linear_f16x3(c_void_p(x.data_ptr() + col0 * esz), ldx, _p(hi), _p(lo),
                                             w.shape[1], _p(b), act, c_void_p(y.data_ptr() + ycol0 * esz), ldy, P, K, w.shape[0], _stream()),
                        "nsr_linear_f16x3")
             return
         _lib.check(lib.nsr_linear(c_void_p(x.data_ptr() + col0 * esz), ldx, _p(w), w.shape[1], _p(b), act,
                                   c_void_p(y.data_ptr() + ycol0 * esz), ldy, c_void_p(0), 0, P, K, w.shape[0], _stream()), "nsr_linear")
 
-    def forward(self, x: torch.Tensor, sigma_only: bool = False) -> torch.Tensor:
-        if self._sd is None:
-            raise RuntimeError("GenericMLP.forward called before load_state_dict")
-        x = _f32(x, "x")
-        n_in = self.in_xyz + (0 if sigma_only else self.in_dir)
-        if x.ndim != 2 or x.shape[1] < n_in:
-            raise ValueError(f"x must be (B, {n_in}), got {tuple(x.shape)}")
-        a, B = self.arch, x.shape[0]
-        out = torch.empty(B, 1 if sigma_only else a["dim_rgb"] + 1, dtype=torch.float32, device=x.device)
-        if self.fused:                  # one launch per POINT_CHUNK, no intermediate buffers
-            lib, arch = _lib.load(), _arch_struct(a)
-            flags = (_lib.NSR_ARCH_FUSED_SIGMA_ONLY if sigma_only else 0) | \
-                (_lib.NSR_ARCH_FUSED_COLOR_NONE if self.color_activation == "none" else 0)
-            ldx, ldo = x.shape[1], out.shape[1]
-            for r0 in range(0, B, self.POINT_CHUNK):
-                P = min(self.POINT_CHUNK, B - r0)
-                _lib.check(lib.nsr_arch_fused_forward(ctypes.byref(arch), _p(self._packed), c_void_p(x.data_ptr() + 4 * r0 * ldx), ldx,
-                                                      P, flags, c_void_p(out.data_ptr() + 4 * r0 * ldo), ldo, _p(self._status),
-                                                      _stream()), "nsr_arch_fused_forward")
-            return out
+    def forward(self, x: torch.Tensor, out: torch.Tensor, sigma_only: bool) -> None:
+        a, P = self.arch, x.shape[0]
         Kx, Wp, Ls = self.Kx, self.Wp, self.Kx + self.Wp
-        for r0 in range(0, B, self.POINT_CHUNK):
-            xb = x[r0:r0 + self.POINT_CHUNK]
-            P = xb.shape[0]
-            slots = [torch.zeros(P, Ls, dtype=torch.float32, device=x.device) for _ in range(2)]     # [pe | pad | h | pad] twice
-            for s in slots:
-                s[:, : self.in_xyz] = xb[:, : self.in_xyz]
-            for i, (w, b, c0, K) in enumerate(self._layers):        # layer i reads slot (i - 1) % 2, writes h of slot i % 2
-                self._gemm(slots[(i - 1) % 2], c0, Ls, K, w, b, 1, slots[i % 2], Kx, Ls, P)
-            h = slots[(a["D"] - 1) % 2]
-            small = torch.empty(P, 32, dtype=torch.float32, device=x.device)
-            self._gemm(h, Kx, Ls, Wp, self._sigma[0], self._sigma[1], 0, small, 0, 32, P)
-            if sigma_only:
-                out[r0:r0 + P, 0] = small[:, 0]
-                continue
+        slots = [torch.zeros(P, Ls, dtype=torch.float32, device=x.device) for _ in range(2)]     # [pe | pad | h | pad] twice
+        for s in slots:
+            s[:, : self.in_xyz] = x[:, : self.in_xyz]
+        for i, (lin, c0, K) in enumerate(self._trunk):           # layer i reads slot (i - 1) % 2, writes h of slot i % 2
+            self._gemm(slots[(i - 1) % 2], c0, Ls, K, lin, 1, slots[i % 2], Kx, Ls, P)
+        h = slots[(a["D"] - 1) % 2]
+        small = torch.empty(P, 32, dtype=torch.float32, device=x.device)
+        self._gemm(h, Kx, Ls, Wp, self._sigma, 0, small, 0, 32, P)
+        if sigma_only:
+            out[:, 0] = small[:, 0]
+        else:
             Ld = Wp + (0 if a["no_dir"] else self.Dp)
             dbuf = torch.zeros(P, Ld, dtype=torch.float32, device=x.device)                             # [final | pad | dir pe | pad]
-            self._gemm(h, Kx, Ls, Wp, self._final[0], self._final[1], 0, dbuf, 0, Ld, P)
+            self._gemm(h, Kx, Ls, Wp, self._final, 0, dbuf, 0, Ld, P)
             if not a["no_dir"]:
-                dbuf[:, Wp:Wp + self.in_dir] = xb[:, self.in_xyz:self.in_xyz + self.in_dir]
+                dbuf[:, Wp:Wp + self.in_dir] = x[:, self.in_xyz:self.in_xyz + self.in_dir]
             c = torch.empty(P, self.Hp, dtype=torch.float32, device=x.device)
-            self._gemm(dbuf, 0, Ld, Ld, self._dir[0], self._dir[1], 1, c, 0, self.Hp, P)
+            self._gemm(dbuf, 0, Ld, Ld, self._dir, 1, c, 0, self.Hp, P)
             rgb = torch.empty(P, self.Rp, dtype=torch.float32, device=x.device)
-            self._gemm(c, 0, self.Hp, self.Hp, self._rgb[0], self._rgb[1], 2 if self.color_activation == "sigmoid" else 0, rgb, 0, self.Rp, P)
-            out[r0:r0 + P, : a["dim_rgb"]] = rgb[:, : a["dim_rgb"]]
-            out[r0:r0 + P, a["dim_rgb"]] = small[:, 0]
+            self._gemm(c, 0, self.Hp, self.Hp, self._rgb, 0 if self.color_none else 2, rgb, 0, self.Rp, P)
+            out[:, : a["dim_rgb"]] = rgb[:, : a["dim_rgb"]]
+            out[:, a["dim_rgb"]] = small[:, 0]
         self._bad |= ~torch.isfinite(out).all()
-        return out
-
-    __call__ = forward
 
 
-def _arch_struct(a: dict) -> "_lib.NsrArch":
-    skips = 0
-    for i in a["skips"]:
-        skips |= 1 << int(i)
-    return _lib.NsrArch(a["D"], a["W"], skips, a["deg_pos"], a["deg_dir"], int(bool(a["no_dir"])))
+class _FusedRoute:
+    """``GenericMLP(fused=True)``: the weights split and re-laid once into the kernel's stream (nsr_arch_fused_pack), the
+    kernel's sticky ``NSR_FLAG_*`` word, and the descriptor every ``nsr_arch_fused_*`` call takes."""
+
+    def __init__(self, arch: dict, device, color_none: bool):
+        self.arch, self.device, self.color_none = arch, device, color_none
+        self._c_arch = _lib.NsrArch.from_arch(arch)
+        self._packed = self._status = None
+
+    def _flags(self, sigma_only: bool) -> int:
+        return (_lib.NSR_ARCH_FUSED_SIGMA_ONLY if sigma_only else 0) | (_lib.NSR_ARCH_FUSED_COLOR_NONE if self.color_none else 0)
+
+    def load(self, dev):
+        lib, arch = _lib.load(), ctypes.byref(self._c_arch)
+        self._packed = None
+        nbytes = lib.nsr_arch_fused_packed_bytes(arch)
+        if nbytes == 0:
+            raise _lib.NsrError(f"nsr_arch_fused_packed_bytes refuses {self.arch}")
+        packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        ptrs = (c_void_p * len(dev))(*[_p(t) for t in dev.values()])
+        _lib.check(lib.nsr_arch_fused_pack(arch, ptrs, _p(packed), _p(self._status), _stream()), "nsr_arch_fused_pack")
+        if int(self._status.item()) & 1:    # the stream holds the out-of-range network: nothing usable is loaded
+            self._status.zero_()
+            raise _lib.NsrNumericsError(
+                "state_dict cannot be carried at precision 'f16x3': a weight or bias is non-finite or |w| >= 1023.75 (the "
+                "split-fp16 stream holds 2^6 w in fp16); load it with precision='fp32'", 1)
+        self._packed = packed
+
+    def status(self, clear: bool) -> int:
+        if self._packed is None:
+            raise RuntimeError("GenericMLP.status called before load_state_dict")
+        flags = int(self._status.item()) & 0xF          # waits for the device
+        if clear:
+            self._status.zero_()
+        return flags
+
+    def describe(self, flags: int) -> str:
+        hint = " -- values left the split-fp16 operand range: re-run with precision='fp32'" if flags & 6 else ""
+        return f"(fused f16x3): numerics status {flags:#x} = {' | '.join(_lib.flag_names(flags))}{hint}"
+
+    def forward(self, x: torch.Tensor, out: torch.Tensor, sigma_only: bool) -> None:
+        """One launch, no intermediate buffers."""
+        _lib.check(_lib.load().nsr_arch_fused_forward(ctypes.byref(self._c_arch), _p(self._packed), _p(x), x.shape[1], x.shape[0],
+                                                      self._flags(sigma_only), _p(out), out.shape[1], _p(self._status), _stream()),
+                   "nsr_arch_fused_forward")
+
+    def render_rays(self, rays: torch.Tensor, z_vals: torch.Tensor, raw: torch.Tensor, sigma_only: bool) -> None:
+        R, N = z_vals.shape
+        _lib.check(_lib.load().nsr_arch_fused_render_rays(ctypes.byref(self._c_arch), _p(self._packed), _p(rays), rays.shape[1], _p(z_vals),
+                                                          R, N, self._flags(sigma_only), _p(raw), raw.shape[2], _p(self._status),
+                                                          _stream()), "nsr_arch_fused_render_rays")
 
 
 def check_arch_fused(arch: dict, precision: str) -> None:
@@ -571,7 +607,7 @@ def warn_generic_mlp(arch: dict, precision: str = "fp32") -> None:
     activation matrix travels through HBM: `bench.py --arch D,W,skips` times it (README: ~an order of magnitude slower per
     sample point than the fused f16x3 kernel at the default size) -- on the fp32 MFMA, or under precision 'f16x3' on the split-fp16 MFMA (three terms per product, nsr_linear_f16x3)."""
     import warnings
-    key = (arch.get("D"), arch.get("W"), tuple(arch.get("skips", ())), arch.get("deg_pos"), arch.get("deg_dir"))
+    key = arch_key(arch)
     if key in _GENERIC_WARNED:
         return
     _GENERIC_WARNED.add(key)
@@ -627,17 +663,12 @@ def _arch_render_rays(model: "GenericMLP", rays: torch.Tensor, z_vals: torch.Ten
     if model._sd is None:
         raise RuntimeError("render_rays called before load_state_dict")
     rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
-    stride = _ray_stride(rays)
+    _ray_stride(rays)
     if z_vals.ndim != 2 or z_vals.shape[0] != rays.shape[0] or z_vals.shape[1] < 1:
         raise ValueError(f"z_vals must be (R, N >= 1) with R = {rays.shape[0]} rays, got {tuple(z_vals.shape)}")
     R, N = z_vals.shape
     raw = torch.empty(R, N, 1 if sigma_only else 4, dtype=torch.float32, device=rays.device)
-    flags = (_lib.NSR_ARCH_FUSED_SIGMA_ONLY if sigma_only else 0) | \
-        (_lib.NSR_ARCH_FUSED_COLOR_NONE if model.color_activation == "none" else 0)
-    arch = _arch_struct(model.arch)
-    _lib.check(_lib.load().nsr_arch_fused_render_rays(ctypes.byref(arch), _p(model._packed), _p(rays), stride, _p(z_vals), R, N, flags,
-                                                      _p(raw), raw.shape[2], _p(model._status), _stream()),
-               "nsr_arch_fused_render_rays")
+    model._route.render_rays(rays, z_vals, raw, sigma_only)
     return raw
 
 

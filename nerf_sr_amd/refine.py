@@ -41,7 +41,7 @@ LAYERS = [
 NOREF_CIN = {"D.conv1": 512, "D.conv3": 1024, "D.conv5": 512, "D.conv7": 256}
 
 
-def _spec(not_use_ref: bool = False) -> "OrderedDict[str, tuple]":
+def _refine_spec(not_use_ref: bool = False) -> "OrderedDict[str, tuple]":
     s = OrderedDict()
     for name, cin, cout, bn in LAYERS:
         if not_use_ref:
@@ -55,8 +55,8 @@ def _spec(not_use_ref: bool = False) -> "OrderedDict[str, tuple]":
 
 
 #: the 106 float tensors of MaxPoolingModel.state_dict(), in order (and with --not_use_ref)
-REFINE_SPEC = _spec()
-REFINE_SPEC_NOREF = _spec(True)
+REFINE_SPEC = _refine_spec()
+REFINE_SPEC_NOREF = _refine_spec(True)
 assert len(REFINE_SPEC) == 106 and len(REFINE_SPEC_NOREF) == 106
 #: the 72 trainable tensors (per layer: conv weight, bias, then the BatchNorm's weight, bias) and the 34 running-statistics
 #: tensors (state, not parameters), both in state_dict order

@@ -7,7 +7,7 @@ the reference's call protocol:
     set_input(rays, rgbs)  ->  optimize_parameters()            (:235-248, :398-408)
         = forward (train mode) + comp_low_res_output + calculate_losses + backward + optimizer.step
 
-All arithmetic runs in libnsr.so (``nsr_train_loss_and_grads``, ``nsr_adam_step``); torch supplies device memory,
+All arithmetic runs in libnsr.so (``nsr_train_loss_and_grads``, ``nsr_adam_step_n``); torch supplies device memory,
 the stream and the random draws (``torch.rand`` / ``torch.randn`` on the device, exactly the four tensors the
 reference draws).  There is no CPU path.
 
@@ -24,16 +24,13 @@ import ctypes
 from ctypes import c_void_p
 from typing import Dict, Optional
 
-import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .ops import _f32, _p, _ray_stride, _stream
-from .weights import STATE_DICT_SPEC, check_state_dict, pad_no_dir, DIR_W, arch_of, arch_spec
-
-OUT_KEYS = ("coarse_comp_rgbs", "coarse_depth", "coarse_opacity", "coarse_weights",
-            "fine_comp_rgbs", "fine_depth", "fine_opacity", "fine_weights")
+from .ops import OUT_KEYS, _f32, _p, _ray_stride, _stream, renderer_flags, state_dict_to_device
+from .weights import STATE_DICT_SPEC, check_state_dict_arch, pad_no_dir, DIR_W, arch_key, arch_spec
+from .weights import normalize_arch as _normalize_arch
 
 
 def _ptr_array(tensors):
@@ -51,28 +48,6 @@ def _flat_like(params: Dict[str, torch.Tensor]):
     flat = torch.zeros(total, dtype=torch.float32, device=next(iter(params.values())).device)
     views = {k: flat[o:o + n].view(shape) for (k, n, shape), o in zip(sizes, offs)}
     return flat, views
-
-
-def _to_dev(sd, device, no_dir: bool = False) -> Dict[str, torch.Tensor]:
-    check_state_dict(sd, no_dir)
-    out = {}
-    for k in STATE_DICT_SPEC:
-        v = sd[k]
-        v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
-        v = v.to(device=device, dtype=torch.float32)
-        out[k] = (pad_no_dir(v) if (no_dir and k == DIR_W) else v).contiguous().clone()
-    return out
-
-
-def _to_dev_arch(sd, device, arch: dict) -> Dict[str, torch.Tensor]:
-    from .weights import check_state_dict_arch
-    check_state_dict_arch(sd, **arch)
-    out = {}
-    for k in arch_spec(**arch):
-        v = sd[k]
-        v = torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v.detach()
-        out[k] = v.to(device=device, dtype=torch.float32).contiguous().clone()
-    return out
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, act: int = 0, transposed: bool = False):
@@ -113,7 +88,6 @@ class TrainWorkspace:
     def status(self, clear: bool = False) -> int:
         if self.buf is None:
             return 0
-        import ctypes
         flags = ctypes.c_uint(0)
         _lib.check(_lib.load().nsr_train_status(_p(self.buf), int(bool(clear)), ctypes.byref(flags), _stream()), "nsr_train_status")
         return int(flags.value)
@@ -122,25 +96,31 @@ class TrainWorkspace:
 _DEFAULT_WS: Dict[torch.device, TrainWorkspace] = {}
 
 
-def _weights24(params, name: str):
-    """A network's 24 tensors in state_dict order: a dict keyed like STATE_DICT_SPEC, an nn.Module (``parameters()`` has the
-    state_dict's order), or a sequence of 24 tensors."""
+def _weights(params, name: str, arch: Optional[dict] = None):
+    """A network's tensors in state_dict order for ``arch`` (None: the default network's 24): an nn.Module such as the
+    reference's own ``netCoarse`` built with those flags (``parameters()`` has the state_dict's order), a dict keyed like
+    ``weights.arch_spec``, or a sequence.  Count and shapes are checked before anything else about the tensors."""
+    spec = STATE_DICT_SPEC if arch is None else arch_spec(**arch)
     if isinstance(params, torch.nn.Module):
         ts = list(params.parameters())
     elif isinstance(params, dict):
-        ts = [params[k] for k in STATE_DICT_SPEC]
+        missing = [k for k in spec if k not in params]
+        if missing:
+            raise ValueError(f"{name}: missing keys {missing}")
+        ts = [params[k] for k in spec]
     else:
         ts = list(params)
-    if len(ts) != len(STATE_DICT_SPEC):
-        raise ValueError(f"{name}: expected {len(STATE_DICT_SPEC)} tensors, got {len(ts)}")
-    for i, (t, (k, shape)) in enumerate(zip(ts, STATE_DICT_SPEC.items())):
-        _f32(t, f"{name}.{k}")
-        if k == DIR_W and tuple(t.shape) == (shape[0], shape[1] - 27):
+    if len(ts) != len(spec):
+        raise ValueError(f"{name}: expected {len(spec)} tensors, got {len(ts)}")
+    for i, (t, (k, shape)) in enumerate(zip(ts, spec.items())):
+        if arch is None and k == DIR_W and tuple(t.shape) == (shape[0], shape[1] - 27):
             # --no_dir (models/networks.py:160-169): the narrow layer with 27 zero columns (weights.pad_no_dir, as Trainer
             # holds it); the padding is a constant, so autograd hands the narrow weight the gradient of its 256 columns
             ts[i] = t = pad_no_dir(t)
         if tuple(t.shape) != tuple(shape):
             raise ValueError(f"{name}: {k} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    for t, k in zip(ts, spec):
+        _f32(t, f"{name}.{k}")
     return [t if t.is_contiguous() else t.contiguous() for t in ts]
 
 
@@ -152,21 +132,12 @@ _ARCH_WARNED = set()
 
 
 def normalize_arch(arch) -> dict:
-    """``arch`` as the dict ``weights.arch_spec`` takes: a dict with any of D, W, skips, deg_pos, deg_dir, no_dir (absent
-    ones = the reference's defaults), or an options object carrying the reference's flags.  Validates (ValueError)."""
-    a = {**arch_of(None), **arch} if isinstance(arch, dict) else arch_of(arch)
-    a["skips"] = tuple(sorted(set(int(s) for s in a["skips"])))
-    if int(a.get("dim_rgb", 3)) != 3:
+    """``weights.normalize_arch`` (a dict with any of D, W, skips, deg_pos, deg_dir, no_dir, or an options object carrying the
+    reference's flags; validates, ValueError) for the training pair, whose compositor renders three colours."""
+    a = _normalize_arch(arch)
+    if a["dim_rgb"] != 3:
         raise ValueError("arch: dim_rgb must be 3 (the compositor renders three colours)")
-    arch_spec(**a)      # D >= 1, even W, degrees >= 0, skips inside 1 .. D - 1
     return a
-
-
-def _arch_struct(a: dict) -> "_lib.NsrArch":
-    skips = 0
-    for i in a["skips"]:
-        skips |= 1 << i
-    return _lib.NsrArch(a["D"], a["W"], skips, a["deg_pos"], a["deg_dir"], int(bool(a["no_dir"])))
 
 
 def arch_precision(arch: dict, precision: str) -> str:
@@ -178,7 +149,7 @@ def arch_precision(arch: dict, precision: str) -> str:
     if precision != "f16x3":
         raise ValueError(f"precision={precision!r} with arch=...: a non-default architecture trains layer by layer under "
                          f"{list(ARCH_PRECISIONS)} ('f16x3' maps to 'f16x3_gemm'); the chain kernels are the default network's")
-    key = (arch["D"], arch["W"], tuple(arch["skips"]), arch["deg_pos"], arch["deg_dir"], bool(arch["no_dir"]))
+    key = arch_key(arch, no_dir=True)
     if key not in _ARCH_WARNED:
         _ARCH_WARNED.add(key)
         import warnings
@@ -189,36 +160,49 @@ def arch_precision(arch: dict, precision: str) -> str:
     return "f16x3_gemm"
 
 
-def _weights_arch(params, name: str, arch: dict):
-    """A network's 2 D + 8 tensors in state_dict order for ``arch`` (an nn.Module such as the reference's own ``netCoarse``
-    built with those flags, a dict keyed like ``weights.arch_spec``, or a sequence); shapes checked."""
-    spec = arch_spec(**arch)
-    if isinstance(params, torch.nn.Module):
-        ts = list(params.parameters())
-    elif isinstance(params, dict):
-        missing = [k for k in spec if k not in params]
-        if missing:
-            raise ValueError(f"{name}: missing keys {missing}")
-        ts = [params[k] for k in spec]
-    else:
-        ts = list(params)
-    if len(ts) != len(spec):
-        raise ValueError(f"{name}: expected {len(spec)} tensors for this architecture, got {len(ts)}")
-    for t, (k, shape) in zip(ts, spec.items()):
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"{name}: {k} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    for t, k in zip(ts, spec):
-        _f32(t, f"{name}.{k}")
-    return [t if t.is_contiguous() else t.contiguous() for t in ts]
+def train_flags(white_bkgd: bool = False, gamma_correct: bool = False, sigma_activation: str = "relu",
+                color_activation: str = "sigmoid", stop_grad: bool = False) -> int:
+    """The option word of the training entry points (include/nsr_train.h): the renderer's word (``ops.renderer_flags``) plus
+    --gamma_correct (render_rays applies rgb ** (1 / 2.2) per sample in training too, models/nerf_downX_model.py:271-276),
+    --color_activation none (models/networks.py:173-180) and --stop_grad (:127, 218-219).  Validates (ValueError)."""
+    if sigma_activation not in ("relu", "softplus") or color_activation not in ("sigmoid", "none"):
+        raise ValueError("sigma_activation: 'relu' or 'softplus'; color_activation: 'sigmoid' or 'none'")
+    if gamma_correct and color_activation == "none":
+        raise ValueError("gamma_correct with color_activation='none': pow(rgb, 1 / 2.2) of an unbounded head is NaN for every negative value")
+    return renderer_flags(white_bkgd, sigma_activation) | (_lib.NSR_TRAIN_GAMMA_CORRECT if gamma_correct else 0) \
+        | (_lib.NSR_TRAIN_COLOR_NONE if color_activation == "none" else 0) | (_lib.NSR_TRAIN_STOP_GRAD if stop_grad else 0)
+
+
+def _rays_per_pass(ray_chunk: int, R: int) -> int:
+    """The effective ray chunk of a batch of R rays (``ray_chunk`` 0 = all)."""
+    return ray_chunk if 0 < ray_chunk < R else R
+
+
+def _alloc_outs(R: int, nc: int, ni: int, device):
+    """The eight output tensors of one train-mode forward, in ``OUT_KEYS`` order."""
+    stage = lambda n: [torch.empty(R, 3, device=device), torch.empty(R, device=device), torch.empty(R, device=device),
+                       torch.empty(R, n, device=device)]
+    return stage(nc) + stage(nc + ni)
 
 
 class _TrainRun:
-    """The arguments of one forward_rays_train call that are not tensors."""
+    """The arguments of one forward_rays_train call that are not tensors, and the pair of entry points it runs: the default
+    network's, or with ``arch`` (struct nsr_arch) the layer-by-layer pair, which differs by that leading argument only."""
 
     def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace, arch=None):
         self.nc, self.ni, self.flags, self.lindisp = nc, ni, flags, lindisp
         self.noise_std, self.prec, self.chunk, self.workspace = noise_std, prec, chunk, workspace
-        self.arch = arch          # None: the default network's pair; else struct nsr_arch (nsr_train_arch_forward / _backward)
+        self.arch = arch
+        self.lead = () if arch is None else (ctypes.byref(arch),)
+        self.names = {"saved_bytes": "nsr_train_saved_bytes", "workspace_bytes": "nsr_train_workspace_bytes_for",
+                      "forward": "nsr_train_forward", "backward": "nsr_train_backward"} if arch is None else \
+            {"saved_bytes": "nsr_train_arch_saved_bytes", "workspace_bytes": "nsr_train_arch_workspace_bytes",
+             "forward": "nsr_train_arch_forward", "backward": "nsr_train_arch_backward"}
+
+    def call(self, what: str, *args):
+        """``(name, result)`` of this run's entry point ``what`` on ``args`` behind the leading descriptor."""
+        name = self.names[what]
+        return name, getattr(_lib.load(), name)(*self.lead, *args)
 
 
 class _ForwardRaysTrain(torch.autograd.Function):
@@ -227,27 +211,22 @@ class _ForwardRaysTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, run, rays, u_c, u_f, n_c, n_f, *weights):
-        lib = _lib.load()
         R, nc, ni = rays.shape[0], run.nc, run.ni
         dev = rays.device
-        outs = [torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, nc, device=dev),
-                torch.empty(R, 3, device=dev), torch.empty(R, device=dev), torch.empty(R, device=dev), torch.empty(R, nc + ni, device=dev)]
-        arch = () if run.arch is None else (ctypes.byref(run.arch),)
-        what = "nsr_train_saved_bytes" if run.arch is None else "nsr_train_arch_saved_bytes"
-        nbytes = getattr(lib, what)(*arch, run.prec, R, nc, ni, run.chunk)
+        outs = _alloc_outs(R, nc, ni, dev)
+        what, nbytes = run.call("saved_bytes", run.prec, R, nc, ni, run.chunk)
         if nbytes == 0:
             raise _lib.NsrError(f"{what}: no saved state for R={R}, samples {nc} + {ni}, ray_chunk {run.chunk} "
                                 "(every ray chunk must hold a multiple of 32 sample points in both networks)")
         saved = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ws_bytes = lib.nsr_train_workspace_bytes_for if run.arch is None else lib.nsr_train_arch_workspace_bytes
-        ctx.ws_need = ws_bytes(*arch, run.prec, run.chunk if 0 < run.chunk < R else R, nc, ni)
+        ctx.ws_need = run.call("workspace_bytes", run.prec, _rays_per_pass(run.chunk, R), nc, ni)[1]
         ws = run.workspace.get(ctx.ws_need, dev)
         nt = len(weights) // 2
-        fwd, what = (lib.nsr_train_forward, "nsr_train_forward") if run.arch is None else (lib.nsr_train_arch_forward, "nsr_train_arch_forward")
-        _lib.check(fwd(
-            *arch, _ptr_array(weights[:nt]), _ptr_array(weights[nt:]), _p(rays), _ray_stride(rays), R, nc, ni, run.flags, run.lindisp,
+        what, rc = run.call(
+            "forward", _ptr_array(weights[:nt]), _ptr_array(weights[nt:]), _p(rays), _ray_stride(rays), R, nc, ni, run.flags, run.lindisp,
             _p(u_c), _p(u_f), _p(n_c), _p(n_f), run.noise_std, run.prec, run.chunk, _ptr_array(outs),
-            _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()), what)
+            _p(ws), ws.numel(), _p(saved), saved.numel(), _stream())
+        _lib.check(rc, what)
         ctx.save_for_backward(*weights)      # an in-place update of a weight before the backward fails autograd's version check
         ctx.run, ctx.state = run, saved
         ctx.set_materialize_grads(False)     # an output the loss does not use arrives as None: a NULL upstream gradient
@@ -260,17 +239,14 @@ class _ForwardRaysTrain(torch.autograd.Function):
         saved = ctx.state
         if saved is None:
             raise RuntimeError("forward_rays_train: the saved state of this forward was released by its first backward")
-        lib = _lib.load()
         g_outs = [None if g is None else g.to(torch.float32).contiguous() for g in g_outs]
         grads = [torch.empty_like(w) for w in weights]
         ws = ctx.run.workspace.get(ctx.ws_need, saved.device)
-        run, nt = ctx.run, len(weights) // 2
-        arch = () if run.arch is None else (ctypes.byref(run.arch),)
-        bwd, what = (lib.nsr_train_backward, "nsr_train_backward") if run.arch is None else (lib.nsr_train_arch_backward, "nsr_train_arch_backward")
-        _lib.check(bwd(
-            *arch, _ptr_array(weights[:nt]), _ptr_array(weights[nt:]), (c_void_p * 8)(*[_p(g) for g in g_outs]),
-            _ptr_array(grads[:nt]), _ptr_array(grads[nt:]), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
-            what)
+        nt = len(weights) // 2
+        what, rc = ctx.run.call(
+            "backward", _ptr_array(weights[:nt]), _ptr_array(weights[nt:]), (c_void_p * 8)(*[_p(g) for g in g_outs]),
+            _ptr_array(grads[:nt]), _ptr_array(grads[nt:]), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream())
+        _lib.check(rc, what)
         ctx.state = None
         return (None,) * 6 + tuple(grads)
 
@@ -297,33 +273,28 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     RuntimeWarning per architecture; the chain names raise ValueError).  None = the default network, as before."""
     if rays.requires_grad:
         raise ValueError("forward_rays_train: rays must not require grad (there is no gradient with respect to rays)")
+    flags = train_flags(white_bkgd, gamma_correct, sigma_activation, color_activation, stop_grad)
     if arch is not None:      # everything about the architecture is checked before a device is touched
         arch = normalize_arch(arch)
-        if gamma_correct and color_activation == "none":
-            raise ValueError("gamma_correct with color_activation='none': pow(rgb, 1 / 2.2) of an unbounded head is NaN for every negative value")
         precision = arch_precision(arch, precision)
-        wc, wf = _weights_arch(params_c, "params_c", arch), _weights_arch(params_f, "params_f", arch)
+        wc, wf = _weights(params_c, "params_c", arch), _weights(params_f, "params_f", arch)
     rays = _f32(rays, "rays")
     _ray_stride(rays)
     if precision not in _lib.TRAIN_PRECISIONS:
         raise ValueError(f"precision must be one of {sorted(_lib.TRAIN_PRECISIONS)}")
-    if sigma_activation not in ("relu", "softplus") or color_activation not in ("sigmoid", "none"):
-        raise ValueError("sigma_activation: 'relu' or 'softplus'; color_activation: 'sigmoid' or 'none'")
-    if arch is None:
-        wc, wf = _weights24(params_c, "params_c"), _weights24(params_f, "params_f")
+    if arch is None:          # the default network's order of checks: the rays come first
+        wc, wf = _weights(params_c, "params_c"), _weights(params_f, "params_f")
     for t in wc + wf:
         if t.device != rays.device:
             raise ValueError("the weights must live on the rays' device")
     draws = draws or {}
     d = [None if draws.get(k) is None else _f32(torch.as_tensor(draws[k], device=rays.device), k)
          for k in ("u_coarse", "u_fine", "noise_coarse", "noise_fine")]
-    flags = (_lib.NSR_WHITE_BKGD if white_bkgd else 0) | (_lib.NSR_TRAIN_GAMMA_CORRECT if gamma_correct else 0) \
-        | (_lib.NSR_SIGMA_SOFTPLUS if sigma_activation == "softplus" else 0) \
-        | (_lib.NSR_TRAIN_COLOR_NONE if color_activation == "none" else 0) | (_lib.NSR_TRAIN_STOP_GRAD if stop_grad else 0)
     if workspace is None:
         workspace = _DEFAULT_WS.setdefault(rays.device, TrainWorkspace())
     run = _TrainRun(int(N_coarse), int(N_importance), flags, int(bool(lindisp)), float(noise_std),
-                    _lib.TRAIN_PRECISIONS[precision], int(ray_chunk), workspace, None if arch is None else _arch_struct(arch))
+                    _lib.TRAIN_PRECISIONS[precision], int(ray_chunk), workspace,
+                    None if arch is None else _lib.NsrArch.from_arch(arch))
     outs = _ForwardRaysTrain.apply(run, rays, *d, *wc, *wf)
     return dict(zip(OUT_KEYS, outs))
 
@@ -361,16 +332,10 @@ class Trainer:
         if grad_clip_type not in ("norm", "value"):
             raise ValueError("grad_clip_type: 'norm' or 'value'")
         self.grad_clip_val, self.grad_clip_type = float(grad_clip_val), grad_clip_type
-        # render_rays applies rgb ** (1 / 2.2) per sample under --gamma_correct (models/nerf_downX_model.py:271-276) in training
-        # too: NSR_TRAIN_GAMMA_CORRECT of the step's option word (include/nsr_train.h)
-        self.gamma_correct = bool(gamma_correct)
-        # --sigma_activation softplus (models/rendering.py:69-73), --color_activation none (models/networks.py:173-180)
-        if sigma_activation not in ("relu", "softplus") or color_activation not in ("sigmoid", "none"):
-            raise ValueError("sigma_activation: 'relu' or 'softplus'; color_activation: 'sigmoid' or 'none'")
-        if gamma_correct and color_activation == "none":
-            raise ValueError("gamma_correct with color_activation='none': pow(rgb, 1 / 2.2) of an unbounded head is NaN for every negative value")
+        # the options of the step's option word (train_flags; --sigma_activation softplus: models/rendering.py:69-73)
+        train_flags(white_bkgd, gamma_correct, sigma_activation, color_activation, stop_grad)      # validates
+        self.gamma_correct, self.stop_grad = bool(gamma_correct), bool(stop_grad)
         self.sigma_activation, self.color_activation = sigma_activation, color_activation
-        self.stop_grad = bool(stop_grad)       # --stop_grad (models/networks.py:127, 218-219): the colour branch's input is detached
         if precision not in _lib.TRAIN_PRECISIONS:
             raise ValueError("precision must be 'fp32' (every product on the fp32 MFMA, layer by layer), 'f16x3' (the chain "
                              "kernels: forward on the split-fp16 MFMA, weight gradients on one fp16 MFMA per product, input "
@@ -383,14 +348,23 @@ class Trainer:
         # dir_encoding's weight (weights.pad_no_dir) whose gradients are dropped every step, so Adam never moves them
         # (m = v = 0 -> update 0): the function, its gradients and the trajectory are the narrow network's
         self.no_dir = bool(no_dir) if self.arch is None else bool(self.arch["no_dir"])
-        if self.arch is None:
-            self.params = [_to_dev(sd_coarse, self.device, self.no_dir), _to_dev(sd_fine, self.device, self.no_dir)]
-        else:
-            self.params = [_to_dev_arch(sd_coarse, self.device, self.arch), _to_dev_arch(sd_fine, self.device, self.arch)]
+        self._padded = self.no_dir and self.arch is None      # an architecture keeps the narrow layer natively
+        desc = self.arch if self.arch is not None else _normalize_arch(no_dir=self.no_dir)
+        self.params = []
+        for sd in (sd_coarse, sd_fine):
+            check_state_dict_arch(sd, **desc)
+            p = state_dict_to_device(sd, arch_spec(**desc), self.device, own=True)
+            if self._padded:
+                p[DIR_W] = pad_no_dir(p[DIR_W])
+            self.params.append(p)
         flat = [_flat_like(p) for p in self.params]
         self.flat_grads, self.grads = [f for f, _ in flat], [v for _, v in flat]
         self.exp_avg = [_flat_like(p)[1] for p in self.params]
         self.exp_avg_sq = [_flat_like(p)[1] for p in self.params]
+        # nsr_adam_step_n's arguments per network, built once: the tensors are only ever updated in place
+        self._numel = [(ctypes.c_int64 * len(p))(*[v.numel() for v in p.values()]) for p in self.params]
+        self._ptrs = {name: [_ptr_array(list(d.values())) for d in getattr(self, name)]
+                      for name in ("params", "grads", "exp_avg", "exp_avg_sq")}
         # data parallelism: every rank scales its loss by 1 / world so that the all-reduce SUM is the gradient of the
         # global-batch MEAN loss, like DistributedDataParallel's averaging (models/networks.py:84).  None = derive it
         # from the default process group at each step; a number pins it (e.g. a custom group).
@@ -421,6 +395,20 @@ class Trainer:
     def _ws(self) -> Optional[torch.Tensor]:
         return self._workspace.buf
 
+    def _grad_scale(self) -> float:
+        """What every loss is scaled by so that the all-reduce SUM is the global-batch MEAN's gradient (see ``grad_scale``)."""
+        from .dist import _world
+        return float(self.grad_scale) if self.grad_scale is not None else 1.0 / _world(self.group)[1]
+
+    def _chunk(self, R: int) -> int:
+        return _rays_per_pass(self.ray_chunk, R)
+
+    def _zero_padding_grads(self):
+        """--no_dir on the default network: the gradients of the 27 zero columns are dropped, so Adam never moves them."""
+        if self._padded:
+            for g in self.grads:
+                g[DIR_W][:, 256:].zero_()
+
     # -- reference protocol ------------------------------------------------------------------------------
     def set_input(self, rays: torch.Tensor, rgbs: torch.Tensor):
         """rays (N_lr, s2, 8 | 11) or (N_lr * s2, 8 | 11); rgbs (N_lr, 3) LR targets (set_input, :235-248)."""
@@ -448,42 +436,33 @@ class Trainer:
         scaled by 1 / world for the data-parallel SUM, see ``grad_scale``)."""
         if self.arch is not None:
             return self._loss_and_grads_arch(draws)
-        from .dist import _world
-        gs = float(self.grad_scale) if self.grad_scale is not None else 1.0 / _world(self.group)[1]
+        gs = self._grad_scale()
         rays = self.data_rays
         R, stride = rays.shape[0], _ray_stride(rays)
         if draws is None:
             draws = self.draw(R)
         draws = {k: (None if v is None else _f32(torch.as_tensor(v, device=self.device), k)) for k, v in draws.items()
                  if k != "noise_std"}
-        nc, nf = self.N_coarse, self.N_coarse + self.N_importance
-        chunk = min(self.ray_chunk, R) if self.ray_chunk > 0 else R
+        nc, chunk = self.N_coarse, self._chunk(R)
         lib = _lib.load()
         need = lib.nsr_train_workspace_bytes_for(self._prec, chunk, nc, self.N_importance)   # the buffers of the path this precision takes
         if need == 0:
             raise _lib.NsrError("sample counts outside the built path")
         self._workspace.get(need, self.device)
         dev = self.device
-        o = {"coarse_comp_rgbs": torch.empty(R, 3, device=dev), "coarse_depth": torch.empty(R, device=dev),
-             "coarse_opacity": torch.empty(R, device=dev), "coarse_weights": torch.empty(R, nc, device=dev),
-             "fine_comp_rgbs": torch.empty(R, 3, device=dev), "fine_depth": torch.empty(R, device=dev),
-             "fine_opacity": torch.empty(R, device=dev), "fine_weights": torch.empty(R, nf, device=dev)}
+        o = dict(zip(OUT_KEYS, _alloc_outs(R, nc, self.N_importance, dev)))
         lr_c = torch.empty(R // self.s2, 3, device=dev)
         lr_f = torch.empty(R // self.s2, 3, device=dev)
-        outs = (c_void_p * 8)(*[c_void_p(o[k].data_ptr()) for k in OUT_KEYS])
-        wc, wf = _ptr_array(list(self.params[0].values())), _ptr_array(list(self.params[1].values()))
-        gc, gf = _ptr_array(list(self.grads[0].values())), _ptr_array(list(self.grads[1].values()))
-        common = (wc, wf, gc, gf, _p(rays), stride, R, self.s2, _p(self.data_rgbs), nc, self.N_importance,
-                  int(self.white_bkgd) | (_lib.NSR_TRAIN_GAMMA_CORRECT if self.gamma_correct else 0)
-                  | (_lib.NSR_SIGMA_SOFTPLUS if self.sigma_activation == "softplus" else 0)
-                  | (_lib.NSR_TRAIN_COLOR_NONE if self.color_activation == "none" else 0)
-                  | (_lib.NSR_TRAIN_STOP_GRAD if self.stop_grad else 0), int(self.lindisp),
+        outs = _ptr_array(list(o.values()))
+        (wc, wf), (gc, gf) = self._ptrs["params"], self._ptrs["grads"]
+        # int(self.white_bkgd) as it stands: the C entry point is the one that refuses a word with unknown or exclusive bits
+        flags = int(self.white_bkgd) | train_flags(False, self.gamma_correct, self.sigma_activation, self.color_activation, self.stop_grad)
+        common = (wc, wf, gc, gf, _p(rays), stride, R, self.s2, _p(self.data_rgbs), nc, self.N_importance, flags, int(self.lindisp),
                   _p(draws.get("u_coarse")), _p(draws.get("u_fine")),
                   _p(draws.get("noise_coarse")), _p(draws.get("noise_fine")), self.noise_std,
                   self.lambda_coarse * gs, self.lambda_fine * gs, self._prec, chunk, outs, _p(lr_c), _p(lr_f), _p(self.losses),
                   _p(self._ws), self._ws.numel(), _stream())
         if any(self.lambda_var):
-            import ctypes
             # self.far of the reference (nerf_downX_model.py:284): forward_rays overwrites it per ray_chunk, so what
             # calculate_losses divides by is the far bound of the FIRST ray of the LAST chunk.  Only the depth-variance
             # terms use it: read (one host sync) only when one of them is on; the colour-variance terms never need it.
@@ -495,9 +474,7 @@ class Trainer:
                        "nsr_train_loss_and_grads_var")
         else:
             _lib.check(lib.nsr_train_loss_and_grads(*common), "nsr_train_loss_and_grads")
-        if self.no_dir:
-            for g in self.grads:
-                g[DIR_W][:, 256:].zero_()
+        self._zero_padding_grads()
         if gs != 1.0:
             self.losses.mul_(1.0 / gs)          # report this rank's own losses, not the 1 / world share
             self.var_losses.mul_(1.0 / gs)
@@ -526,7 +503,7 @@ class Trainer:
                 terms[0], terms[1] = var_of(out["coarse_comp_rgbs"]), var_of(out["fine_comp_rgbs"])
             if any(self.lambda_var[2:]):
                 # self.far of the reference (:284): the far bound of the first ray of the last ray chunk
-                chunk = min(self.ray_chunk, R) if self.ray_chunk > 0 else R
+                chunk = self._chunk(R)
                 far = rays[((R - 1) // chunk) * chunk, 7]
                 terms[2], terms[3] = var_of(out["coarse_depth"] / far), var_of(out["fine_depth"] / far)
             for i, (lam, t) in enumerate(zip(self.lambda_var, terms)):
@@ -568,8 +545,7 @@ class Trainer:
         """d(loss)/d(weights) of the forwards behind ``loss`` into ``self.grads`` / ``self.flat_grads`` (OVERWRITTEN; scaled by
         1 / world like ``loss_and_grads``, see ``grad_scale``), where ``all_reduce_grads`` and ``optimizer_step`` find them.
         A weight the loss does not reach gets a zero gradient."""
-        from .dist import _world
-        gs = float(self.grad_scale) if self.grad_scale is not None else 1.0 / _world(self.group)[1]
+        gs = self._grad_scale()
         leaves = self._weight_leaves()
         flat = leaves[0] + leaves[1]
         grads = torch.autograd.grad(loss, flat, grad_outputs=None if gs == 1.0 else torch.full_like(loss, gs), allow_unused=True)
@@ -578,9 +554,7 @@ class Trainer:
         for d, g in zip(dst, grads):
             if g is None:
                 d.zero_()
-        if self.no_dir and self.arch is None:
-            for g in self.grads:
-                g[DIR_W][:, 256:].zero_()
+        self._zero_padding_grads()
         return self.grads
 
     def clip_grads(self) -> Optional[torch.Tensor]:
@@ -631,21 +605,12 @@ class Trainer:
     def optimizer_step(self):
         """torch.optim.Adam.step over both networks (:201-204, :408)."""
         self.step += 1
-        for n in range(2):
-            if self.arch is not None:
-                ps = list(self.params[n].values())
-                numel = (ctypes.c_int64 * len(ps))(*[p.numel() for p in ps])
-                _lib.check(_lib.load().nsr_adam_step_n(
-                    len(ps), numel, _ptr_array(ps), _ptr_array(list(self.grads[n].values())),
-                    _ptr_array(list(self.exp_avg[n].values())), _ptr_array(list(self.exp_avg_sq[n].values())),
-                    self.step, self.lr, self.beta1, self.beta2, self.eps, _stream()), "nsr_adam_step_n")
-                continue
-            _lib.check(_lib.load().nsr_adam_step(
-                _ptr_array(list(self.params[n].values())), _ptr_array(list(self.grads[n].values())),
-                _ptr_array(list(self.exp_avg[n].values())), _ptr_array(list(self.exp_avg_sq[n].values())),
-                self.step, self.lr, self.beta1, self.beta2, self.eps, _stream()), "nsr_adam_step")
+        for n, numel in enumerate(self._numel):
+            _lib.check(_lib.load().nsr_adam_step_n(
+                len(numel), numel, *(self._ptrs[k][n] for k in ("params", "grads", "exp_avg", "exp_avg_sq")),
+                self.step, self.lr, self.beta1, self.beta2, self.eps, _stream()), "nsr_adam_step_n")
         if self._leaves is not None:
-            # nsr_adam_step wrote the weights behind autograd's back: mark them modified, so that the backward of a forward
+            # nsr_adam_step_n wrote the weights behind autograd's back: mark them modified, so that the backward of a forward
             # made before this step fails the version check instead of mixing two sets of weights
             torch.autograd.graph.increment_version(self._leaves[0] + self._leaves[1])
 
@@ -702,6 +667,4 @@ class Trainer:
         return self.lr
 
     def state_dicts(self):
-        if self.arch is not None:
-            return [{k: v.clone() for k, v in p.items()} for p in self.params]
-        return [{k: (v[:, :256] if (self.no_dir and k == DIR_W) else v).clone() for k, v in p.items()} for p in self.params]
+        return [{k: (v[:, :256] if (self._padded and k == DIR_W) else v).clone() for k, v in p.items()} for p in self.params]

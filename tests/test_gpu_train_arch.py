@@ -190,7 +190,7 @@ def test_saved_state_does_not_cross_entry_point_families(golden_dir, tr):
     lib = _lib.load()
     rays = torch.from_numpy(g["rays"]).cuda()
     draws = au.draws_of(g)
-    small = tr._arch_struct(tr.normalize_arch(g["arch"]))
+    small = _lib.NsrArch.from_arch(tr.normalize_arch(g["arch"]))
     w_small = [[torch.from_numpy(v).cuda() for v in sd.values()] for sd in au.state_dicts(g)]
     w_def = [[torch.from_numpy(v).cuda() for v in make_state_dict(s).values()] for s in (3, 4)]
     g_fine = torch.ones(rays.shape[0], 3, device="cuda")
@@ -334,7 +334,7 @@ def test_misuse_is_rejected(golden_dir, tr):
     grads = [[torch.empty_like(p) for p in n] for n in leaves]
     gf = torch.ones_like(out["fine_comp_rgbs"])
     g8 = (c_void_p * 8)(*[c_void_p(0)] * 4, c_void_p(gf.data_ptr()), *[c_void_p(0)] * 3)
-    mine = tr._arch_struct(tr.normalize_arch(g["arch"]))
+    mine = _lib.NsrArch.from_arch(tr.normalize_arch(g["arch"]))
 
     def bwd(buf, nbytes, arch=mine):
         rc = lib.nsr_train_arch_backward(ctypes.byref(arch), tr._ptr_array(leaves[0]), tr._ptr_array(leaves[1]), g8,
@@ -350,7 +350,7 @@ def test_misuse_is_rejected(golden_dir, tr):
     garbage = saved.clone()
     garbage[48:52] = 9                                         # D of the recorded descriptor
     assert bwd(garbage, garbage.numel()) == -1
-    same_shapes = tr._arch_struct(tr.normalize_arch(dict(g["arch"], deg_dir=g["arch"]["deg_dir"] + 1)))
+    same_shapes = _lib.NsrArch.from_arch(tr.normalize_arch(dict(g["arch"], deg_dir=g["arch"]["deg_dir"] + 1)))
     assert bwd(saved, saved.numel(), same_shapes) == -1        # another descriptor with as many tensors
     assert bwd(saved, saved.numel() - 1) == -4
     assert bwd(saved, 256) == -4

@@ -280,7 +280,7 @@ def test_documented_value_errors_without_a_device():
     with pytest.raises(ValueError, match="rays must live on the GPU"):
         tr.forward_rays_train(list(other.values()), other, torch.zeros(64, 8))
     with pytest.raises(ValueError, match="expected 24 tensors"):
-        tr._weights24(list(other.values()), "params_c")
+        tr._weights(list(other.values()), "params_c")
 
 
 def test_f16x3_maps_to_f16x3_gemm_with_one_warning_per_architecture():
