@@ -91,6 +91,23 @@ int nsr_refine_train_forward(const float* const* tensors, float* const* running,
 int nsr_refine_train_backward(const float* const* tensors, const float* g_out, float* const* grads, void* workspace,
                               size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream);
 
+/* The same pair with the arithmetic of the convolutions as an argument.  precision = NSR_FP32: the pair above, bit for bit (the
+ * two entry points above are calls of these).  precision = NSR_F16X3 ("f16x3_mixed" in the Python layer): the forward
+ * convolutions of layers 1 .. 18 and the input gradients of the stride-1 layers (with and without the x2 upsample) run on the
+ * split-fp16 MFMA (three terms per product, products exact to ~2^-21, fp32 accumulation) and gather the 3 x 3 window on the
+ * fly -- no im2col, split-K or dcol matrix; E.conv1's forward (K = 32), the stride-2 layers' input gradients, BatchNorm, the
+ * max over the references, the per-channel gradients and ALL weight gradients stay fp32 as above.  Any other value is
+ * NSR_ERR_UNSUPPORTED, returned before anything else is looked at.
+ * The saved state and the two size queries do not depend on the precision: a backward of either precision runs on the
+ * saved state of a forward of either (the header records the forward's, nothing requires it to match).  At NSR_F16X3 the
+ * outputs do not depend on img_chunk bit for bit either, and identical calls give identical bits: the range of the gradient
+ * operand is tracked with an integer maximum, not a float atomic. */
+int nsr_refine_train_forward_p(int precision, const float* const* tensors, float* const* running, float momentum,
+                               const float* x_synth, const float* x_candi, int B, int R, int H, int W, int img_chunk, float* out,
+                               void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream);
+int nsr_refine_train_backward_p(int precision, const float* const* tensors, const float* g_out, float* const* grads,
+                                void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream);
+
 /* ---- patch tiler / stitcher around the network (the 'test' path of data/llff_refine_dataset.py:303-340 and
  * models/refine_model.py:205-216): an SR image is cut into `patch` x `patch` tiles on a grid (x outer, y inner, starts
  * clamped to size - patch); each tile gets `n_ref` reference patches whose top-left corners are the first `n_ref`

@@ -36,6 +36,7 @@ UNITS = [
     ("nsr_warp.hip", ["-ffp-contract=off"]),
     ("nsr_refine.hip", ["-ffp-contract=off"]),
     ("nsr_refine_train.hip", ["-ffp-contract=off"]),
+    ("nsr_refine_dgrad_f16.hip", ["-ffp-contract=off"]),
     ("nsr_image.hip", ["-ffp-contract=off"]),
     ("nsr_metrics.hip", ["-ffp-contract=off"]),
     ("nsr_losses.hip", ["-ffp-contract=off"]),
@@ -156,6 +157,10 @@ if os.path.exists(_HEADS_HOOKS_SRC):
 _REFINE_TRAIN_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_train.hip")
 if os.path.exists(_REFINE_TRAIN_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_REFINE_TRAIN_HOOKS_SRC)
+# ... and the launchers of its split-fp16 forward and input gradient (tests/test_gpu_refine_mixed_units.py); same condition
+_REFINE_MIXED_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_mixed.hip")
+if os.path.exists(_REFINE_MIXED_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_REFINE_MIXED_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -15,6 +15,12 @@
 // are routed to the winning reference, skip-connection gradients are accumulated in place in the gradient of the
 // concatenated buffers, the encoder's second call adds into the gradients of its first.
 //
+// NSR_F16X3 (opt-in; nsr_refine_train_forward_p / _backward_p): the forward convolutions of layers 1 .. 18 are one
+// gemm_f16x3 call per site that gathers the window from the saved fp32 input (no im2col, no split-K, no chunks), the input
+// gradients of the stride-1 sites an implicit convolution of dZ with the flipped weight (nsr_refine_dgrad_f16.hip; behind an
+// upsample at the upsampled extent, then a 2 x 2 fold).  Everything else, the weight gradients included, is as above, and the
+// saved state is the same: a backward of either precision runs on the saved state of a forward of either.
+//
 // Every reduction has a fixed order (no float atomics): two identical calls give identical bits.  The 17 convolution
 // biases in front of a BatchNorm are cancelled by the mean subtraction: their gradients are DEFINED as exact zeros.
 //
@@ -40,7 +46,7 @@ constexpr uint64_t kMagic = 0x31545246525343ull;               // "CSRFRT1"
 constexpr int64_t kHeaderFloats = 64;
 struct Header {
   uint64_t magic, floats;
-  int B, R, H, W, img_chunk, pad_;
+  int B, R, H, W, img_chunk, precision;   // precision: of the forward that wrote it (informative: a backward of either runs on it)
 };
 static_assert(sizeof(Header) <= kHeaderFloats * 4 && sizeof(Header) % 4 == 0, "header");
 
@@ -170,49 +176,70 @@ __global__ void __launch_bounds__(256) bn_relu_kernel(const float* __restrict__ 
                                                              bn_act(v.z, mu.z, rs.z, g.z, b.z), bn_act(v.w, mu.w, rs.w, g.w, b.w));
 }
 
+// The range word of the split-fp16 input gradient (nsr_refine_train_work.h): *max_bits = max(*max_bits, float bits of the
+// wave's largest |v|).  Every lane of the wave calls it (lanes without an element pass 0).  An integer maximum of bit patterns
+// does not depend on the order; the plain read in front only spares the atomics that could not raise the word.
+__device__ __forceinline__ void raise_max_bits(unsigned* max_bits, unsigned bits) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)bits, o, 64);
+    bits = bits > t ? bits : t;
+  }
+  if ((threadIdx.x & 63) == 0 && bits > __hip_atomic_load(max_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(max_bits, bits);
+}
+__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+__device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+
 // dZ = gamma rstd (dy - sum dy / n - xhat sum(dy xhat) / n), dy = dA [a > 0]
 __global__ void __launch_bounds__(256) bn_bwd_kernel(const float* __restrict__ z, const float* __restrict__ da, int64_t ldda,
                                                      const float* __restrict__ stat, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, const float* __restrict__ m, int64_t rows, int C,
-                                                     float* __restrict__ dz) {
+                                                     float* __restrict__ dz, unsigned* __restrict__ max_bits) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= rows * (C / 4)) return;
-  const int c = (int)(idx % (C / 4)) * 4;
-  const int64_t r = idx / (C / 4);
-  const float4 v4 = *reinterpret_cast<const float4*>(z + r * C + c), d4 = *reinterpret_cast<const float4*>(da + r * ldda + c);
-  const float v[4] = {v4.x, v4.y, v4.z, v4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w};
-  float o[4];
+  unsigned mb = 0u;
+  if (idx < rows * (C / 4)) {
+    const int c = (int)(idx % (C / 4)) * 4;
+    const int64_t r = idx / (C / 4);
+    const float4 v4 = *reinterpret_cast<const float4*>(z + r * C + c), d4 = *reinterpret_cast<const float4*>(da + r * ldda + c);
+    const float v[4] = {v4.x, v4.y, v4.z, v4.w}, d[4] = {d4.x, d4.y, d4.z, d4.w};
+    float o[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float mean = stat[c + e], rstd = stat[C + c + e], g = gamma[c + e];
-    const float dy = bn_act(v[e], mean, rstd, g, beta[c + e]) > 0.0f ? d[e] : 0.0f;
-    const float xhat = (v[e] - mean) * rstd;
-    o[e] = (g * rstd) * ((dy - m[c + e]) - xhat * m[C + c + e]);
+    for (int e = 0; e < 4; ++e) {
+      const float mean = stat[c + e], rstd = stat[C + c + e], g = gamma[c + e];
+      const float dy = bn_act(v[e], mean, rstd, g, beta[c + e]) > 0.0f ? d[e] : 0.0f;
+      const float xhat = (v[e] - mean) * rstd;
+      o[e] = (g * rstd) * ((dy - m[c + e]) - xhat * m[C + c + e]);
+    }
+    *reinterpret_cast<float4*>(dz + r * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+    mb = umax(umax(abs_bits(o[0]), abs_bits(o[1])), umax(abs_bits(o[2]), abs_bits(o[3])));
   }
-  *reinterpret_cast<float4*>(dz + r * C + c) = make_float4(o[0], o[1], o[2], o[3]);
+  if (max_bits) raise_max_bits(max_bits, mb);      // outside the branch: every lane of the wave takes part in the shuffles
 }
 
 // E.conv1 (ReLU only): dZ = dA [a > 0]
 __global__ void __launch_bounds__(256) relu_bwd_kernel(const float* __restrict__ a, const float* __restrict__ da, int64_t n,
-                                                       float* __restrict__ dz) {
+                                                       float* __restrict__ dz, unsigned* __restrict__ max_bits) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n) return;
-  dz[idx] = a[idx] > 0.0f ? da[idx] : 0.0f;
+  float v = 0.0f;
+  if (idx < n) dz[idx] = v = a[idx] > 0.0f ? da[idx] : 0.0f;
+  if (max_bits) raise_max_bits(max_bits, abs_bits(v));
 }
 
 // D.conv9 (tanh): dZ[(b, px)][c] = g_out[b][c][px] (1 - y^2) for c < 3, 0 for the 29 padding columns
 __global__ void __launch_bounds__(256) tanh_bwd_kernel(const float* __restrict__ y, const float* __restrict__ g_out, int64_t px_per_img,
-                                                       int64_t rows, float* __restrict__ dz) {
+                                                       int64_t rows, float* __restrict__ dz, unsigned* __restrict__ max_bits) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= rows * 32) return;
-  const int c = (int)(idx & 31);
-  const int64_t r = idx >> 5;
   float v = 0.0f;
-  if (c < 3) {
-    const float t = y[r * 3 + c];
-    v = g_out[((r / px_per_img) * 3 + c) * px_per_img + r % px_per_img] * (1.0f - t * t);
+  if (idx < rows * 32) {
+    const int c = (int)(idx & 31);
+    const int64_t r = idx >> 5;
+    if (c < 3) {
+      const float t = y[r * 3 + c];
+      v = g_out[((r / px_per_img) * 3 + c) * px_per_img + r % px_per_img] * (1.0f - t * t);
+    }
+    dz[idx] = v;
   }
-  dz[idx] = v;
+  if (max_bits) raise_max_bits(max_bits, abs_bits(v));
 }
 
 // dst[(b, px)][c] = max_r src[(b R + r, px)][c], idx = the FIRST r that reaches it (torch.max; NaN wins as in torch)
@@ -368,18 +395,18 @@ int refine_bn_relu(hipStream_t st, const float* z, const float* stat, const floa
   return NSR_OK;
 }
 int refine_bn_bwd(hipStream_t st, const float* z, const float* da, int64_t ldda, const float* stat, const float* gamma,
-                  const float* beta, const float* m, int64_t rows, int C, float* dz) {
-  hipLaunchKernelGGL(bn_bwd_kernel, blocks(rows * (C / 4)), dim3(256), 0, st, z, da, ldda, stat, gamma, beta, m, rows, C, dz);
+                  const float* beta, const float* m, int64_t rows, int C, float* dz, unsigned* max_bits) {
+  hipLaunchKernelGGL(bn_bwd_kernel, blocks(rows * (C / 4)), dim3(256), 0, st, z, da, ldda, stat, gamma, beta, m, rows, C, dz, max_bits);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
-int refine_relu_bwd(hipStream_t st, const float* a, const float* da, int64_t n, float* dz) {
-  hipLaunchKernelGGL(relu_bwd_kernel, blocks(n), dim3(256), 0, st, a, da, n, dz);
+int refine_relu_bwd(hipStream_t st, const float* a, const float* da, int64_t n, float* dz, unsigned* max_bits) {
+  hipLaunchKernelGGL(relu_bwd_kernel, blocks(n), dim3(256), 0, st, a, da, n, dz, max_bits);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
-int refine_tanh_bwd(hipStream_t st, const float* y, const float* g_out, int64_t px_per_img, int64_t rows, float* dz) {
-  hipLaunchKernelGGL(tanh_bwd_kernel, blocks(rows * 32), dim3(256), 0, st, y, g_out, px_per_img, rows, dz);
+int refine_tanh_bwd(hipStream_t st, const float* y, const float* g_out, int64_t px_per_img, int64_t rows, float* dz, unsigned* max_bits) {
+  hipLaunchKernelGGL(tanh_bwd_kernel, blocks(rows * 32), dim3(256), 0, st, y, g_out, px_per_img, rows, dz, max_bits);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
@@ -613,12 +640,13 @@ Geo geo(const Site& s) {
   return g;
 }
 
-int relayout(hipStream_t st, const Site& s, const float* const* t, float* wr) {
+// f16x3: the same matrix x 2^6 as (hi, lo) fp16 halves (pack_conv_kernel), the operand of gemm_f16x3
+int relayout(hipStream_t st, const Site& s, const float* const* t, float* wr, int f16x3 = 0) {
   const Layer& L = layer(s.l);
   const int kp = kp_of(s.l), np = np_of(s.l);
   const int64_t n = (int64_t)np * kp + np;
   hipLaunchKernelGGL(pack_conv_kernel, blocks(n), dim3(256), 0, st, t[t_of(s.l)], t[t_of(s.l) + 1], (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, L.cin, L.cout, kp, np, 0, wr);
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, L.cin, L.cout, kp, np, f16x3, wr);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
@@ -641,12 +669,22 @@ int im2col(hipStream_t st, const Site& s, const Geo& g, const float* x_nchw, int
     if (np_ < 0) return np_;          \
   } while (0)
 
+// the range word of a site's split-fp16 input gradient (nsr_refine_train_work.h): the first of the kCMax floats behind the
+// re-laid weight, which hold the bias in the forward and nothing the backward reads
+inline unsigned* range_word(const Work& w) { return reinterpret_cast<unsigned*>(w.wr + (int64_t)kCMax * kKpMax); }
+
 int site_forward(hipStream_t st, const Site& s, const float* const* t, float* const* running, float momentum, const float* x_nchw,
-                 int chunk, const Work& w) {
+                 int chunk, const Work& w, int prec) {
   const Layer& L = layer(s.l);
   const Geo g = geo(s);
-  NSR_TRY(relayout(st, s, t, w.wr));
-  for (int i0 = 0; i0 < s.n_img; i0 += chunk) {
+  // NSR_F16X3, layers 1 .. 18 (cin % 32 == 0): ONE split-fp16 GEMM per site that gathers the 3 x 3 window from the saved fp32
+  // input while it stages it -- no im2col, no split-K, no chunks.  Layer 0 (K = 32) stays on the fp32 route.
+  const bool f16 = prec == NSR_F16X3 && s.l != 0;
+  NSR_TRY(relayout(st, s, t, w.wr, f16 ? 1 : 0));
+  if (f16)
+    NSR_TRY(refine_conv_f16x3(st, at(s.src), s.src.ld, L.cin, s.n_img, s.Hs, s.Ws, L.stride, L.up, w.wr, g.np, L.cout,
+                              L.bn ? (int)kActNone : L.act, L.bn ? s.Z : at(s.dst), L.bn ? (int64_t)L.cout : s.dst.ld));
+  for (int i0 = 0; i0 < s.n_img && !f16; i0 += chunk) {
     const int nc = s.n_img - i0 < chunk ? s.n_img - i0 : chunk;
     NSR_TRY(im2col(st, s, g, x_nchw, i0, nc, w.col));
     // K in chains of kFwdKChunk: in ONE chain the fp32 MFMA adds a K of up to 13,824 with 2.5 - 4 x the rounding error of
@@ -689,13 +727,19 @@ int site_forward(hipStream_t st, const Site& s, const float* const* t, float* co
 
 // `acc`: this site adds to the parameter gradients (the encoder's second call)
 int site_backward(hipStream_t st, const Site& s, const float* const* t, float* const* grads, const float* g_out, const float* x_nchw,
-                  int chunk, const Work& w, int acc) {
+                  int chunk, const Work& w, int acc, int prec) {
   const Layer& L = layer(s.l);
   const Geo g = geo(s);
   const int64_t rows = (int64_t)s.n_img * g.rows_img;
   const int C = L.cout, ldz = g.np;       // dZ is dense: Cout columns, 32 for D.conv9
   const int p = p_of(s.l);
   int np;
+  // NSR_F16X3: the input gradient of a stride-1 site is an implicit convolution of dZ on the split-fp16 MFMA; the kernel that
+  // writes dZ leaves its largest magnitude in the range word.  Stride-2 sites (the accumulating ones) keep dcol + col2im.
+  const bool implicit = prec == NSR_F16X3 && s.l != 0 && L.stride == 1;
+  unsigned* const mbits = implicit ? range_word(w) : nullptr;
+  if (implicit && s.gacc) return NSR_ERR_UNSUPPORTED;
+  if (mbits && hipMemsetAsync(mbits, 0, sizeof(unsigned), st) != hipSuccess) return NSR_ERR_LAUNCH;
   // ---- dZ and the gradients of the per-channel parameters
   if (L.bn) {
     const float *gamma = t[t_of(s.l) + 2], *beta = t[t_of(s.l) + 3];
@@ -704,11 +748,11 @@ int site_backward(hipStream_t st, const Site& s, const float* const* t, float* c
     r.rows = rows; r.C = C; r.part = w.red;
     NSR_REDUCE(np, st, 2, r);
     NSR_TRY(refine_fin_bn_bwd(st, w.red, np, C, rows, acc, grads[p + 2], grads[p + 3], w.m));
-    NSR_TRY(refine_bn_bwd(st, s.Z, at(s.gdst), s.gdst.ld, s.stat, gamma, beta, w.m, rows, C, w.gz));
+    NSR_TRY(refine_bn_bwd(st, s.Z, at(s.gdst), s.gdst.ld, s.stat, gamma, beta, w.m, rows, C, w.gz, mbits));
     // the bias in front of a BatchNorm is cancelled by the mean subtraction: its gradient is exactly zero
     if (!acc && hipMemsetAsync(grads[p + 1], 0, (size_t)C * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
   } else {
-    if (L.act == kActTanh) NSR_TRY(refine_tanh_bwd(st, s.dst.p, g_out, g.rows_img, rows, w.gz));
+    if (L.act == kActTanh) NSR_TRY(refine_tanh_bwd(st, s.dst.p, g_out, g.rows_img, rows, w.gz, mbits));
     else NSR_TRY(refine_relu_bwd(st, s.dst.p, s.gdst.p, rows * C, w.gz));
     ReduceArgs r{};
     r.x = w.gz; r.ldx = ldz; r.rows = rows; r.C = ldz; r.part = w.red;
@@ -717,7 +761,8 @@ int site_backward(hipStream_t st, const Site& s, const float* const* t, float* c
   }
   // 32 zeroed rows behind dZ: the K padding of the last chunk's weight-gradient product
   if (hipMemsetAsync(w.gz + rows * ldz, 0, (size_t)32 * ldz * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
-  if (s.l != 0) NSR_TRY(relayout(st, s, t, w.wr));
+  if (implicit) NSR_TRY(refine_flip_pack(st, t[t_of(s.l)], L.cin, C, g.np, reinterpret_cast<unsigned short*>(w.wr)));
+  else if (s.l != 0) NSR_TRY(relayout(st, s, t, w.wr));
   const int Mw = C < 4 ? 4 : C;           // rows of the weight-gradient product (a K-major operand needs >= 4)
   for (int i0 = 0; i0 < s.n_img; i0 += chunk) {
     const int nc = s.n_img - i0 < chunk ? s.n_img - i0 : chunk;
@@ -735,7 +780,7 @@ int site_backward(hipStream_t st, const Site& s, const float* const* t, float* c
     a.splits = (int)splits; a.split_stride = (int64_t)Mw * g.kp;
     NSR_TRY(gemm(a, st));
     NSR_TRY(refine_wgrad_reduce(st, w.part, (int)splits, a.split_stride, g.kp, L.cin, C, (acc || i0 > 0) ? 1 : 0, grads[p]));
-    if (s.l == 0) continue;               // no gradient with respect to the input images
+    if (s.l == 0 || implicit) continue;   // no gradient with respect to the input images; implicit: below, whole site
     // ---- input gradient: dcol = dZ W, then every input pixel gathers its taps
     GemmArgs d{};
     d.A = dz; d.lda = ldz; d.B = w.wr; d.ldb = g.kp; d.b_kmajor = 1; d.C = w.dcol; d.ldc = g.kp;
@@ -743,6 +788,21 @@ int site_backward(hipStream_t st, const Site& s, const float* const* t, float* c
     NSR_TRY(gemm(d, st));
     NSR_TRY(refine_col2im(st, w.dcol, g.kp, L.cin, nc, s.Hs, s.Ws, L.stride, L.up, g.Ho, g.Wo, s.gacc,
                           at(s.gsrc) + (int64_t)i0 * s.Hs * s.Ws * s.gsrc.ld, s.gsrc.ld));
+  }
+  if (!implicit) return NSR_OK;
+  // ---- input gradient, NSR_F16X3: dX = dZ * flipped weight, stored straight into the gsrc slice
+  const unsigned short* bw = reinterpret_cast<const unsigned short*>(w.wr);
+  if (!L.up) return refine_dgrad_f16x3(st, w.gz, ldz, bw, L.cin, s.n_img, s.Hs, s.Ws, mbits, at(s.gsrc), s.gsrc.ld);
+  // behind the x2 upsample: the same convolution at the upsampled extent into the dcol buffer (free here), as many images per
+  // pass as fit, then every source pixel sums its 2 x 2 block.  A pass changes nothing per element: no dependence on img_chunk.
+  const int64_t per_img = g.rows_img * L.cin;            // rows_img = 4 Hs Ws
+  int64_t pass = w.dcol_floats / per_img;
+  if (pass < 1) return NSR_ERR_WORKSPACE;
+  pass = pass > s.n_img ? s.n_img : pass;
+  for (int64_t i0 = 0; i0 < s.n_img; i0 += pass) {
+    const int nc = (int)(s.n_img - i0 < pass ? s.n_img - i0 : pass);
+    NSR_TRY(refine_dgrad_f16x3(st, w.gz + i0 * g.rows_img * ldz, ldz, bw, L.cin, nc, g.Ho, g.Wo, mbits, w.dcol, L.cin));
+    NSR_TRY(refine_fold2x2(st, w.dcol, L.cin, nc, s.Hs, s.Ws, at(s.gsrc) + i0 * s.Hs * s.Ws * s.gsrc.ld, s.gsrc.ld));
   }
   return NSR_OK;
 }
@@ -767,9 +827,11 @@ extern "C" size_t nsr_refine_train_saved_bytes(int B, int R, int H, int W) {
   return (size_t)carve_saved(B, R, H, W, nullptr, nullptr) * sizeof(float);
 }
 
-extern "C" int nsr_refine_train_forward(const float* const* tensors, float* const* running, float momentum, const float* x_synth,
-                                        const float* x_candi, int B, int R, int H, int W, int img_chunk, float* out, void* workspace,
-                                        size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream) {
+extern "C" int nsr_refine_train_forward_p(int precision, const float* const* tensors, float* const* running, float momentum,
+                                          const float* x_synth, const float* x_candi, int B, int R, int H, int W, int img_chunk,
+                                          float* out, void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes,
+                                          void* stream) {
+  if (precision != NSR_FP32 && precision != NSR_F16X3) return NSR_ERR_UNSUPPORTED;
   NSR_TRY(check_shape(B, R, H, W));
   if (!tensors || !x_synth || !x_candi || !out || !workspace || !saved || !(momentum >= 0.0f && momentum <= 1.0f)) return NSR_ERR_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0 || (reinterpret_cast<uintptr_t>(saved) & 255) != 0) return NSR_ERR_INVALID_ARG;
@@ -789,7 +851,7 @@ extern "C" int nsr_refine_train_forward(const float* const* tensors, float* cons
   carve_saved(B, R, H, W, &k, static_cast<float*>(saved));
   Site s[kNSites];
   build_sites(s, B, R, H, W, k, w);
-  const Header h{kMagic, (uint64_t)total, B, R, H, W, chunk, 0};
+  const Header h{kMagic, (uint64_t)total, B, R, H, W, chunk, precision};
   hipLaunchKernelGGL(header_kernel, dim3(1), dim3(64), 0, st, h, reinterpret_cast<unsigned*>(saved));
   NSR_CHECK_LAUNCH();
   // encoder on the synthesised patches, encoder on the references, the max over the references, decoder: the running
@@ -798,18 +860,27 @@ extern "C" int nsr_refine_train_forward(const float* const* tensors, float* cons
   if (hipMemcpyAsync(k.x[0], x_synth, (size_t)B * 3 * px0 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
       hipMemcpyAsync(k.x[1], x_candi, (size_t)B * R * 3 * px0 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     return NSR_ERR_LAUNCH;
-  for (int i = 0; i < 7; ++i) NSR_TRY(site_forward(st, s[i], tensors, running, momentum, k.x[0], chunk, w));
-  for (int i = 7; i < 14; ++i) NSR_TRY(site_forward(st, s[i], tensors, running, momentum, k.x[1], chunk, w));
+  for (int i = 0; i < 7; ++i) NSR_TRY(site_forward(st, s[i], tensors, running, momentum, k.x[0], chunk, w, precision));
+  for (int i = 7; i < 14; ++i) NSR_TRY(site_forward(st, s[i], tensors, running, momentum, k.x[1], chunk, w, precision));
   const int64_t px[4] = {px0, px0 / 4, px0 / 16, px0 / 64};
   const int fcw[4] = {128, 256, 512, 512};
   const Act mx[4] = {{k.cat7, 384, 256}, {k.cat5, 768, 512}, {k.cat3, 1536, 1024}, {k.cat1, 1024, 512}};
   for (int i = 0; i < 4; ++i) NSR_TRY(refine_max_idx(st, k.fc[i], fcw[i], R, px[i], B, at(mx[i]), mx[i].ld, k.win[i]));
-  for (int i = 14; i < kNSites; ++i) NSR_TRY(site_forward(st, s[i], tensors, running, momentum, nullptr, chunk, w));
+  for (int i = 14; i < kNSites; ++i) NSR_TRY(site_forward(st, s[i], tensors, running, momentum, nullptr, chunk, w, precision));
   return refine_nhwc3_to_nchw(st, k.rgb, px0, B, out);
 }
 
-extern "C" int nsr_refine_train_backward(const float* const* tensors, const float* g_out, float* const* grads, void* workspace,
-                                         size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream) {
+extern "C" int nsr_refine_train_forward(const float* const* tensors, float* const* running, float momentum, const float* x_synth,
+                                        const float* x_candi, int B, int R, int H, int W, int img_chunk, float* out, void* workspace,
+                                        size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream) {
+  return nsr_refine_train_forward_p(NSR_FP32, tensors, running, momentum, x_synth, x_candi, B, R, H, W, img_chunk, out, workspace,
+                                    workspace_bytes, saved, saved_bytes, stream);
+}
+
+extern "C" int nsr_refine_train_backward_p(int precision, const float* const* tensors, const float* g_out, float* const* grads,
+                                           void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes,
+                                           void* stream) {
+  if (precision != NSR_FP32 && precision != NSR_F16X3) return NSR_ERR_UNSUPPORTED;
   if (!tensors || !g_out || !grads || !workspace || !saved) return NSR_ERR_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0 || (reinterpret_cast<uintptr_t>(saved) & 255) != 0) return NSR_ERR_INVALID_ARG;
   for (int i = 0; i < NSR_REFINE_N_TENSORS; ++i)
@@ -837,13 +908,18 @@ extern "C" int nsr_refine_train_backward(const float* const* tensors, const floa
   build_sites(s, B, R, H, W, k, w);
   // decoder, then the encoder's call on the synthesised patches (its features' gradients sit in the gradients of the
   // concatenated buffers), then the call on the references (gradients routed to the winners) ADDING to the same gradients
-  for (int i = kNSites - 1; i >= 14; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, g_out, nullptr, chunk, w, 0));
-  for (int i = 6; i >= 0; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[0], chunk, w, 0));
+  for (int i = kNSites - 1; i >= 14; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, g_out, nullptr, chunk, w, 0, precision));
+  for (int i = 6; i >= 0; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[0], chunk, w, 0, precision));
   const int64_t px0 = (int64_t)H * W;
   const int64_t px[4] = {px0, px0 / 4, px0 / 16, px0 / 64};
   const int fcw[4] = {128, 256, 512, 512};
   const Act gmx[4] = {{w.gcat7, 384, 256}, {w.gcat5, 768, 512}, {w.gcat3, 1536, 1024}, {w.gcat1, 1024, 512}};
   for (int i = 0; i < 4; ++i) NSR_TRY(refine_route(st, at(gmx[i]), gmx[i].ld, k.win[i], fcw[i], R, px[i], B, w.gfc[i]));
-  for (int i = 13; i >= 7; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[1], chunk, w, 1));
+  for (int i = 13; i >= 7; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[1], chunk, w, 1, precision));
   return NSR_OK;
+}
+
+extern "C" int nsr_refine_train_backward(const float* const* tensors, const float* g_out, float* const* grads, void* workspace,
+                                         size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream) {
+  return nsr_refine_train_backward_p(NSR_FP32, tensors, g_out, grads, workspace, workspace_bytes, saved, saved_bytes, stream);
 }

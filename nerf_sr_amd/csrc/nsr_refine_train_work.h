@@ -46,11 +46,15 @@ NSR_INTERNAL int refine_bn_relu(hipStream_t st, const float* z, const float* sta
                                 int C, float* dst, int64_t ld);
 // dZ = gamma rstd (dy - m[c] - xhat m[C + c]), dy = dA [bn_act(z) > 0]; z, dz dense, dA with row stride ldda; C % 4 == 0
 NSR_INTERNAL int refine_bn_bwd(hipStream_t st, const float* z, const float* da, int64_t ldda, const float* stat, const float* gamma,
-                               const float* beta, const float* m, int64_t rows, int C, float* dz);
+                               const float* beta, const float* m, int64_t rows, int C, float* dz, unsigned* max_bits = nullptr);
 // dz[i] = a[i] > 0 ? da[i] : 0 over n elements
-NSR_INTERNAL int refine_relu_bwd(hipStream_t st, const float* a, const float* da, int64_t n, float* dz);
+NSR_INTERNAL int refine_relu_bwd(hipStream_t st, const float* a, const float* da, int64_t n, float* dz, unsigned* max_bits = nullptr);
 // dz (rows x 32): columns 0..2 = g_out (NCHW, px_per_img pixels per image) (1 - y^2), y (rows x 3); columns 3..31 zero
-NSR_INTERNAL int refine_tanh_bwd(hipStream_t st, const float* y, const float* g_out, int64_t px_per_img, int64_t rows, float* dz);
+NSR_INTERNAL int refine_tanh_bwd(hipStream_t st, const float* y, const float* g_out, int64_t px_per_img, int64_t rows, float* dz,
+                                 unsigned* max_bits = nullptr);
+// `max_bits` of the three above (null: off): the RANGE WORD of the split-fp16 input gradient.  The kernel raises *max_bits to the
+// float bits of the largest |dz| it wrote (sign cleared; integer atomicMax on the bit pattern, one per wave: the result does not
+// depend on the order, and a NaN or an infinity ends above every finite value).  The caller zeroes the word first.
 
 // dst[(b, px)][c] = max over r of src[(b R + r, px)][c] (row stride ld), win = the first r that reaches it (NaN wins)
 NSR_INTERNAL int refine_max_idx(hipStream_t st, const float* src, int C, int R, int64_t px_per_img, int B, float* dst, int64_t ld,
@@ -69,6 +73,24 @@ NSR_INTERNAL int refine_wgrad_reduce(hipStream_t st, const float* part, int spli
 // forward split-K partials (splits, M x np) in order in double, + bias, activation (GemmAct) -> dst[m][n], n < cout
 NSR_INTERNAL int refine_fwd_reduce(hipStream_t st, const float* part, int splits, int64_t split_stride, int np, int cout,
                                    const float* bias, int act, int64_t M, float* dst, int64_t ld);
+// ---- NSR_F16X3 (nsr_refine_dgrad_f16.hip): the split-fp16 MFMA with implicit gather, forward and input gradient
+// Forward convolution of one site: 3x3 / pad 1 (stride 1 or 2, optionally behind a nearest x2 upsample) gathered from the fp32
+// NHWC activation src (row stride lds, channels [0, cin), cin % 32 == 0), weights `packed` = pack_conv_kernel's f16x3 layout of
+// the RAW weight ([hi (np x 9 cin)] [lo] halves, then np bias floats) -> dst[m][n] = act(sum 2^-6 + bias), n < cout, row stride
+// ld.  One gemm_f16x3 call on its fp32-A route; NSR_ERR_UNSUPPORTED where the shape would take another one.
+NSR_INTERNAL int refine_conv_f16x3(hipStream_t st, const float* src, int64_t lds, int cin, int n_img, int Hs, int Ws, int stride,
+                                   int up, const float* packed, int np, int cout, int act, float* dst, int64_t ld);
+// dst = [hi (cin x 9 np)] [lo] halves of B'[c][((2 - ky) * 3 + (2 - kx)) np + n] = 2^6 w[n][c][ky][kx] (w: (cout, cin, 3, 3));
+// columns n >= cout zero
+NSR_INTERNAL int refine_flip_pack(hipStream_t st, const float* w, int cin, int cout, int np, unsigned short* dst);
+// Input gradient of a stride-1 convolution as an implicit 3x3 / pad 1 convolution of dz (n_img H W rows x np, dense) with
+// refine_flip_pack's operand: dst[(img, y, x)][c] (row stride ld, c < cin) is STORED.  *max_bits = float bits of max |dz| (the
+// range word above).  cin % 128 == 0 and np % 32 == 0, NSR_ERR_UNSUPPORTED otherwise.
+NSR_INTERNAL int refine_dgrad_f16x3(hipStream_t st, const float* dz, int np, const unsigned short* packed, int cin, int n_img, int H,
+                                    int W, const unsigned* max_bits, float* dst, int64_t ld);
+// the nearest x2 upsample backwards: dst[(img, sy, sx)][c] (row stride ld) = the 2 x 2 block of src (n_img, 2 Hs, 2 Ws, C dense)
+// summed in a fixed order; C % 4 == 0
+NSR_INTERNAL int refine_fold2x2(hipStream_t st, const float* src, int C, int n_img, int Hs, int Ws, float* dst, int64_t ld);
 // (B px_per_img, 3) NHWC -> (B, 3, px_per_img)
 NSR_INTERNAL int refine_nhwc3_to_nchw(hipStream_t st, const float* src, int64_t px_per_img, int B, float* dst);
 

@@ -268,11 +268,23 @@ def _ptr_array(tensors):
     return (c_void_p * len(tensors))(*[c_void_p(t.data_ptr()) for t in tensors])
 
 
+# training precisions: name -> the `precision` of nsr_refine_train_forward_p / _backward_p.  "f16x3_mixed": forward and input
+# gradients split-fp16, weight gradients fp32; the short name "f16x3" stays free for a pair whose weight gradient is 16-bit too
+TRAIN_PRECISIONS = {"fp32": _lib.NSR_FP32, "f16x3_mixed": _lib.NSR_F16X3}
+
+
+def _train_precision(precision, who: str) -> int:
+    if precision not in TRAIN_PRECISIONS:
+        raise ValueError(f"{who}: precision must be 'fp32' or 'f16x3_mixed' (got {precision!r}): the refinement network trains in "
+                         "fp32, or with the forward and the input gradients on the split-fp16 MFMA and fp32 weight gradients")
+    return TRAIN_PRECISIONS[precision]
+
+
 class _TrainRun:
     """The arguments of one forward_train call that are not differentiable tensors."""
 
-    def __init__(self, running, momentum, img_chunk):
-        self.running, self.momentum, self.img_chunk = running, momentum, img_chunk
+    def __init__(self, running, momentum, img_chunk, precision=_lib.NSR_FP32):
+        self.running, self.momentum, self.img_chunk, self.precision = running, momentum, img_chunk, precision
 
     def tensors106(self, params):
         by_name = dict(zip(TRAIN_PARAM_KEYS, params))
@@ -296,9 +308,9 @@ class _ForwardTrain(torch.autograd.Function):
         ws = _train_workspace(ctx.ws_need, x.device)
         saved = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
-        _lib.check(lib.nsr_refine_train_forward(run.tensors106(params), _ptr_array(run.running), run.momentum, _p(x), _p(c), B, R, H, W,
-                                                run.img_chunk, _p(out), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
-                   "nsr_refine_train_forward")
+        _lib.check(lib.nsr_refine_train_forward_p(run.precision, run.tensors106(params), _ptr_array(run.running), run.momentum, _p(x),
+                                                  _p(c), B, R, H, W, run.img_chunk, _p(out), _p(ws), ws.numel(), _p(saved),
+                                                  saved.numel(), _stream()), "nsr_refine_train_forward_p")
         ctx.save_for_backward(*params)       # an in-place update of a weight before the backward fails autograd's version check
         ctx.run, ctx.state = run, saved
         return out
@@ -312,21 +324,25 @@ class _ForwardTrain(torch.autograd.Function):
         grads = [torch.empty_like(p) for p in params]
         ws = _train_workspace(ctx.ws_need, saved.device)
         g_out = g_out.to(torch.float32).contiguous()
-        _lib.check(_lib.load().nsr_refine_train_backward(ctx.run.tensors106(params), _p(g_out), _ptr_array(grads), _p(ws), ws.numel(),
-                                                         _p(saved), saved.numel(), _stream()), "nsr_refine_train_backward")
+        _lib.check(_lib.load().nsr_refine_train_backward_p(ctx.run.precision, ctx.run.tensors106(params), _p(g_out), _ptr_array(grads),
+                                                           _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
+                   "nsr_refine_train_backward_p")
         ctx.state = None
         return (None, None, None) + tuple(grads)
 
 
 def forward_train(params, running, x_synth: torch.Tensor, list_x_candi: torch.Tensor, momentum: float = 0.1,
-                  img_chunk: Optional[int] = None) -> torch.Tensor:
+                  img_chunk: Optional[int] = None, precision: str = "fp32") -> torch.Tensor:
     """``MaxPoolingModel.forward`` in train mode (networks.py:964-990 under ``.train()``): BatchNorm normalises with the batch
     statistics of each call (the encoder's two calls each with their own), fp32.  ``params``: name -> CUDA fp32 leaf for the 72
     ``TRAIN_PARAM_KEYS``; ``running``: name -> tensor for the 34 ``RUNNING_KEYS``, updated IN PLACE (momentum; the encoder's
     twice).  Returns ``y`` (B, 3, H, W); any loss written in torch over it back-propagates through ``nsr_refine_train_backward``
     into the 72 parameters (once: the backward is not differentiable).  The 17 convolution biases in front of a BatchNorm get
     exact-zero gradients (include/nsr_refine.h).  There is no gradient with respect to the images (None).
-    ``img_chunk``: images whose im2col matrix is live at once (None: the library picks)."""
+    ``img_chunk``: images whose im2col matrix is live at once (None: the library picks).
+    ``precision``: ``"fp32"``, or ``"f16x3_mixed"`` -- the forward convolutions and the input gradients on the split-fp16 MFMA
+    with implicit gather, BatchNorm and the weight gradients fp32 (include/nsr_refine.h, nsr_refine_train_forward_p)."""
+    prec = _train_precision(precision, "forward_train")
     missing = [k for k in TRAIN_PARAM_KEYS if k not in params] + [k for k in RUNNING_KEYS if k not in running]
     if missing:
         raise KeyError(f"forward_train: missing {missing[:3]}{'...' if len(missing) > 3 else ''}")
@@ -338,13 +354,13 @@ def forward_train(params, running, x_synth: torch.Tensor, list_x_candi: torch.Te
         if not isinstance(t, torch.Tensor) or t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous() \
                 or tuple(t.shape) != tuple(REFINE_SPEC[k]):
             raise ValueError(f"forward_train: {k} must be a contiguous float32 tensor of shape {REFINE_SPEC[k]} on {x.device}")
-    run = _TrainRun(rs, float(momentum), 0 if img_chunk is None else int(img_chunk))
+    run = _TrainRun(rs, float(momentum), 0 if img_chunk is None else int(img_chunk), prec)
     return _ForwardTrain.apply(run, x, c, *ps)
 
 
 class RefineTrainer:
     """``RefineModel``'s training protocol (models/refine_model.py:84-175) for the ``MaxPoolingModel`` with reference patches,
-    fp32: ``set_input`` -> ``forward`` -> ``calculate_losses`` -> ``backward`` -> ``optimizer_step`` (``optimize_parameters``
+    fp32 (or ``precision="f16x3_mixed"``, see ``forward_train``): ``set_input`` -> ``forward`` -> ``calculate_losses`` -> ``backward`` -> ``optimizer_step`` (``optimize_parameters``
     does the four), Adam(lr, betas=(beta1, 0.999)) over the 72 parameters.  ``sd``: the reference's ``state_dict`` (tensors or
     arrays).  ``refine_with_ssim`` / ``lambda_refine_ssim`` are this build's addition, not the reference's: they add
     ``lambda_refine_ssim * (1 - SSIM(data_range=(-1, 1))(pred, gt_patch))`` -- the score ``evaluate_image`` reports, as a loss --
@@ -361,8 +377,7 @@ class RefineTrainer:
             if on:
                 raise NotImplementedError(f"RefineTrainer: {name} is not built in; compose that loss in torch over "
                                           "nerf_sr_amd.refine.forward_train, which back-propagates any torch loss")
-        if precision != "fp32":
-            raise ValueError(f"RefineTrainer: precision must be 'fp32' (got {precision!r}): the refinement network trains in fp32 only")
+        _train_precision(precision, "RefineTrainer")
         if not_use_ref:
             raise NotImplementedError("RefineTrainer: --not_use_ref training is not supported (inference is: MaxPoolingModel(not_use_ref=True))")
         if not (refine_with_l1 or refine_with_mse or refine_with_ssim):
@@ -375,7 +390,7 @@ class RefineTrainer:
         self.refine_with_l1, self.refine_with_mse = bool(refine_with_l1), bool(refine_with_mse)
         self.lambda_refine_l1, self.lambda_refine_mse = float(lambda_refine_l1), float(lambda_refine_mse)
         self.refine_with_ssim, self.lambda_refine_ssim = bool(refine_with_ssim), float(lambda_refine_ssim)
-        self.momentum, self.img_chunk = float(momentum), img_chunk
+        self.momentum, self.img_chunk, self.precision = float(momentum), img_chunk, precision
         dev = OrderedDict()
         for k, shape in REFINE_SPEC.items():
             v = sd[k]
@@ -396,7 +411,8 @@ class RefineTrainer:
             setattr(self, f"data_{name}", input[name].to(device=self.device, dtype=torch.float32).contiguous())
 
     def forward(self):
-        self.pred = forward_train(self.params, self.running, self.data_sr_patch, self.data_ref_patches, self.momentum, self.img_chunk)
+        self.pred = forward_train(self.params, self.running, self.data_sr_patch, self.data_ref_patches, self.momentum, self.img_chunk,
+                                  self.precision)
         return self.pred
 
     def calculate_losses(self):

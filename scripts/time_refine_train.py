@@ -11,11 +11,26 @@ synchronisation.  Recorded, not gated: nobody had measured either number.  Print
 
     python scripts/time_refine_train.py --out profiles/refine_train_timing.json
     rocprofv3 --kernel-trace --stats -d DIR -- python scripts/time_refine_train.py --only ours --repeats 1 --block 3
+
+`--precision f16x3_mixed` times the trainer at that precision (forward and input gradients split-fp16, weight gradients fp32).
+`--baseline-lib PATH` is the A/B against another build of the library -- the parent commit's, built beforehand as
+ab/libnsr_parent.so: every timed block then runs in a CHILD process of its own (a library is chosen when the package is
+imported: NSR_LIB_PATH), `--repeats` alternating rounds of
+
+    parent_fp32   the baseline library's fp32 step      ours_fp32   this build's fp32 step
+    ours_<precision>   this build at --precision        torch       the restatement
+
+and the verdicts the project's yardstick asks for are recorded: the new precision faster than the parent's fp32 step by more
+than three times the spread of the parent's repeats, this build's fp32 step within that spread of the parent's.
+
+    python scripts/time_refine_train.py --precision f16x3_mixed --baseline-lib ab/libnsr_parent.so \
+        --out profiles/refine_train_mixed_timing.json
 """
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 from collections import OrderedDict
@@ -38,7 +53,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--only", default="", help="'ours' or 'torch' (default: both, alternating)")
     ap.add_argument("--out", default="")
+    ap.add_argument("--precision", default="fp32", help="'fp32' or 'f16x3_mixed': RefineTrainer(precision=...)")
+    ap.add_argument("--baseline-lib", default="", help="another build of libnsr.so to time the fp32 step of, in child processes")
+    ap.add_argument("--child", default="", help=argparse.SUPPRESS)      # one block of one variant: what a child process runs
     a = ap.parse_args()
+    if a.baseline_lib and not a.child:
+        return ab_rounds(a)
+    if a.child == "parent_fp32":
+        # a library from before the entry points with a precision argument (NSR_LIB_PATH): its fp32 pair under their names
+        from nerf_sr_amd import _lib
+        new = [k for k in ("nsr_refine_train_forward_p", "nsr_refine_train_backward_p") if k in _lib.SIGNATURES]
+        sigs = {k: _lib.SIGNATURES.pop(k) for k in new}
+        lib = _lib.load()
+        for k, (res, args) in sigs.items():
+            try:
+                fn = getattr(lib, k)
+                fn.restype, fn.argtypes = res, args
+            except AttributeError:
+                old = getattr(lib, k[:-2])
+                setattr(lib, k, lambda prec, *rest, _f=old: _f(*rest))
     dev = torch.device("cuda", 0)
     B, R, P = a.batch, a.refs, a.patch
     gen = torch.Generator().manual_seed(3)
@@ -48,7 +81,7 @@ def main():
     sd = refine.make_refine_state_dict(7)
     variants = {}
     if a.only in ("", "ours"):
-        tr = refine.RefineTrainer(sd, lr=5e-4, device=dev)
+        tr = refine.RefineTrainer(sd, lr=5e-4, device=dev, precision=a.precision)
         tr.set_input({"sr_patch": x, "ref_patches": c, "gt_patch": gt})
         variants["ours"] = tr.optimize_parameters
     if a.only in ("", "torch"):
@@ -77,7 +110,11 @@ def main():
                 f()
             torch.cuda.synchronize()
             runs[name].append((time.perf_counter() - t0) * 1e3 / a.block)
-    res = {"shape": f"B = {B} patch sets, R = {R} references, {P} x {P}, fp32; forward -> L1 -> backward -> Adam; "
+    if a.child:
+        print(json.dumps({"ms": runs[a.only][0], "device": torch.cuda.get_device_name(dev),
+                          "peak_memory_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2)}))
+        return
+    res = {"shape": f"B = {B} patch sets, R = {R} references, {P} x {P}, ours: {a.precision}; forward -> L1 -> backward -> Adam; "
                     f"{a.repeats} alternating runs of {a.block} iterations after {a.warmup} warm-up iterations",
            "device": torch.cuda.get_device_name(dev), "conv_gmacs_forward": round(B * refine.refine_macs(P, P, R) / 1e9, 1),
            "peak_memory_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2), "variants": {}}
@@ -86,6 +123,55 @@ def main():
                               "spread_ms": round(max(v) - min(v), 2)}
     if len(runs) == 2:
         res["ours_over_torch"] = round(statistics.median(runs["ours"]) / statistics.median(runs["torch"]), 3)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def ab_rounds(a):
+    """--baseline-lib: `--repeats` alternating rounds, every block in a child process (one process, one library)."""
+    here = os.path.abspath(__file__)
+    base = os.path.abspath(a.baseline_lib)
+    if not os.path.exists(base):
+        raise SystemExit(f"{base} not found: build the parent commit's library there first")
+    mixed = f"ours_{a.precision}"
+    plan = [("parent_fp32", "ours", "fp32", base), ("ours_fp32", "ours", "fp32", "")]
+    if a.precision != "fp32":
+        plan.append((mixed, "ours", a.precision, ""))
+    plan.append(("torch", "torch", "fp32", ""))
+    runs, info = {name: [] for name, *_ in plan}, {}
+    for _ in range(a.repeats):
+        for name, only, prec, lib in plan:
+            env = dict(os.environ)
+            env.pop("NSR_LIB_PATH", None)
+            if lib:
+                env["NSR_LIB_PATH"] = lib
+            cmd = [sys.executable, here, "--child", name, "--only", only, "--precision", prec, "--repeats", "1", "--batch", str(a.batch),
+                   "--refs", str(a.refs), "--patch", str(a.patch), "--block", str(a.block), "--warmup", str(a.warmup)]
+            out = subprocess.run(cmd, env=env, check=True, capture_output=True, text=True, timeout=600).stdout
+            rec = json.loads(out.strip().splitlines()[-1])
+            runs[name].append(rec["ms"])
+            info[name] = rec
+            print(f"{name}: {rec['ms']:.2f} ms", flush=True)
+    med = {k: statistics.median(v) for k, v in runs.items()}
+    spread = max(runs["parent_fp32"]) - min(runs["parent_fp32"])
+    res = {"shape": f"B = {a.batch} patch sets, R = {a.refs} references, {a.patch} x {a.patch}; forward -> L1 -> backward -> Adam; "
+                    f"{a.repeats} alternating rounds, every block ({a.block} iterations after {a.warmup} warm-up iterations) in a "
+                    "process of its own",
+           "device": info["ours_fp32"]["device"], "baseline_lib": os.path.basename(base), "variants": {}}
+    for k, v in runs.items():
+        res["variants"][k] = {"ms_per_iteration_median": round(med[k], 2), "ms_per_iteration_runs": [round(t, 2) for t in v],
+                              "spread_ms": round(max(v) - min(v), 2), "peak_memory_gb": info[k]["peak_memory_gb"]}
+    res["parent_spread_ms"] = round(spread, 2)
+    res["ours_fp32_minus_parent_ms"] = round(med["ours_fp32"] - med["parent_fp32"], 2)
+    res["ours_fp32_within_parent_spread"] = bool(abs(med["ours_fp32"] - med["parent_fp32"]) <= spread)
+    if mixed in med:
+        res[f"{mixed}_gain_over_parent_ms"] = round(med["parent_fp32"] - med[mixed], 2)
+        res[f"{mixed}_faster_by_more_than_3_spreads"] = bool(med["parent_fp32"] - med[mixed] > 3 * spread)
+        res[f"{mixed}_over_torch"] = round(med[mixed] / med["torch"], 3)
+    res["ours_fp32_over_torch"] = round(med["ours_fp32"] / med["torch"], 3)
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
