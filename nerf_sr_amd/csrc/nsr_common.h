@@ -64,12 +64,14 @@ __device__ __forceinline__ float nsr_softplus_density(float x) { return logf(__f
 // --gamma_correct: out_rgbs = pow(out_rgbs, 1 / 2.2) on the per-sample colours (nerf_downX_model.py:271-276)
 __device__ __forceinline__ float nsr_gamma(float c) { return powf(c, 1.0f / 2.2f); }
 
-// ---- torch.linspace(0, 1, n) element i, fp32 (ATen CPU kernel: symmetric form,
-// start + step*i below the midpoint, end - step*(n-1-i) above it).
+// ---- torch.linspace(0, 1, n) element i, fp32, in the form torch produces and the fixtures under tests/golden record:
+// symmetric, start + step*i below the midpoint and end - step*(n-1-i) above it, the upper half with ONE rounding (a fused
+// multiply-subtract; rounding the product first is one ulp off on some entries of most n).  The fmaf is explicit, so
+// -ffp-contract=off does not touch it.  Pinned against torch.linspace for n = 1..600 by tests/test_ray_stages_cpu.py.
 __device__ __forceinline__ float nsr_linspace01(int i, int n) {
   if (n == 1) return 0.0f;
   const float step = 1.0f / (float)(n - 1);
-  return (i < n / 2) ? __fmul_rn(step, (float)i) : __fsub_rn(1.0f, __fmul_rn(step, (float)(n - 1 - i)));
+  return (i < n / 2) ? __fmul_rn(step, (float)i) : fmaf(-step, (float)(n - 1 - i), 1.0f);
 }
 
 // z of the deterministic stratified sampler (models/utils.py:31-35), fp32, no contraction.

@@ -132,37 +132,14 @@ def _exp(t, Et):
     return v, E + TRANSCENDENTAL_ULPS * ulp32(v + E)
 
 
-def error_bounds(rgb4, sigma, z, g_comp, flags, g_depth=None, g_opacity=None, g_weights=None):
-    """Elementwise bounds (P, 4) on |d4 of composite_bwd_kernel - ref_composite_bwd|, and (R, 4) on bias_part.  Derived, not
-    fitted: a running error analysis of the arithmetic csrc/nsr_train.hip states, carried out on the reference's own values.
-
-    Every intermediate carries (value v, bound E >= |v^ - v|) where v^ is what a correct fp32 implementation holds.  Rules,
-    u = 2^-24:
-      one fp32 operation on operands known to Ea, Eb: the exact operation's propagated error (product: |a| Eb + |b| Ea + Ea Eb;
-        sum: Ea + Eb) and then one rounding, u (|v| + E) (+ 2^-149 should it underflow);
-      expf / logf / powf: the argument's error through the function, plus TRANSCENDENTAL_ULPS ulps of the function value;
-      the inputs (rgb, sigma, z, upstream gradients) are exact: both sides read the same fp32 numbers.
-    Applied in the kernel's order:
-      delta = fl(z' - z) (exact 1e10 at the last sample); density = relu (exact) or logf(fl(1 + expf(fl(sigma - 1))));
-      x = fl(delta density); e = expf(-x); alpha = fl(1 - e);  f = fl(fl(1 - alpha) + 1e-10).
-        The roundings of alpha and f ARE the absorption of e < 2^-24 and of 1e-10: up to u ABSOLUTE each, however small f
-        itself is (delta sigma ~ 20: f^ = 1e-10, f = 2.2e-9).  Everything below therefore carries absolute errors.
-      T_k = fl(prod_{j<k} f_j), the product held in fp64: product rule per factor, one fp32 rounding at the end;
-      w = fl(alpha T);  gw = the fp32 sum, term by term, of the three rounded products, the white term, g_depth z, g_opacity,
-        g_weights (3 to 6 terms, one rounding per addition);
-      dL/dalpha = fl32(gw T - S / f), S = sum_{i>k} gw_i w_i in fp64.  S and f are NOT treated as independent: every w_i of the
-        suffix holds f_k as a factor of its T_i, so S / f_k = sum_{i>k} gw_i alpha_i Q_ki (1 + d)(1 + d'), Q_ki = prod_{j<i,
-        j != k} f_j, |d|, |d'| <= u (the roundings of T_i and w_i) -- the same f^_k cancels exactly.  Q's error follows the
-        product rule over its own factors.  What does NOT cancel is the fp64 rounding of the kernel's S = total - prefix
-        (absolute, (N + 16) 2^-53 sum |gw w|), which is divided by f^_k >= max(f_k - E_f, 1e-10 (1 - 2u)).
-      d sigma = fl(fl(dL/dalpha delta) e) [x the mask: exact under relu; under softplus fl(1 / fl(1 + expf(fl(1 - sigma)))), one
-        more expf, and a correctly rounded division];
-      d rgb_pre = fl(g_comp w) through the head: fl(fl(g y) fl(1 - y)), or with powf(y, 2.2f) (its exponent is 2.2 (1 + d):
-        relative 2.2 u |ln y| more) and the constant 1 / 2.2f (relative 2 u).
-    bias_part: the sum of its points' bounds plus N fp32 additions of values bounded by |ref| + bound.
-    Nothing measured on a device enters."""
-    R, N, rgb, sigma, z, g_comp = _rays(rgb4, sigma, z, g_comp)
-    g_depth, g_opacity, g_weights = _opt(g_depth, (R,)), _opt(g_opacity, (R,)), _opt(g_weights, (R, N))
+def forward_bounds(sigma, z, flags):
+    """The forward part of error_bounds on its own (sigma, z: (R, N), the fp32 inputs as given): every intermediate of the
+    compositing forward as (fp64 value, bound on a correct fp32 implementation's distance from it), by the rules error_bounds
+    states, in the kernels' order (csrc/nsr_composite.h states the same chain as csrc/nsr_train.hip):
+      delta, E_delta; x = delta density, Ex; e = exp(-x), Ee; alpha, Ea; f, Ef, f_lo; T, ET; w = alpha T, Ew.
+    Shared by error_bounds below and by the forward compositor's unit tests (tests/ray_stages_ref.py)."""
+    sigma, z = np.asarray(sigma, dtype=np.float64), np.asarray(z, dtype=np.float64)
+    R, N = sigma.shape
     soft = bool(flags & SOFTPLUS)
     zero = np.zeros((R, N))
     delta = np.empty((R, N))
@@ -196,6 +173,45 @@ def error_bounds(rgb4, sigma, z, g_comp, flags, g_depth=None, g_opacity=None, g_
     T, ET = Td, _rnd(Td, E_Td)
     ET[:, 0] = 0.0
     w, Ew = _mul(alpha, Ea, T, ET)
+    return dict(delta=delta, E_delta=E_delta, dens=dens, E_dens=E_dens, x=x, Ex=Ex, e=e, Ee=Ee, alpha=alpha, Ea=Ea, f=f, Ef=Ef,
+                f_lo=f_lo, T=T, ET=ET, w=w, Ew=Ew)
+
+
+def error_bounds(rgb4, sigma, z, g_comp, flags, g_depth=None, g_opacity=None, g_weights=None):
+    """Elementwise bounds (P, 4) on |d4 of composite_bwd_kernel - ref_composite_bwd|, and (R, 4) on bias_part.  Derived, not
+    fitted: a running error analysis of the arithmetic csrc/nsr_train.hip states, carried out on the reference's own values.
+
+    Every intermediate carries (value v, bound E >= |v^ - v|) where v^ is what a correct fp32 implementation holds.  Rules,
+    u = 2^-24:
+      one fp32 operation on operands known to Ea, Eb: the exact operation's propagated error (product: |a| Eb + |b| Ea + Ea Eb;
+        sum: Ea + Eb) and then one rounding, u (|v| + E) (+ 2^-149 should it underflow);
+      expf / logf / powf: the argument's error through the function, plus TRANSCENDENTAL_ULPS ulps of the function value;
+      the inputs (rgb, sigma, z, upstream gradients) are exact: both sides read the same fp32 numbers.
+    Applied in the kernel's order:
+      delta = fl(z' - z) (exact 1e10 at the last sample); density = relu (exact) or logf(fl(1 + expf(fl(sigma - 1))));
+      x = fl(delta density); e = expf(-x); alpha = fl(1 - e);  f = fl(fl(1 - alpha) + 1e-10).
+        The roundings of alpha and f ARE the absorption of e < 2^-24 and of 1e-10: up to u ABSOLUTE each, however small f
+        itself is (delta sigma ~ 20: f^ = 1e-10, f = 2.2e-9).  Everything below therefore carries absolute errors.
+      T_k = fl(prod_{j<k} f_j), the product held in fp64: product rule per factor, one fp32 rounding at the end;
+      w = fl(alpha T);  gw = the fp32 sum, term by term, of the three rounded products, the white term, g_depth z, g_opacity,
+        g_weights (3 to 6 terms, one rounding per addition);
+      dL/dalpha = fl32(gw T - S / f), S = sum_{i>k} gw_i w_i in fp64.  S and f are NOT treated as independent: every w_i of the
+        suffix holds f_k as a factor of its T_i, so S / f_k = sum_{i>k} gw_i alpha_i Q_ki (1 + d)(1 + d'), Q_ki = prod_{j<i,
+        j != k} f_j, |d|, |d'| <= u (the roundings of T_i and w_i) -- the same f^_k cancels exactly.  Q's error follows the
+        product rule over its own factors.  What does NOT cancel is the fp64 rounding of the kernel's S = total - prefix
+        (absolute, (N + 16) 2^-53 sum |gw w|), which is divided by f^_k >= max(f_k - E_f, 1e-10 (1 - 2u)).
+      d sigma = fl(fl(dL/dalpha delta) e) [x the mask: exact under relu; under softplus fl(1 / fl(1 + expf(fl(1 - sigma)))), one
+        more expf, and a correctly rounded division];
+      d rgb_pre = fl(g_comp w) through the head: fl(fl(g y) fl(1 - y)), or with powf(y, 2.2f) (its exponent is 2.2 (1 + d):
+        relative 2.2 u |ln y| more) and the constant 1 / 2.2f (relative 2 u).
+    bias_part: the sum of its points' bounds plus N fp32 additions of values bounded by |ref| + bound.
+    Nothing measured on a device enters."""
+    R, N, rgb, sigma, z, g_comp = _rays(rgb4, sigma, z, g_comp)
+    g_depth, g_opacity, g_weights = _opt(g_depth, (R,)), _opt(g_opacity, (R,)), _opt(g_weights, (R, N))
+    soft = bool(flags & SOFTPLUS)
+    fw = forward_bounds(sigma, z, flags)
+    delta, E_delta, e, Ee, alpha, Ea, f, Ef, f_lo = (fw[k] for k in ("delta", "E_delta", "e", "Ee", "alpha", "Ea", "f", "Ef", "f_lo"))
+    T, ET, w, Ew = fw["T"], fw["ET"], fw["w"], fw["Ew"]
     # gw
     gw, Egw = _mul(g_comp[:, None, 0], 0.0, rgb[:, :, 0], 0.0)
     for c in (1, 2):
