@@ -161,6 +161,11 @@ if os.path.exists(_REFINE_TRAIN_HOOKS_SRC):
 _REFINE_MIXED_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_mixed.hip")
 if os.path.exists(_REFINE_MIXED_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_REFINE_MIXED_HOOKS_SRC)
+# ... and nsr_sincos per element, the run-time-degree encoder's launcher and the TRAIN forward with its encoding panels
+# (tests/test_gpu_encoding.py); same condition
+_ENCODE_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_encode.hip")
+if os.path.exists(_ENCODE_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_ENCODE_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -382,26 +382,26 @@ int nsr::prepare_weights(hipStream_t st, const Shape& S, const float* const* w, 
   return NSR_OK;
 }
 
+// one encoded row per sample point, columns [0, 4 n_groups), into each of the n_dst destinations (row stride ld floats)
+int nsr::encode_arch(hipStream_t st, const float* rays, int ray_stride, const float* z, int64_t P, int N, int deg, int view_dir,
+                     float* const* dst_rows, int n_dst, int64_t ld, int n_groups) {
+  EncodeDst dst{};
+  for (int j = 0; j < n_dst; ++j) dst.p[j] = dst_rows[j];
+  dst.n = n_dst;
+  const int64_t n = P * n_groups;
+  hipLaunchKernelGGL(encode_arch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rays, ray_stride, z, P, N, deg,
+                     view_dir, dst, ld, n_groups);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
 // E1 + cast_rays of the P = rays x N sample points, then the network with everything kept for the backward pass
 int nsr::net_forward(hipStream_t st, const Shape& S, const float* rays, int ray_stride, const float* z, int N, const float* const* w,
                 const Pack& q, const Kept& s, int64_t P, bool split, int color_none) {
-  {
-    EncodeDst dst{};
-    for (int j = 0; j < S.n_x; ++j) dst.p[j] = s.x[j];
-    dst.n = S.n_x;
-    const int64_t n = P * (S.Kx / 4);
-    hipLaunchKernelGGL(encode_arch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rays, ray_stride, z, P, N,
-                       S.arch.deg_pos, 0, dst, (int64_t)S.ldx, S.Kx / 4);
-    NSR_CHECK_LAUNCH();
-  }
+  NSR_TRY(encode_arch(st, rays, ray_stride, z, P, N, S.arch.deg_pos, 0, s.x, S.n_x, (int64_t)S.ldx, S.Kx / 4));
   if (!S.no_dir) {
-    const int64_t n = P * (S.Dp / 4);
-    EncodeDst dst{};
-    dst.p[0] = s.ci + S.Wp;
-    dst.n = 1;
-    hipLaunchKernelGGL(encode_arch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rays, ray_stride, z, P, N,
-                       S.arch.deg_dir, 1, dst, (int64_t)S.Ci, S.Dp / 4);
-    NSR_CHECK_LAUNCH();
+    float* const dir_rows = s.ci + S.Wp;
+    NSR_TRY(encode_arch(st, rays, ray_stride, z, P, N, S.arch.deg_dir, 1, &dir_rows, 1, (int64_t)S.Ci, S.Dp / 4));
   }
   for (int l = 0; l < S.D; ++l) {
     const Mat x = in_of(S, s, l), y = out_of(S, s, l);

@@ -178,6 +178,11 @@ NSR_INTERNAL Pack carve_pack(Carver& a, const Shape& S, bool split);
 NSR_INTERNAL int check_alignment(const Shape& S, const float* const* w);
 // split: also the (hi, lo) fp16 halves of the forward matrices (NSR_F16X3_GEMM; the pack must have been carved with them)
 NSR_INTERNAL int prepare_weights(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, bool split);
+// the encoder with run-time degree: row p of each of the n_dst (<= kMaxD) destinations, row stride ld floats (a multiple of 4,
+// >= 4 n_groups; rows 16-byte aligned), gets columns [0, 4 n_groups) = [x, sin(2^0 x), cos(2^0 x), ..., 2^(deg - 1) | zeros] with
+// x = the sample point o + z d of ray p / N (view_dir: the ray's encoded view direction; z is then not read)
+NSR_INTERNAL int encode_arch(hipStream_t st, const float* rays, int ray_stride, const float* z, int64_t P, int N, int deg,
+                             int view_dir, float* const* dst_rows, int n_dst, int64_t ld, int n_groups);
 // E1 + cast_rays of the P = rays x N sample points, then the network with everything kept for the backward pass; the raw
 // density goes to column 3 of s.rgb.  split: the forward products on the pack's split-fp16 halves
 NSR_INTERNAL int net_forward(hipStream_t st, const Shape& S, const float* rays, int ray_stride, const float* z, int N,

@@ -108,6 +108,11 @@ SIGNATURES = {
     "nsr_test_refine_fwd_reduce": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_int64, c_void_p, c_int64,
                                            c_void_p]),
     "nsr_test_refine_nhwc3_to_nchw": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    # tests/csrc/nsr_test_hooks_encode.hip (the last argument of each is the stream)
+    "nsr_test_sincos": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "nsr_test_encode_arch": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, POINTER(c_void_p), c_int, c_int64, c_int,
+                                     c_void_p]),
+    "nsr_test_f16x3_train_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int] + [c_void_p] * 5),
 }
 
 # nsr::GemmF16Route (csrc/nsr_gemm.h): the instantiation gemm_f16x3 launches

@@ -8,7 +8,7 @@ from rounding.
 
 Ray-level entry points: the in-kernel encoding is exact only on the three un-encoded coordinates of each block (and, at the
 origin, on all of them: sin 0 = 0, cos 0 = 1 exactly), so the ray cases carry zero weights on every sin / cos column; those
-columns of these kernels stay covered by the tolerance tests."""
+columns are tested bit for bit in tests/test_gpu_encoding.py, against a numpy restatement of nsr_sincos."""
 from types import SimpleNamespace
 
 import numpy as np
