@@ -36,14 +36,16 @@ def main():
     ap.add_argument("--aug-num", type=int, default=200)
     ap.add_argument("--with-gt-patch", action="store_true")
     ap.add_argument("--precision", default="fp32", choices=("fp32", "f16x3_mixed"),
-                    help="f16x3_mixed: forward and input gradients on the split-fp16 MFMA, weight gradients fp32")
+                    help="f16x3_mixed: forward and input gradients on the split-fp16 MFMA")
+    ap.add_argument("--weight-grad", default="fp32", choices=("fp32", "f16x3"),
+                    help="f16x3: the weight gradients as one implicit split-fp16 GEMM per layer (fp32: im2col + fp32 GEMM)")
     a = ap.parse_args()
     gt, sr = synthetic_pair(*a.wh)
     ps = RefinePatchSet(gt, sr, patch_len=64, num_ref_patches=8, ref_offset=64, with_gt_patch=a.with_gt_patch, aug_num=a.aug_num,
                         generator=torch.Generator().manual_seed(0))
     print(f"patch set: {ps.aug_num} augmentations of {a.wh[0]} x {a.wh[1]}, {ps.resident_bytes() / 1e6:.2f} MB resident "
           f"(the reference's fp32 stacks: {2 * ps.aug_num * 3 * a.wh[0] * a.wh[1] * 4 / 1e6:.0f} MB)")
-    tr = refine.RefineTrainer(refine.make_refine_state_dict(7), lr=5e-4, precision=a.precision)
+    tr = refine.RefineTrainer(refine.make_refine_state_dict(7), lr=5e-4, precision=a.precision, weight_grad=a.weight_grad)
     gen = torch.Generator(device="cuda").manual_seed(1)
     t0, it = time.time(), 0
     for batch in ps.epoch(a.batch, a.iters * a.batch, gen):

@@ -27,7 +27,9 @@ def main():
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--precision", default="fp32", choices=("fp32", "f16x3_mixed"),
-                    help="f16x3_mixed: forward and input gradients on the split-fp16 MFMA, weight gradients fp32")
+                    help="f16x3_mixed: forward and input gradients on the split-fp16 MFMA")
+    ap.add_argument("--weight-grad", default="fp32", choices=("fp32", "f16x3"),
+                    help="f16x3: the weight gradients as one implicit split-fp16 GEMM per layer (fp32: im2col + fp32 GEMM)")
     ap.add_argument("--ssim", type=float, default=None, metavar="LAMBDA", help="add LAMBDA * (1 - SSIM) to the loss")
     ap.add_argument("--grad-loss", type=float, default=None, metavar="LAMBDA", help="add LAMBDA * GradientLoss(pred, gt) to the loss")
     a = ap.parse_args()
@@ -38,8 +40,8 @@ def main():
     sr = (F.avg_pool2d(F.pad(gt, (2, 2, 2, 2), mode="reflect"), 5, 1) + 0.05 * torch.randn(B, 3, P, P, generator=gen)).clamp(-1, 1)
     offs = torch.randint(0, 17, (R, 2), generator=gen)
     refs = torch.stack([big[:, :, int(oy):int(oy) + P, int(ox):int(ox) + P] for oy, ox in offs], 1).contiguous()
-    tr = refine.RefineTrainer(refine.make_refine_state_dict(7), lr=5e-4, precision=a.precision, refine_with_ssim=a.ssim is not None,
-                              lambda_refine_ssim=1.0 if a.ssim is None else a.ssim)
+    tr = refine.RefineTrainer(refine.make_refine_state_dict(7), lr=5e-4, precision=a.precision, weight_grad=a.weight_grad,
+                              refine_with_ssim=a.ssim is not None, lambda_refine_ssim=1.0 if a.ssim is None else a.ssim)
     tr.set_input({"sr_patch": sr, "ref_patches": refs, "gt_patch": gt})
     t0 = time.time()
     grad_loss = losses.GradientLoss()

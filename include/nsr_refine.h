@@ -107,6 +107,19 @@ int nsr_refine_train_forward_p(int precision, const float* const* tensors, float
                                void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream);
 int nsr_refine_train_backward_p(int precision, const float* const* tensors, const float* g_out, float* const* grads,
                                 void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream);
+/* The backward with the route of the WEIGHT gradients as a second, independent argument.  weight_grad = NSR_FP32: im2col + the
+ * fp32-MFMA GEMM, split-K -- nsr_refine_train_backward_p, bit for bit (which is this call with NSR_FP32).  weight_grad =
+ * NSR_F16X3 ("f16x3" in the Python layer): the weight gradient of every layer but E.conv1 (cin 3, K = 27: fp32 as before) is
+ * one implicit GEMM per site on the split-fp16 MFMA -- dZ and the gathered input both split to fp16 (hi, lo) while they are
+ * staged, three terms per product, fp32 accumulation, dZ scaled by a power of two from its tracked range; no col matrix.  The
+ * pixels of a site are cut into slices whose length is a function of the layer's shape alone and whose partial sums are added
+ * in slice order: no float atomics, identical calls give identical bits, and these weight gradients do not depend on
+ * img_chunk.  A power of two applied to g_out comes out of every gradient exactly.  Every other output (gamma, beta, biases,
+ * E.conv1's weight, the input gradients the backward passes on) is what `precision` alone makes it.  Any other weight_grad is
+ * NSR_ERR_UNSUPPORTED, returned before anything else -- `precision` included -- is looked at; everything else is validated as in
+ * nsr_refine_train_backward_p.  The workspace and saved-state sizes do not depend on it. */
+int nsr_refine_train_backward_w(int precision, int weight_grad, const float* const* tensors, const float* g_out, float* const* grads,
+                                void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream);
 
 /* ---- patch tiler / stitcher around the network (the 'test' path of data/llff_refine_dataset.py:303-340 and
  * models/refine_model.py:205-216): an SR image is cut into `patch` x `patch` tiles on a grid (x outer, y inner, starts

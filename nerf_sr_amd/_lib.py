@@ -175,6 +175,8 @@ SIGNATURES = {
                                            c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "nsr_refine_train_backward_p": (c_int, [c_int, POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p,
                                             c_size_t, c_void_p]),
+    "nsr_refine_train_backward_w": (c_int, [c_int, c_int, POINTER(c_void_p), c_void_p, POINTER(c_void_p), c_void_p, c_size_t, c_void_p,
+                                            c_size_t, c_void_p]),
     "nsr_refine_tile": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "nsr_refine_gather": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                   c_void_p, c_void_p]),

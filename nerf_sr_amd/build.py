@@ -37,6 +37,7 @@ UNITS = [
     ("nsr_refine.hip", ["-ffp-contract=off"]),
     ("nsr_refine_train.hip", ["-ffp-contract=off"]),
     ("nsr_refine_dgrad_f16.hip", ["-ffp-contract=off"]),
+    ("nsr_refine_wgrad_f16.hip", ["-ffp-contract=off"]),
     ("nsr_image.hip", ["-ffp-contract=off"]),
     ("nsr_metrics.hip", ["-ffp-contract=off"]),
     ("nsr_losses.hip", ["-ffp-contract=off"]),
@@ -161,6 +162,10 @@ if os.path.exists(_REFINE_TRAIN_HOOKS_SRC):
 _REFINE_MIXED_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_mixed.hip")
 if os.path.exists(_REFINE_MIXED_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_REFINE_MIXED_HOOKS_SRC)
+# ... and the launcher of its implicit split-fp16 weight gradient (tests/test_gpu_refine_wgrad_units.py); same condition
+_REFINE_WGRAD_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_wgrad.hip")
+if os.path.exists(_REFINE_WGRAD_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_REFINE_WGRAD_HOOKS_SRC)
 # ... and nsr_sincos per element, the run-time-degree encoder's launcher and the TRAIN forward with its encoding panels
 # (tests/test_gpu_encoding.py); same condition
 _ENCODE_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_encode.hip")

@@ -21,6 +21,11 @@
 // upsample at the upsampled extent, then a 2 x 2 fold).  Everything else, the weight gradients included, is as above, and the
 // saved state is the same: a backward of either precision runs on the saved state of a forward of either.
 //
+// weight_grad = NSR_F16X3 (opt-in, independent of the precision; nsr_refine_train_backward_w): the weight gradient of every
+// site but layer 0 is one implicit split-fp16 product over the whole site (nsr_refine_wgrad_f16.hip: no im2col, no chunks,
+// pixel slices that are a function of the shape, added in order); the kernels that write dZ then raise the range word at
+// every such site.  With NSR_FP32 nothing is launched differently.
+//
 // Every reduction has a fixed order (no float atomics): two identical calls give identical bits.  The 17 convolution
 // biases in front of a BatchNorm are cancelled by the mean subtraction: their gradients are DEFINED as exact zeros.
 //
@@ -727,7 +732,7 @@ int site_forward(hipStream_t st, const Site& s, const float* const* t, float* co
 
 // `acc`: this site adds to the parameter gradients (the encoder's second call)
 int site_backward(hipStream_t st, const Site& s, const float* const* t, float* const* grads, const float* g_out, const float* x_nchw,
-                  int chunk, const Work& w, int acc, int prec) {
+                  int chunk, const Work& w, int acc, int prec, int wgrad) {
   const Layer& L = layer(s.l);
   const Geo g = geo(s);
   const int64_t rows = (int64_t)s.n_img * g.rows_img;
@@ -737,7 +742,10 @@ int site_backward(hipStream_t st, const Site& s, const float* const* t, float* c
   // NSR_F16X3: the input gradient of a stride-1 site is an implicit convolution of dZ on the split-fp16 MFMA; the kernel that
   // writes dZ leaves its largest magnitude in the range word.  Stride-2 sites (the accumulating ones) keep dcol + col2im.
   const bool implicit = prec == NSR_F16X3 && s.l != 0 && L.stride == 1;
-  unsigned* const mbits = implicit ? range_word(w) : nullptr;
+  // weight_grad = NSR_F16X3: the weight gradient of every site but layer 0 (K = 27) is one implicit split-fp16 product over
+  // the whole site (nsr_refine_wgrad_f16.hip), scaled by the same range word
+  const bool wg16 = wgrad == NSR_F16X3 && s.l != 0;
+  unsigned* const mbits = (implicit || wg16) ? range_word(w) : nullptr;
   if (implicit && s.gacc) return NSR_ERR_UNSUPPORTED;
   if (mbits && hipMemsetAsync(mbits, 0, sizeof(unsigned), st) != hipSuccess) return NSR_ERR_LAUNCH;
   // ---- dZ and the gradients of the per-channel parameters
@@ -761,25 +769,31 @@ int site_backward(hipStream_t st, const Site& s, const float* const* t, float* c
   }
   // 32 zeroed rows behind dZ: the K padding of the last chunk's weight-gradient product
   if (hipMemsetAsync(w.gz + rows * ldz, 0, (size_t)32 * ldz * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
+  // in front of the re-layout below: the bias it writes behind the widest layer's weight lands on the range word
+  if (wg16)
+    NSR_TRY(refine_wgrad_f16x3(st, w.gz, ldz, C, at(s.src), s.src.ld, L.cin, s.n_img, s.Hs, s.Ws, L.stride, L.up, mbits, w.part,
+                               kPartFloats, acc, grads[p]));
   if (implicit) NSR_TRY(refine_flip_pack(st, t[t_of(s.l)], L.cin, C, g.np, reinterpret_cast<unsigned short*>(w.wr)));
   else if (s.l != 0) NSR_TRY(relayout(st, s, t, w.wr));
   const int Mw = C < 4 ? 4 : C;           // rows of the weight-gradient product (a K-major operand needs >= 4)
-  for (int i0 = 0; i0 < s.n_img; i0 += chunk) {
+  for (int i0 = 0; i0 < s.n_img && !(wg16 && implicit); i0 += chunk) {
     const int nc = s.n_img - i0 < chunk ? s.n_img - i0 : chunk;
     const int64_t M = (int64_t)nc * g.rows_img, Kp = (M + 31) & ~(int64_t)31;
     const float* dz = w.gz + (int64_t)i0 * g.rows_img * ldz;
-    // ---- weight gradient: dW[n][k] = sum over the output pixels p of dZ[p][n] col[p][k]
-    NSR_TRY(im2col(st, s, g, x_nchw, i0, nc, w.col));
-    if (Kp > M && hipMemsetAsync(w.col + M * g.kp, 0, (size_t)(Kp - M) * g.kp * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
-    int64_t splits = Kp / 256, cap = kPartFloats / ((int64_t)Mw * g.kp);
-    splits = splits > cap ? cap : splits;
-    splits = splits > kMaxSplits ? kMaxSplits : (splits < 1 ? 1 : splits);
-    GemmArgs a{};
-    a.A = dz; a.lda = ldz; a.a_kmajor = 1; a.B = w.col; a.ldb = g.kp; a.b_kmajor = 1;
-    a.C = w.part; a.ldc = g.kp; a.M = Mw; a.N = g.kp; a.K = Kp; a.n_valid = g.kp; a.act = kActNone;
-    a.splits = (int)splits; a.split_stride = (int64_t)Mw * g.kp;
-    NSR_TRY(gemm(a, st));
-    NSR_TRY(refine_wgrad_reduce(st, w.part, (int)splits, a.split_stride, g.kp, L.cin, C, (acc || i0 > 0) ? 1 : 0, grads[p]));
+    if (!wg16) {
+      // ---- weight gradient: dW[n][k] = sum over the output pixels p of dZ[p][n] col[p][k]
+      NSR_TRY(im2col(st, s, g, x_nchw, i0, nc, w.col));
+      if (Kp > M && hipMemsetAsync(w.col + M * g.kp, 0, (size_t)(Kp - M) * g.kp * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
+      int64_t splits = Kp / 256, cap = kPartFloats / ((int64_t)Mw * g.kp);
+      splits = splits > cap ? cap : splits;
+      splits = splits > kMaxSplits ? kMaxSplits : (splits < 1 ? 1 : splits);
+      GemmArgs a{};
+      a.A = dz; a.lda = ldz; a.a_kmajor = 1; a.B = w.col; a.ldb = g.kp; a.b_kmajor = 1;
+      a.C = w.part; a.ldc = g.kp; a.M = Mw; a.N = g.kp; a.K = Kp; a.n_valid = g.kp; a.act = kActNone;
+      a.splits = (int)splits; a.split_stride = (int64_t)Mw * g.kp;
+      NSR_TRY(gemm(a, st));
+      NSR_TRY(refine_wgrad_reduce(st, w.part, (int)splits, a.split_stride, g.kp, L.cin, C, (acc || i0 > 0) ? 1 : 0, grads[p]));
+    }
     if (s.l == 0 || implicit) continue;   // no gradient with respect to the input images; implicit: below, whole site
     // ---- input gradient: dcol = dZ W, then every input pixel gathers its taps
     GemmArgs d{};
@@ -877,9 +891,10 @@ extern "C" int nsr_refine_train_forward(const float* const* tensors, float* cons
                                     workspace_bytes, saved, saved_bytes, stream);
 }
 
-extern "C" int nsr_refine_train_backward_p(int precision, const float* const* tensors, const float* g_out, float* const* grads,
-                                           void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes,
-                                           void* stream) {
+extern "C" int nsr_refine_train_backward_w(int precision, int weight_grad, const float* const* tensors, const float* g_out,
+                                           float* const* grads, void* workspace, size_t workspace_bytes, const void* saved,
+                                           size_t saved_bytes, void* stream) {
+  if (weight_grad != NSR_FP32 && weight_grad != NSR_F16X3) return NSR_ERR_UNSUPPORTED;
   if (precision != NSR_FP32 && precision != NSR_F16X3) return NSR_ERR_UNSUPPORTED;
   if (!tensors || !g_out || !grads || !workspace || !saved) return NSR_ERR_INVALID_ARG;
   if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0 || (reinterpret_cast<uintptr_t>(saved) & 255) != 0) return NSR_ERR_INVALID_ARG;
@@ -908,15 +923,22 @@ extern "C" int nsr_refine_train_backward_p(int precision, const float* const* te
   build_sites(s, B, R, H, W, k, w);
   // decoder, then the encoder's call on the synthesised patches (its features' gradients sit in the gradients of the
   // concatenated buffers), then the call on the references (gradients routed to the winners) ADDING to the same gradients
-  for (int i = kNSites - 1; i >= 14; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, g_out, nullptr, chunk, w, 0, precision));
-  for (int i = 6; i >= 0; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[0], chunk, w, 0, precision));
+  for (int i = kNSites - 1; i >= 14; --i)
+    NSR_TRY(site_backward(st, s[i], tensors, grads, g_out, nullptr, chunk, w, 0, precision, weight_grad));
+  for (int i = 6; i >= 0; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[0], chunk, w, 0, precision, weight_grad));
   const int64_t px0 = (int64_t)H * W;
   const int64_t px[4] = {px0, px0 / 4, px0 / 16, px0 / 64};
   const int fcw[4] = {128, 256, 512, 512};
   const Act gmx[4] = {{w.gcat7, 384, 256}, {w.gcat5, 768, 512}, {w.gcat3, 1536, 1024}, {w.gcat1, 1024, 512}};
   for (int i = 0; i < 4; ++i) NSR_TRY(refine_route(st, at(gmx[i]), gmx[i].ld, k.win[i], fcw[i], R, px[i], B, w.gfc[i]));
-  for (int i = 13; i >= 7; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[1], chunk, w, 1, precision));
+  for (int i = 13; i >= 7; --i) NSR_TRY(site_backward(st, s[i], tensors, grads, nullptr, k.x[1], chunk, w, 1, precision, weight_grad));
   return NSR_OK;
+}
+
+extern "C" int nsr_refine_train_backward_p(int precision, const float* const* tensors, const float* g_out, float* const* grads,
+                                           void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes,
+                                           void* stream) {
+  return nsr_refine_train_backward_w(precision, NSR_FP32, tensors, g_out, grads, workspace, workspace_bytes, saved, saved_bytes, stream);
 }
 
 extern "C" int nsr_refine_train_backward(const float* const* tensors, const float* g_out, float* const* grads, void* workspace,

@@ -91,6 +91,18 @@ NSR_INTERNAL int refine_dgrad_f16x3(hipStream_t st, const float* dz, int np, con
 // the nearest x2 upsample backwards: dst[(img, sy, sx)][c] (row stride ld) = the 2 x 2 block of src (n_img, 2 Hs, 2 Ws, C dense)
 // summed in a fixed order; C % 4 == 0
 NSR_INTERNAL int refine_fold2x2(hipStream_t st, const float* src, int C, int n_img, int Hs, int Ws, float* dst, int64_t ld);
+// ---- weight_grad = NSR_F16X3 (nsr_refine_wgrad_f16.hip): the weight gradient on the split-fp16 MFMA without the col matrix
+// Pixels per slice of a site's weight-gradient product: a function of the shape alone (cin, cout, K = output pixels of the call)
+NSR_INTERNAL int64_t refine_wgrad_slice_len(int cin, int cout, int64_t K);
+// g[n][c][ky][kx] (cout, cin, 3, 3) = or += (`acc`) sum over the output pixels of dz[(img, y, x)][n] (rows x np, dense)
+// src[(img, s y + ky - 1, s x + kx - 1)][c] -- src NHWC (n_img, Hs, Ws) with row stride ld, read through the nearest x2
+// upsample if `up`, zero padding.  *max_bits = float bits of max |dz| (the range word above).  Partials of the slices go to
+// `part` (part_floats floats; as many slices per pass as fit) and are added in slice order by refine_wgrad_reduce.
+// slice_len: 0 = refine_wgrad_slice_len (the product path), otherwise a multiple of 32 (the unit tests: small cases that span
+// several slices).  cin % 128 == 0, np % 32 == 0, cout <= np, stride 1 or 2: NSR_ERR_UNSUPPORTED otherwise.
+NSR_INTERNAL int refine_wgrad_f16x3(hipStream_t st, const float* dz, int np, int cout, const float* src, int64_t ld, int cin, int n_img,
+                                    int Hs, int Ws, int stride, int up, const unsigned* max_bits, float* part, int64_t part_floats,
+                                    int acc, float* g, int64_t slice_len = 0);
 // (B px_per_img, 3) NHWC -> (B, 3, px_per_img)
 NSR_INTERNAL int refine_nhwc3_to_nchw(hipStream_t st, const float* src, int64_t px_per_img, int B, float* dst);
 

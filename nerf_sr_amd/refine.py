@@ -269,7 +269,8 @@ def _ptr_array(tensors):
 
 
 # training precisions: name -> the `precision` of nsr_refine_train_forward_p / _backward_p.  "f16x3_mixed": forward and input
-# gradients split-fp16, weight gradients fp32; the short name "f16x3" stays free for a pair whose weight gradient is 16-bit too
+# gradients split-fp16; the route of the weight gradients is an option of its own (WEIGHT_GRADS below), so the short name "f16x3"
+# is no precision here and keeps raising
 TRAIN_PRECISIONS = {"fp32": _lib.NSR_FP32, "f16x3_mixed": _lib.NSR_F16X3}
 
 
@@ -280,11 +281,24 @@ def _train_precision(precision, who: str) -> int:
     return TRAIN_PRECISIONS[precision]
 
 
+# weight-gradient routes: name -> the `weight_grad` of nsr_refine_train_backward_w; independent of `precision`.  "f16x3": every
+# weight gradient but E.conv1's as one implicit split-fp16 GEMM per site (three terms per product), no col matrix
+WEIGHT_GRADS = {"fp32": _lib.NSR_FP32, "f16x3": _lib.NSR_F16X3}
+
+
+def _weight_grad(weight_grad, who: str) -> int:
+    if not isinstance(weight_grad, str) or weight_grad not in WEIGHT_GRADS:
+        raise ValueError(f"{who}: weight_grad must be 'fp32' or 'f16x3' (got {weight_grad!r}): the weight gradients run as im2col + "
+                         "fp32 GEMM, or as one implicit split-fp16 GEMM per layer")
+    return WEIGHT_GRADS[weight_grad]
+
+
 class _TrainRun:
     """The arguments of one forward_train call that are not differentiable tensors."""
 
-    def __init__(self, running, momentum, img_chunk, precision=_lib.NSR_FP32):
+    def __init__(self, running, momentum, img_chunk, precision=_lib.NSR_FP32, weight_grad=_lib.NSR_FP32):
         self.running, self.momentum, self.img_chunk, self.precision = running, momentum, img_chunk, precision
+        self.weight_grad = weight_grad
 
     def tensors106(self, params):
         by_name = dict(zip(TRAIN_PARAM_KEYS, params))
@@ -324,15 +338,15 @@ class _ForwardTrain(torch.autograd.Function):
         grads = [torch.empty_like(p) for p in params]
         ws = _train_workspace(ctx.ws_need, saved.device)
         g_out = g_out.to(torch.float32).contiguous()
-        _lib.check(_lib.load().nsr_refine_train_backward_p(ctx.run.precision, ctx.run.tensors106(params), _p(g_out), _ptr_array(grads),
-                                                           _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
-                   "nsr_refine_train_backward_p")
+        _lib.check(_lib.load().nsr_refine_train_backward_w(ctx.run.precision, ctx.run.weight_grad, ctx.run.tensors106(params), _p(g_out),
+                                                           _ptr_array(grads), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream()),
+                   "nsr_refine_train_backward_w")
         ctx.state = None
         return (None, None, None) + tuple(grads)
 
 
 def forward_train(params, running, x_synth: torch.Tensor, list_x_candi: torch.Tensor, momentum: float = 0.1,
-                  img_chunk: Optional[int] = None, precision: str = "fp32") -> torch.Tensor:
+                  img_chunk: Optional[int] = None, precision: str = "fp32", *, weight_grad: str = "fp32") -> torch.Tensor:
     """``MaxPoolingModel.forward`` in train mode (networks.py:964-990 under ``.train()``): BatchNorm normalises with the batch
     statistics of each call (the encoder's two calls each with their own), fp32.  ``params``: name -> CUDA fp32 leaf for the 72
     ``TRAIN_PARAM_KEYS``; ``running``: name -> tensor for the 34 ``RUNNING_KEYS``, updated IN PLACE (momentum; the encoder's
@@ -341,8 +355,12 @@ def forward_train(params, running, x_synth: torch.Tensor, list_x_candi: torch.Te
     exact-zero gradients (include/nsr_refine.h).  There is no gradient with respect to the images (None).
     ``img_chunk``: images whose im2col matrix is live at once (None: the library picks).
     ``precision``: ``"fp32"``, or ``"f16x3_mixed"`` -- the forward convolutions and the input gradients on the split-fp16 MFMA
-    with implicit gather, BatchNorm and the weight gradients fp32 (include/nsr_refine.h, nsr_refine_train_forward_p)."""
+    with implicit gather, BatchNorm and the weight gradients fp32 (include/nsr_refine.h, nsr_refine_train_forward_p).
+    ``weight_grad`` (independent of ``precision``): ``"fp32"`` -- im2col + fp32 GEMM --, or ``"f16x3"`` -- the weight gradient of
+    every layer but E.conv1 as one implicit split-fp16 GEMM per site, three terms per product, bit-identical from call to call
+    and independent of ``img_chunk`` (include/nsr_refine.h, nsr_refine_train_backward_w)."""
     prec = _train_precision(precision, "forward_train")
+    wgrad = _weight_grad(weight_grad, "forward_train")
     missing = [k for k in TRAIN_PARAM_KEYS if k not in params] + [k for k in RUNNING_KEYS if k not in running]
     if missing:
         raise KeyError(f"forward_train: missing {missing[:3]}{'...' if len(missing) > 3 else ''}")
@@ -354,13 +372,13 @@ def forward_train(params, running, x_synth: torch.Tensor, list_x_candi: torch.Te
         if not isinstance(t, torch.Tensor) or t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous() \
                 or tuple(t.shape) != tuple(REFINE_SPEC[k]):
             raise ValueError(f"forward_train: {k} must be a contiguous float32 tensor of shape {REFINE_SPEC[k]} on {x.device}")
-    run = _TrainRun(rs, float(momentum), 0 if img_chunk is None else int(img_chunk), prec)
+    run = _TrainRun(rs, float(momentum), 0 if img_chunk is None else int(img_chunk), prec, wgrad)
     return _ForwardTrain.apply(run, x, c, *ps)
 
 
 class RefineTrainer:
     """``RefineModel``'s training protocol (models/refine_model.py:84-175) for the ``MaxPoolingModel`` with reference patches,
-    fp32 (or ``precision="f16x3_mixed"``, see ``forward_train``): ``set_input`` -> ``forward`` -> ``calculate_losses`` -> ``backward`` -> ``optimizer_step`` (``optimize_parameters``
+    fp32 (or ``precision="f16x3_mixed"`` and / or ``weight_grad="f16x3"``, see ``forward_train``): ``set_input`` -> ``forward`` -> ``calculate_losses`` -> ``backward`` -> ``optimizer_step`` (``optimize_parameters``
     does the four), Adam(lr, betas=(beta1, 0.999)) over the 72 parameters.  ``sd``: the reference's ``state_dict`` (tensors or
     arrays).  ``refine_with_ssim`` / ``lambda_refine_ssim`` are this build's addition, not the reference's: they add
     ``lambda_refine_ssim * (1 - SSIM(data_range=(-1, 1))(pred, gt_patch))`` -- the score ``evaluate_image`` reports, as a loss --
@@ -371,13 +389,14 @@ class RefineTrainer:
                  lambda_refine_l1: float = 1.0, lambda_refine_mse: float = 10.0, device="cuda", *, refine_with_vgg: bool = False,
                  refine_with_grad: bool = False, refine_as_gan: bool = False, precision: str = "fp32", not_use_ref: bool = False,
                  momentum: float = 0.1, img_chunk: Optional[int] = None, beta2: float = 0.999, eps: float = 1e-8,
-                 refine_with_ssim: bool = False, lambda_refine_ssim: float = 1.0):
+                 refine_with_ssim: bool = False, lambda_refine_ssim: float = 1.0, weight_grad: str = "fp32"):
         # every option is checked before a device is touched
         for name, on in (("refine_with_vgg", refine_with_vgg), ("refine_with_grad", refine_with_grad), ("refine_as_gan", refine_as_gan)):
             if on:
                 raise NotImplementedError(f"RefineTrainer: {name} is not built in; compose that loss in torch over "
                                           "nerf_sr_amd.refine.forward_train, which back-propagates any torch loss")
         _train_precision(precision, "RefineTrainer")
+        _weight_grad(weight_grad, "RefineTrainer")
         if not_use_ref:
             raise NotImplementedError("RefineTrainer: --not_use_ref training is not supported (inference is: MaxPoolingModel(not_use_ref=True))")
         if not (refine_with_l1 or refine_with_mse or refine_with_ssim):
@@ -390,7 +409,7 @@ class RefineTrainer:
         self.refine_with_l1, self.refine_with_mse = bool(refine_with_l1), bool(refine_with_mse)
         self.lambda_refine_l1, self.lambda_refine_mse = float(lambda_refine_l1), float(lambda_refine_mse)
         self.refine_with_ssim, self.lambda_refine_ssim = bool(refine_with_ssim), float(lambda_refine_ssim)
-        self.momentum, self.img_chunk, self.precision = float(momentum), img_chunk, precision
+        self.momentum, self.img_chunk, self.precision, self.weight_grad = float(momentum), img_chunk, precision, weight_grad
         dev = OrderedDict()
         for k, shape in REFINE_SPEC.items():
             v = sd[k]
@@ -412,7 +431,7 @@ class RefineTrainer:
 
     def forward(self):
         self.pred = forward_train(self.params, self.running, self.data_sr_patch, self.data_ref_patches, self.momentum, self.img_chunk,
-                                  self.precision)
+                                  self.precision, weight_grad=self.weight_grad)
         return self.pred
 
     def calculate_losses(self):

@@ -25,6 +25,18 @@ than three times the spread of the parent's repeats, this build's fp32 step with
 
     python scripts/time_refine_train.py --precision f16x3_mixed --baseline-lib ab/libnsr_parent.so \
         --out profiles/refine_train_mixed_timing.json
+
+`--weight-grad f16x3` times the trainer with the implicit split-fp16 weight gradients (RefineTrainer(weight_grad=...)).  With
+`--baseline-lib` the rounds then are
+
+    parent_fp32, parent_<precision>   the baseline library's steps      ours_fp32, ours_<precision>   this build, weight_grad fp32
+    ours_<precision>_wgrad_f16x3      this build with the new route     torch                         the restatement
+
+and the verdicts: the new route faster than the parent's step at the same precision by more than three times the spread of that
+parent step's repeats; this build's fp32 and <precision> steps with weight_grad fp32 not slower than the parent's beyond its spread.
+
+    python scripts/time_refine_train.py --precision f16x3_mixed --weight-grad f16x3 --baseline-lib ab/libnsr_parent.so \
+        --out profiles/refine_train_wgrad_timing.json
 """
 import argparse
 import json
@@ -54,15 +66,17 @@ def main():
     ap.add_argument("--only", default="", help="'ours' or 'torch' (default: both, alternating)")
     ap.add_argument("--out", default="")
     ap.add_argument("--precision", default="fp32", help="'fp32' or 'f16x3_mixed': RefineTrainer(precision=...)")
+    ap.add_argument("--weight-grad", default="fp32", help="'fp32' or 'f16x3': RefineTrainer(weight_grad=...)")
     ap.add_argument("--baseline-lib", default="", help="another build of libnsr.so to time the fp32 step of, in child processes")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)      # one block of one variant: what a child process runs
     a = ap.parse_args()
     if a.baseline_lib and not a.child:
         return ab_rounds(a)
-    if a.child == "parent_fp32":
-        # a library from before the entry points with a precision argument (NSR_LIB_PATH): its fp32 pair under their names
+    if a.child.startswith("parent_"):
+        # a library from before the entry points with a precision / a weight-gradient argument (NSR_LIB_PATH): the pair it has
+        # under their names (the baseline is only ever asked for weight_grad fp32, and for fp32 where it has no precision)
         from nerf_sr_amd import _lib
-        new = [k for k in ("nsr_refine_train_forward_p", "nsr_refine_train_backward_p") if k in _lib.SIGNATURES]
+        new = [k for k in ("nsr_refine_train_forward_p", "nsr_refine_train_backward_p", "nsr_refine_train_backward_w") if k in _lib.SIGNATURES]
         sigs = {k: _lib.SIGNATURES.pop(k) for k in new}
         lib = _lib.load()
         for k, (res, args) in sigs.items():
@@ -70,8 +84,11 @@ def main():
                 fn = getattr(lib, k)
                 fn.restype, fn.argtypes = res, args
             except AttributeError:
-                old = getattr(lib, k[:-2])
-                setattr(lib, k, lambda prec, *rest, _f=old: _f(*rest))
+                if k.endswith("_w"):
+                    setattr(lib, k, lambda prec, wgrad, *rest, _lib=lib: _lib.nsr_refine_train_backward_p(prec, *rest))
+                else:
+                    old = getattr(lib, k[:-2])
+                    setattr(lib, k, lambda prec, *rest, _f=old: _f(*rest))
     dev = torch.device("cuda", 0)
     B, R, P = a.batch, a.refs, a.patch
     gen = torch.Generator().manual_seed(3)
@@ -81,7 +98,7 @@ def main():
     sd = refine.make_refine_state_dict(7)
     variants = {}
     if a.only in ("", "ours"):
-        tr = refine.RefineTrainer(sd, lr=5e-4, device=dev, precision=a.precision)
+        tr = refine.RefineTrainer(sd, lr=5e-4, device=dev, precision=a.precision, weight_grad=a.weight_grad)
         tr.set_input({"sr_patch": x, "ref_patches": c, "gt_patch": gt})
         variants["ours"] = tr.optimize_parameters
     if a.only in ("", "torch"):
@@ -114,7 +131,7 @@ def main():
         print(json.dumps({"ms": runs[a.only][0], "device": torch.cuda.get_device_name(dev),
                           "peak_memory_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2)}))
         return
-    res = {"shape": f"B = {B} patch sets, R = {R} references, {P} x {P}, ours: {a.precision}; forward -> L1 -> backward -> Adam; "
+    res = {"shape": f"B = {B} patch sets, R = {R} references, {P} x {P}, ours: {a.precision}, weight gradients {a.weight_grad}; forward -> L1 -> backward -> Adam; "
                     f"{a.repeats} alternating runs of {a.block} iterations after {a.warmup} warm-up iterations",
            "device": torch.cuda.get_device_name(dev), "conv_gmacs_forward": round(B * refine.refine_macs(P, P, R) / 1e9, 1),
            "peak_memory_gb": round(torch.cuda.max_memory_allocated(dev) / 1e9, 2), "variants": {}}
@@ -137,19 +154,26 @@ def ab_rounds(a):
     if not os.path.exists(base):
         raise SystemExit(f"{base} not found: build the parent commit's library there first")
     mixed = f"ours_{a.precision}"
-    plan = [("parent_fp32", "ours", "fp32", base), ("ours_fp32", "ours", "fp32", "")]
+    wg = a.weight_grad != "fp32"
+    plan = [("parent_fp32", "ours", "fp32", "fp32", base)]
+    if wg and a.precision != "fp32":
+        plan.append((f"parent_{a.precision}", "ours", a.precision, "fp32", base))
+    plan.append(("ours_fp32", "ours", "fp32", "fp32", ""))
     if a.precision != "fp32":
-        plan.append((mixed, "ours", a.precision, ""))
-    plan.append(("torch", "torch", "fp32", ""))
+        plan.append((mixed, "ours", a.precision, "fp32", ""))
+    new = f"{mixed}_wgrad_{a.weight_grad}"
+    if wg:
+        plan.append((new, "ours", a.precision, a.weight_grad, ""))
+    plan.append(("torch", "torch", "fp32", "fp32", ""))
     runs, info = {name: [] for name, *_ in plan}, {}
     for _ in range(a.repeats):
-        for name, only, prec, lib in plan:
+        for name, only, prec, wgrad, lib in plan:
             env = dict(os.environ)
             env.pop("NSR_LIB_PATH", None)
             if lib:
                 env["NSR_LIB_PATH"] = lib
-            cmd = [sys.executable, here, "--child", name, "--only", only, "--precision", prec, "--repeats", "1", "--batch", str(a.batch),
-                   "--refs", str(a.refs), "--patch", str(a.patch), "--block", str(a.block), "--warmup", str(a.warmup)]
+            cmd = [sys.executable, here, "--child", name, "--only", only, "--precision", prec, "--weight-grad", wgrad, "--repeats", "1",
+                   "--batch", str(a.batch), "--refs", str(a.refs), "--patch", str(a.patch), "--block", str(a.block), "--warmup", str(a.warmup)]
             out = subprocess.run(cmd, env=env, check=True, capture_output=True, text=True, timeout=600).stdout
             rec = json.loads(out.strip().splitlines()[-1])
             runs[name].append(rec["ms"])
@@ -172,6 +196,19 @@ def ab_rounds(a):
         res[f"{mixed}_faster_by_more_than_3_spreads"] = bool(med["parent_fp32"] - med[mixed] > 3 * spread)
         res[f"{mixed}_over_torch"] = round(med[mixed] / med["torch"], 3)
     res["ours_fp32_over_torch"] = round(med["ours_fp32"] / med["torch"], 3)
+    if wg:
+        # the new route against the parent's step at the SAME precision, in units of that parent step's spread
+        par = f"parent_{a.precision}"
+        pspread = max(runs[par]) - min(runs[par])
+        res[f"{par}_spread_ms"] = round(pspread, 2)
+        res[f"{new}_gain_over_{par}_ms"] = round(med[par] - med[new], 2)
+        res[f"{new}_faster_than_{par}_by_more_than_3_spreads"] = bool(med[par] - med[new] > 3 * pspread)
+        res[f"{new}_over_torch"] = round(med[new] / med["torch"], 3)
+        res["torch_still_ahead"] = bool(med["torch"] < med[new])
+        if a.precision != "fp32":
+            res[f"{mixed}_minus_{par}_ms"] = round(med[mixed] - med[par], 2)
+            res[f"{mixed}_not_slower_than_{par}_beyond_its_spread"] = bool(med[mixed] - med[par] <= pspread)
+        res["ours_fp32_not_slower_than_parent_beyond_its_spread"] = bool(med["ours_fp32"] - med["parent_fp32"] <= spread)
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
