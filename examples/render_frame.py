@@ -39,6 +39,8 @@ def main():
                     help="'density': test-time mode -- the coarse pass only feeds the resampler and computes no colours "
                          "(precision f16x3; the frame is bit-identical)")
     ap.add_argument("--arch", default="", help="'D,W,skips' of a non-default network, skips joined by '+' (e.g. 6,192,1+3)")
+    ap.add_argument("--no-xyz", action="store_true", help="the embedding's --no_xyz: no identity columns (runs the descriptor routes)")
+    ap.add_argument("--no-logscale", action="store_true", help="the embedding's --no_logscale: linear bands (runs the descriptor routes)")
     ap.add_argument("--arch-fused", action="store_true",
                     help="run a non-default --arch in one fused launch per pass, encodings computed in the kernel, instead of "
                          "layer by layer (precision f16x3)")
@@ -52,14 +54,14 @@ def main():
     if a.checkpoint_dir:
         pc, pf = io.checkpoint_paths(a.checkpoint_dir, a.name, a.epoch)
         sd_c, sd_f = io.load_network_state(pc), io.load_network_state(pf)
-    elif arch:
+    elif arch or a.no_xyz or a.no_logscale:
         from nerf_sr_amd.weights import make_state_dict_arch
-        sd_c, sd_f = make_state_dict_arch(99, **arch), make_state_dict_arch(100, **arch)
+        sd_c, sd_f = make_state_dict_arch(99, no_xyz=a.no_xyz, **arch), make_state_dict_arch(100, no_xyz=a.no_xyz, **arch)
     else:
         sd_c, sd_f = make_state_dict(99), make_state_dict(100)
     opt = default_options(img_wh=tuple(a.wh), downscale=a.downscale, white_bkgd=False, precision=a.precision,
                           early_stop=a.early_stop, coarse_rgb=a.coarse == "rgb", arch_fused=a.arch_fused,
-                          arch_fused_rays=not a.arch_fused_rows, **arch)
+                          arch_fused_rays=not a.arch_fused_rows, no_xyz=a.no_xyz, no_logscale=a.no_logscale, **arch)
     model = NeRFDownXModel(opt, device="cuda").load_networks(sd_c, sd_f).eval()
     res = model.render_image(cameras.spiral_pose(a.pose_t), cameras.llff_focal(a.wh[0]), ndc=True)
     torch.cuda.synchronize()

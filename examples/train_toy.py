@@ -24,9 +24,11 @@ def main():
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--batch", type=int, default=512, help="LR pixels per step (x4 sub-rays)")
     ap.add_argument("--arch", default="", help="D,W,skips of a non-default network, skips joined by '+' ('6,192,1+3'; '4,128,' = none)")
+    ap.add_argument("--no-xyz", action="store_true", help="the embedding's --no_xyz (the layer-by-layer pair, on the default network without --arch)")
+    ap.add_argument("--no-logscale", action="store_true", help="the embedding's --no_logscale (likewise)")
     a = ap.parse_args()
     W, H, s = 504, 378, 2
-    if a.arch:
+    if a.arch or a.no_xyz or a.no_logscale:
         return main_arch(a, W, H, s)
     teacher_c = ops.VanillaMLP(precision="f16x3").load_state_dict(make_state_dict(99))
     teacher_f = ops.VanillaMLP(precision="f16x3").load_state_dict(make_state_dict(100))
@@ -51,18 +53,22 @@ def main():
 def main_arch(a, W, H, s):
     """The same loop for ``--arch D,W,skips``: teacher and student are networks of that architecture; the teacher's frames are
     its deterministic train-mode forward, the student trains through ``Trainer(..., arch=)``."""
-    D, Wd, skips = a.arch.split(",")
-    arch = {"D": int(D), "W": int(Wd), "skips": tuple(int(x) for x in skips.split("+") if x)}
-    teacher = [{k: torch.from_numpy(v).cuda() for k, v in make_state_dict_arch(seed, **arch).items()} for seed in (99, 100)]
+    arch = {}            # the embedding options alone: the default network as a descriptor
+    if a.arch:
+        D, Wd, skips = a.arch.split(",")
+        arch = {"D": int(D), "W": int(Wd), "skips": tuple(int(x) for x in skips.split("+") if x)}
+    embed = (1 if a.no_xyz else 0) | (2 if a.no_logscale else 0)      # weights.embed_of of an options object
+    sd = lambda seed: make_state_dict_arch(seed, no_xyz=a.no_xyz, **arch)
+    teacher = [{k: torch.from_numpy(v).cuda() for k, v in sd(seed).items()} for seed in (99, 100)]
     frames = []
     for t in (0.1, 0.5, 0.9):
         rays = ops.subpixel_rays(cameras.spiral_pose(t), (W, H), cameras.llff_focal(W), s, True)
         with torch.no_grad():
             out = train.forward_rays_train(teacher[0], teacher[1], rays.view(-1, 8), None, precision="f16x3_gemm", arch=arch,
-                                           ray_chunk=16384)
+                                           ray_chunk=16384, embed=embed)
         frames.append((rays, out["fine_comp_rgbs"].view(rays.shape[0], s * s, 3).mean(1)))
-    student = train.Trainer(make_state_dict_arch(7, **arch), make_state_dict_arch(8, **arch), randomized=True, noise_std=1.0,
-                            lr=5e-4, ray_chunk=4 * a.batch, precision="f16x3_gemm", arch=arch)
+    student = train.Trainer(sd(7), sd(8), randomized=True, noise_std=1.0,
+                            lr=5e-4, ray_chunk=4 * a.batch, precision="f16x3_gemm", arch=arch, embed=embed)
     t0 = time.time()
     for it in range(a.iters):
         rays, target = frames[it % len(frames)]

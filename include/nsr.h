@@ -167,6 +167,21 @@ int nsr_gen_rays_range(const float* c2w, int H, int W, double focal, int s, int 
  * Replaces PositionalEncoding.__call__ (models/embedding.py:44-62), 3 input
  * channels: x (n,3) -> out (n, 3 + 6*deg) = [x, sin(2^0 x), cos(2^0 x), ...]. */
 int nsr_posenc(const float* x, int64_t n, int deg, float* out, void* stream);
+/* The embedding's two flags (models/embedding.py:17-18) as one option word, carried by every `_e` entry point of this header
+ * and of nsr_train.h; the entry point without the suffix is its `_e` form at embed = 0 (one implementation, the same bits):
+ *   NSR_EMBED_NO_XYZ        --no_xyz: the identity columns are dropped, out is (n, 6 * deg) = [sin(f_0 x), cos(f_0 x), ...]
+ *   NSR_EMBED_LINEAR_FREQS  --no_logscale: the bands f_k are torch.linspace(1, 2^(deg-1), deg) instead of 2^k
+ * Any other bit is NSR_ERR_INVALID_ARG, and so is NO_XYZ on an encoding of degree 0 that a network reads (no columns left:
+ * the reference cannot build that network either).
+ * nsr_posenc_freqs is a HOST function and the only place the bands are computed: freqs (deg floats, 0 <= deg <= 16).  The
+ * linear table is ATen's fp32 linspace, symmetric form: step = (end - 1) / (deg - 1); element i < deg / 2 is 1 + step * i,
+ * the others end - step * (deg - 1 - i) with ONE rounding.  deg = 1 gives [1], deg = 2 gives [1, 2]: the log-scale bands.
+ * The kernels receive the table by value and form the argument as one fp32 multiply f_k * x, like `freq * x` of the
+ * reference; under the log-scale bands that product is the exact ldexpf of nsr_posenc. */
+#define NSR_EMBED_NO_XYZ 1u       /* --no_xyz */
+#define NSR_EMBED_LINEAR_FREQS 2u /* --no_logscale */
+int nsr_posenc_freqs(int deg, unsigned embed, float* freqs);
+int nsr_posenc_e(const float* x, int64_t n, int deg, unsigned embed, float* out, void* stream);
 
 /* ---- S1: stratified sampling -------------------------------------------------
  * Replaces sample_along_rays (models/utils.py:17-44).  rays (R,8).

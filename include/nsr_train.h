@@ -282,6 +282,47 @@ int nsr_arch_fused_forward(const nsr_arch* arch, const void* packed, const float
 int nsr_arch_fused_render_rays(const nsr_arch* arch, const void* packed, const float* rays, int ray_stride, const float* z, int64_t R,
                                int n_samples, int flags, float* out, int64_t ldo, unsigned* status, void* stream);
 
+/* ---- The embedding's options --no_xyz / --no_logscale (models/embedding.py:17-18) on the descriptor routes.  The option word
+ * `embed` (NSR_EMBED_NO_XYZ | NSR_EMBED_LINEAR_FREQS, include/nsr.h: nsr_posenc_e, nsr_posenc_freqs) is an extra argument
+ * behind the descriptor; struct nsr_arch keeps its layout.  Every entry point above that takes a descriptor IS its `_e` form
+ * called with embed = 0: one implementation, the same bits.
+ *   Widths.    Under NSR_EMBED_NO_XYZ in_xyz = 6 deg_pos and in_dir = 6 deg_dir everywhere a size derives from the descriptor:
+ *              the state tensors (layer 0, the skip layers, dir_encoding), the K padding, workspace, saved state and packed
+ *              stream.  nsr_arch_n_tensors does not depend on the word.
+ *   Refusals.  NSR_ERR_INVALID_ARG (sizes: 0) before anything is enqueued: an unknown bit; NO_XYZ with deg_pos == 0; NO_XYZ with
+ *              deg_dir == 0 unless no_dir -- a layer without input columns, which the reference cannot build either.
+ *   Training.  The encoder writes the word's columns, sin / cos (nsr_sincos) of band * x from the table of nsr_posenc_freqs (the
+ *              largest band is 2^(deg-1) under both tables).  The saved header records the word next to the descriptor: a
+ *              backward with another word is NSR_ERR_INVALID_ARG.  Nothing differentiates through the encoding.
+ *   Fused.     nsr_arch_fused_forward_e takes rows of the narrower widths (what nsr_posenc_e writes).  nsr_arch_fused_render_rays_e
+ *              computes them in the kernel by nsr_posenc_e's expression: output and status word are bit-identical to the rows
+ *              entry on nsr_posenc_e's rows under every word.  NSR_FLAG_INPUT_RANGE tests the columns the network sees: under
+ *              NO_XYZ a large raw coordinate is not one of them. */
+#ifndef NSR_EMBED_NO_XYZ
+#define NSR_EMBED_NO_XYZ 1u       /* --no_xyz */
+#define NSR_EMBED_LINEAR_FREQS 2u /* --no_logscale */
+#endif
+int64_t nsr_arch_tensor_numel_e(const nsr_arch* arch, unsigned embed, int t);
+size_t nsr_train_arch_workspace_bytes_e(const nsr_arch* arch, unsigned embed, int precision, int64_t ray_chunk, int n_coarse,
+                                        int n_importance);
+size_t nsr_train_arch_saved_bytes_e(const nsr_arch* arch, unsigned embed, int precision, int64_t R, int n_coarse, int n_importance,
+                                    int64_t ray_chunk);
+int nsr_train_arch_forward_e(const nsr_arch* arch, unsigned embed, const float* const* w_coarse, const float* const* w_fine,
+                             const float* rays, int ray_stride, int64_t R, int n_coarse, int n_importance, int render_flags,
+                             int lindisp, const float* u_coarse, const float* u_fine, const float* noise_coarse,
+                             const float* noise_fine, float noise_std, int precision, int64_t ray_chunk, float* const* outs,
+                             void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream);
+int nsr_train_arch_backward_e(const nsr_arch* arch, unsigned embed, const float* const* w_coarse, const float* const* w_fine,
+                              const float* const* g_outs, float* const* g_coarse, float* const* g_fine, void* workspace,
+                              size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream);
+size_t nsr_arch_fused_packed_bytes_e(const nsr_arch* arch, unsigned embed);
+int nsr_arch_fused_pack_e(const nsr_arch* arch, unsigned embed, const float* const* w, void* packed, unsigned* status, void* stream);
+int nsr_arch_fused_forward_e(const nsr_arch* arch, unsigned embed, const void* packed, const float* x, int64_t ldx, int64_t P,
+                             int flags, float* out, int64_t ldo, unsigned* status, void* stream);
+int nsr_arch_fused_render_rays_e(const nsr_arch* arch, unsigned embed, const void* packed, const float* rays, int ray_stride,
+                                 const float* z, int64_t R, int n_samples, int flags, float* out, int64_t ldo, unsigned* status,
+                                 void* stream);
+
 /* One nn.Linear (+ activation) on the training GEMM, exposed for testing the kernel on its own:
  *   y (P, N) = act(x (P, K) · w (N, K)^T + b),  act: 0 none, 1 relu, 2 sigmoid;  y_t (N, P) optional transpose.
  * K % 32 == 0, ldx % 4 == 0, ldw % 4 == 0, 16-byte aligned pointers (the training step pads its operands). */

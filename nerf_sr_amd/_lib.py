@@ -25,6 +25,7 @@ NSR_ARCH_FUSED_SIGMA_ONLY, NSR_ARCH_FUSED_COLOR_NONE = 1, 2      # include/nsr_t
 NSR_ARCH_FUSED_MAX_D, NSR_ARCH_FUSED_MAX_W, NSR_ARCH_FUSED_MAX_DEG_POS, NSR_ARCH_FUSED_MAX_DEG_DIR = 8, 256, 10, 4
 NSR_OPT_GAMMA, NSR_OPT_COLOR_NONE = 1, 2     # include/nsr.h: colour-head option word (nsr_weights_set_options)
 NSR_WHITE_BKGD, NSR_SIGMA_SOFTPLUS = 1, 2    # include/nsr.h: renderer option word (the `white_bkgd` argument)
+NSR_EMBED_NO_XYZ, NSR_EMBED_LINEAR_FREQS = 1, 2    # include/nsr.h: the embedding's option word (--no_xyz, --no_logscale)
 NSR_LAYOUT_BCHW, NSR_LAYOUT_BHWC = 0, 1      # include/nsr_metrics.h: memory order of nsr_ssim's images
 NSR_LOSS_TV, NSR_LOSS_GRADIENT, NSR_LOSS_LAPLACIAN = 0, 1, 2     # include/nsr_losses.h: `kind` of nsr_loss_workspace_bytes
 NSR_TRAIN_GAMMA_CORRECT, NSR_TRAIN_COLOR_NONE, NSR_TRAIN_STOP_GRAD = 4, 8, 16    # include/nsr_train.h: the training entry points' own bits of that word
@@ -84,6 +85,8 @@ SIGNATURES = {
     "nsr_gen_rays_range": (c_int, [POINTER(c_float), c_int, c_int, c_double, c_int, c_int, c_float, c_float, c_int64, c_int64,
                                    c_void_p, c_void_p]),
     "nsr_posenc": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "nsr_posenc_freqs": (c_int, [c_int, c_uint, POINTER(c_float)]),
+    "nsr_posenc_e": (c_int, [c_void_p, c_int64, c_int, c_uint, c_void_p, c_void_p]),
     "nsr_sample_along_rays": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "nsr_mlp_forward": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "nsr_render_rays": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
@@ -152,6 +155,21 @@ SIGNATURES = {
                                        c_void_p]),
     "nsr_arch_fused_render_rays": (c_int, [POINTER(NsrArch), c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
                                            c_int64, c_void_p, c_void_p]),
+    # the same with the embedding's option word behind the descriptor (--no_xyz / --no_logscale)
+    "nsr_arch_tensor_numel_e": (c_int64, [POINTER(NsrArch), c_uint, c_int]),
+    "nsr_train_arch_workspace_bytes_e": (c_size_t, [POINTER(NsrArch), c_uint, c_int, c_int64, c_int, c_int]),
+    "nsr_train_arch_saved_bytes_e": (c_size_t, [POINTER(NsrArch), c_uint, c_int, c_int64, c_int, c_int, c_int64]),
+    "nsr_train_arch_forward_e": (c_int, [POINTER(NsrArch), c_uint, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int, c_int64, c_int,
+                                         c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int, c_int64,
+                                         POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "nsr_train_arch_backward_e": (c_int, [POINTER(NsrArch), c_uint, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                          POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "nsr_arch_fused_packed_bytes_e": (c_size_t, [POINTER(NsrArch), c_uint]),
+    "nsr_arch_fused_pack_e": (c_int, [POINTER(NsrArch), c_uint, POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
+    "nsr_arch_fused_forward_e": (c_int, [POINTER(NsrArch), c_uint, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64,
+                                         c_void_p, c_void_p]),
+    "nsr_arch_fused_render_rays_e": (c_int, [POINTER(NsrArch), c_uint, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int,
+                                             c_void_p, c_int64, c_void_p, c_void_p]),
     # ---- include/nsr_warp.h
     "nsr_depth_warp": (c_int, [c_void_p, c_int, c_int, c_double, POINTER(c_float), POINTER(c_double), c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p]),

@@ -26,8 +26,11 @@
 // (nsr_arch_fused_render_rays) takes rays (R, 8 | 11) and z (R, n_samples) -- point p is sample p % n_samples of ray
 // p / n_samples, a tile may straddle rays -- forms o + z d and computes, in registers, exactly the encoded columns the lane
 // would have loaded in mode 0, by the expression of the stand-alone encoder (nsr_posenc), so both modes feed the same bits to
-// the same network code.
+// the same network code.  2 is mode 1 under a non-zero embedding option word (include/nsr.h: no identity columns, linear bands
+// from the table in the arguments), by the expression nsr_posenc_e has for that word; the host selects it, so the launch of
+// embed = 0 is the instantiation it always was.  Mode 0 sees the word only as the narrower widths in_xyz / in_dir.
 #include "nsr_f16x3_core.h"
+#include "nsr_embed.h"
 #include "../../include/nsr_train.h"
 
 namespace {
@@ -45,7 +48,7 @@ struct FusedShape {
 };
 constexpr int chunk_pieces(int kb) { return 4 * kb + 1; }
 
-int fused_shape(const nsr_arch* a, FusedShape& S) {
+int fused_shape(const nsr_arch* a, unsigned embed, FusedShape& S) {
   if (!a) return NSR_ERR_INVALID_ARG;
   if (a->D < 1 || a->W < 2 || (a->W & 1) || a->deg_pos < 0 || a->deg_dir < 0 || (a->no_dir != 0 && a->no_dir != 1))
     return NSR_ERR_INVALID_ARG;
@@ -53,7 +56,9 @@ int fused_shape(const nsr_arch* a, FusedShape& S) {
   if (a->D > kFusedMaxD || a->W > kFusedMaxW || a->deg_pos > kFusedMaxDegPos || a->deg_dir > kFusedMaxDegDir)
     return NSR_ERR_UNSUPPORTED;
   S.D = a->D; S.W = a->W; S.H = a->W / 2; S.skips = a->skips; S.no_dir = a->no_dir;
-  S.in_xyz = 3 + 6 * a->deg_pos; S.in_dir = 3 + 6 * a->deg_dir;
+  const int rc = nsr_embed_check_net(embed, a->deg_pos, a->deg_dir, a->no_dir);
+  if (rc != NSR_OK) return rc;
+  S.in_xyz = nsr_embed_cols(a->deg_pos, embed); S.in_dir = nsr_embed_cols(a->deg_dir, embed);
   S.NB = (S.W + 31) / 32; S.HB = (S.H + 31) / 32; S.KXB = (S.in_xyz + 31) / 32;
   return NSR_OK;
 }
@@ -136,6 +141,8 @@ struct FusedArgs {
   const float* rays;      // MODE 1: (R, ray_stride) ray records and (R, n_samples) depths instead of x; P = R * n_samples
   const float* z;
   int ray_stride, n_samples;
+  unsigned embed;         // MODE 2: the embedding's option word and the bands of the two encodings
+  NsrBands bands_pos, bands_dir;
 };
 
 template <int N>
@@ -283,9 +290,26 @@ __device__ __forceinline__ float encoded_column(float v0, float v1, float v2, in
   return r < 3 ? sn : cs;
 }
 
+// MODE 2: the same under the option word `embed` -- nsr_posenc_e's expression.  c0 (the column of lane half 0) is wave-uniform and
+// so are the two bands a pair of halves can need: they are read with uniform indices and selected by h.
+__device__ __forceinline__ float encoded_column_e(float v0, float v1, float v2, int c0, int h, unsigned embed, const NsrBands& bands) {
+  const int first = nsr_embed_first(embed), c = c0 + 4 * h;
+  const int u = c < first ? c : c - first;
+  const int f = u / 6, r = u - 6 * f, comp = r < 3 ? r : r - 3;
+  const float x = comp == 0 ? v0 : (comp == 1 ? v1 : v2);
+  if (c < first) return x;
+  const int u0 = c0 < first ? 0 : c0 - first;
+  const int f0 = min(u0 / 6, kEmbedMaxDeg - 1), f1 = min((u0 + 4) / 6, kEmbedMaxDeg - 1);
+  const float band = h ? bands.f[f1] : bands.f[f0];
+  const float arg = (embed & NSR_EMBED_LINEAR_FREQS) ? __fmul_rn(band, x) : ldexpf(x, f);
+  const float sn = sinf(arg), cs = cosf(arg);
+  return r < 3 ? sn : cs;
+}
+
 // load_block without the row: the same 32 columns of the encoding of v, in the same registers, under the same range test
+template <int MODE>
 __device__ __forceinline__ void encode_block(float v0, float v1, float v2, int kb, int n_cols, int h, u32x4 (&hi)[2], u32x4 (&lo)[2],
-                                             bool& ok) {
+                                             bool& ok, unsigned embed, const NsrBands& bands) {
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -294,8 +318,13 @@ __device__ __forceinline__ void encode_block(float v0, float v1, float v2, int k
       const int c = c0 + 4 * h;
       float f0 = 0.0f, f1 = 0.0f;
       if (c0 < n_cols) {                               // a pair past the encoding in both halves costs nothing
-        f0 = c < n_cols ? encoded_column(v0, v1, v2, c) : 0.0f;
-        f1 = c + 1 < n_cols ? encoded_column(v0, v1, v2, c + 1) : 0.0f;
+        if (MODE == 2) {
+          f0 = c < n_cols ? encoded_column_e(v0, v1, v2, c0, h, embed, bands) : 0.0f;
+          f1 = c + 1 < n_cols ? encoded_column_e(v0, v1, v2, c0 + 1, h, embed, bands) : 0.0f;
+        } else {
+          f0 = c < n_cols ? encoded_column(v0, v1, v2, c) : 0.0f;
+          f1 = c + 1 < n_cols ? encoded_column(v0, v1, v2, c + 1) : 0.0f;
+        }
       }
       ok = ok && fabsf(f0) <= 65504.0f && fabsf(f1) <= 65504.0f;                    // false for NaN
       unsigned a, b;
@@ -343,9 +372,10 @@ __global__ void __launch_bounds__(256) arch_fused_kernel(FusedArgs a) {
                 v2 = __fadd_rn(rq.o[2], __fmul_rn(zk, rq.d[2]));
     bool ok = true;
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) encode_block(v0, v1, v2, kb, a.in_xyz, h, pe.hi[kb], pe.lo[kb], ok);
+    for (int kb = 0; kb < 2; ++kb) encode_block<MODE>(v0, v1, v2, kb, a.in_xyz, h, pe.hi[kb], pe.lo[kb], ok, a.embed, a.bands_pos);
     const bool with_dir = !a.sigma_only && !a.no_dir;
-    encode_block(rq.v[0], rq.v[1], rq.v[2], 0, with_dir ? a.in_dir : 0, h, de.hi[0], de.lo[0], ok);   // the direction that is ENCODED
+    encode_block<MODE>(rq.v[0], rq.v[1], rq.v[2], 0, with_dir ? a.in_dir : 0, h, de.hi[0], de.lo[0], ok, a.embed,
+                       a.bands_dir);   // the direction that is ENCODED
     if (!ok) flags |= NSR_FLAG_INPUT_RANGE;
   }
   ring_advance(ring, chunk_pieces(a.kxb));
@@ -452,15 +482,20 @@ void launch_fused(int NB, const FusedArgs& a, hipStream_t st) {
 
 }  // namespace
 
-extern "C" size_t nsr_arch_fused_packed_bytes(const nsr_arch* arch) {
+extern "C" size_t nsr_arch_fused_packed_bytes(const nsr_arch* arch) { return nsr_arch_fused_packed_bytes_e(arch, 0u); }
+extern "C" size_t nsr_arch_fused_packed_bytes_e(const nsr_arch* arch, unsigned embed) {
   FusedShape S;
-  if (fused_shape(arch, S) != NSR_OK) return 0;
+  if (fused_shape(arch, embed, S) != NSR_OK) return 0;
   return (size_t)fused_total_pieces(S) * 1024u;
 }
 
 extern "C" int nsr_arch_fused_pack(const nsr_arch* arch, const float* const* w, void* packed, unsigned* status, void* stream) {
+  return nsr_arch_fused_pack_e(arch, 0u, w, packed, status, stream);
+}
+extern "C" int nsr_arch_fused_pack_e(const nsr_arch* arch, unsigned embed, const float* const* w, void* packed, unsigned* status,
+                                     void* stream) {
   FusedShape S;
-  const int rc = fused_shape(arch, S);
+  const int rc = fused_shape(arch, embed, S);
   if (rc != NSR_OK) return rc;
   if (!w || !packed || (reinterpret_cast<uintptr_t>(packed) & 15) != 0) return NSR_ERR_INVALID_ARG;
   const int nt = 2 * S.D + 8;
@@ -500,8 +535,12 @@ extern "C" int nsr_arch_fused_pack(const nsr_arch* arch, const float* const* w, 
 
 extern "C" int nsr_arch_fused_forward(const nsr_arch* arch, const void* packed, const float* x, int64_t ldx, int64_t P, int flags,
                                       float* out, int64_t ldo, unsigned* status, void* stream) {
+  return nsr_arch_fused_forward_e(arch, 0u, packed, x, ldx, P, flags, out, ldo, status, stream);
+}
+extern "C" int nsr_arch_fused_forward_e(const nsr_arch* arch, unsigned embed, const void* packed, const float* x, int64_t ldx, int64_t P,
+                                        int flags, float* out, int64_t ldo, unsigned* status, void* stream) {
   FusedShape S;
-  const int rc = fused_shape(arch, S);
+  const int rc = fused_shape(arch, embed, S);
   if (rc != NSR_OK) return rc;
   if ((flags & ~(NSR_ARCH_FUSED_SIGMA_ONLY | NSR_ARCH_FUSED_COLOR_NONE)) != 0) return NSR_ERR_INVALID_ARG;
   const bool sigma_only = (flags & NSR_ARCH_FUSED_SIGMA_ONLY) != 0;
@@ -517,6 +556,7 @@ extern "C" int nsr_arch_fused_forward(const nsr_arch* arch, const void* packed, 
   a.sigma_only = sigma_only ? 1 : 0;
   a.color_none = (flags & NSR_ARCH_FUSED_COLOR_NONE) ? 1 : 0;
   a.rays = nullptr; a.z = nullptr; a.ray_stride = 0; a.n_samples = 0;
+  a.embed = embed; a.bands_pos = NsrBands{}; a.bands_dir = NsrBands{};   // the rows carry the word: only the widths differ
   launch_fused<0>(S.NB, a, nsr_stream(stream));
   NSR_CHECK_LAUNCH();
   return NSR_OK;
@@ -525,8 +565,13 @@ extern "C" int nsr_arch_fused_forward(const nsr_arch* arch, const void* packed, 
 extern "C" int nsr_arch_fused_render_rays(const nsr_arch* arch, const void* packed, const float* rays, int ray_stride, const float* z,
                                           int64_t R, int n_samples, int flags, float* out, int64_t ldo, unsigned* status,
                                           void* stream) {
+  return nsr_arch_fused_render_rays_e(arch, 0u, packed, rays, ray_stride, z, R, n_samples, flags, out, ldo, status, stream);
+}
+extern "C" int nsr_arch_fused_render_rays_e(const nsr_arch* arch, unsigned embed, const void* packed, const float* rays, int ray_stride,
+                                            const float* z, int64_t R, int n_samples, int flags, float* out, int64_t ldo,
+                                            unsigned* status, void* stream) {
   FusedShape S;
-  const int rc = fused_shape(arch, S);
+  const int rc = fused_shape(arch, embed, S);
   if (rc != NSR_OK) return rc;
   if ((flags & ~(NSR_ARCH_FUSED_SIGMA_ONLY | NSR_ARCH_FUSED_COLOR_NONE)) != 0) return NSR_ERR_INVALID_ARG;
   const bool sigma_only = (flags & NSR_ARCH_FUSED_SIGMA_ONLY) != 0;
@@ -543,7 +588,11 @@ extern "C" int nsr_arch_fused_render_rays(const nsr_arch* arch, const void* pack
   a.sigma_only = sigma_only ? 1 : 0;
   a.color_none = (flags & NSR_ARCH_FUSED_COLOR_NONE) ? 1 : 0;
   a.rays = rays; a.z = z; a.ray_stride = ray_stride; a.n_samples = n_samples;
-  launch_fused<1>(S.NB, a, nsr_stream(stream));
+  a.embed = embed;
+  if (nsr_bands(arch->deg_pos, embed, a.bands_pos) != NSR_OK || nsr_bands(arch->deg_dir, embed, a.bands_dir) != NSR_OK)
+    return NSR_ERR_INVALID_ARG;
+  if (embed != 0u) launch_fused<2>(S.NB, a, nsr_stream(stream));   // embed = 0 keeps the instantiation it always had
+  else launch_fused<1>(S.NB, a, nsr_stream(stream));
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }

@@ -6,6 +6,7 @@
 #include <math.h>
 #include "nsr_common.h"
 #include "nsr_raygen.h"
+#include "nsr_embed.h"
 #include "../../include/nsr_data.h"
 
 // ---------------------------------------------------------------------------
@@ -64,34 +65,57 @@ extern "C" int nsr_gen_rays_opt(const float* c2w, int H, int W, double focal, in
 // ---------------------------------------------------------------------------
 // E1  (reference: models/embedding.py:44-62)
 // ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) posenc_kernel(const float* __restrict__ x, int64_t n, int deg,
-                                                     float* __restrict__ out) {
-  const int C = 3 + 6 * deg;
+// the option word's column map (include/nsr.h): the identity columns unless NO_XYZ, then per band sin of the 3-vector, cos of it
+__global__ void __launch_bounds__(256) posenc_kernel(const float* __restrict__ x, int64_t n, int deg, unsigned embed,
+                                                     NsrBands bands, float* __restrict__ out) {
+  const int first = nsr_embed_first(embed);
+  const int C = first + 6 * deg;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n * C) return;
   const int64_t row = idx / C;
   const int col = (int)(idx - row * C);
   float v;
-  if (col < 3) {
+  if (col < first) {
     v = x[row * 3 + col];
   } else {
-    const int f = (col - 3) / 6, c = (col - 3) % 6;
-    const float arg = ldexpf(x[row * 3 + (c % 3)], f);   // 2^f * x, exact
+    const int f = (col - first) / 6, c = (col - first) % 6;
+    const float arg = nsr_band_arg(x[row * 3 + (c % 3)], f, bands, embed);   // log-scale: 2^f * x, exact
     v = (c < 3) ? sinf(arg) : cosf(arg);
   }
   out[idx] = v;
 }
 
-extern "C" int nsr_posenc(const float* x, int64_t n, int deg, float* out, void* stream) {
-  if (n < 0 || deg < 0 || deg > 16) return NSR_ERR_INVALID_ARG;
-  if (n == 0) return NSR_OK;
+extern "C" int nsr_posenc_freqs(int deg, unsigned embed, float* freqs) {
+  if (deg < 0 || deg > kEmbedMaxDeg || (embed & ~kEmbedBits) != 0u || (deg > 0 && !freqs)) return NSR_ERR_INVALID_ARG;
+  if (!(embed & NSR_EMBED_LINEAR_FREQS) || deg == 1) {
+    for (int k = 0; k < deg; ++k) freqs[k] = ldexpf(1.0f, k);
+    return NSR_OK;
+  }
+  // torch.linspace(1, 2^(deg-1), deg), fp32, ATen's symmetric form; the upper half with ONE rounding (nsr_linspace01)
+  const float end = ldexpf(1.0f, deg - 1);
+  const float step = (end - 1.0f) / (float)(deg - 1);
+  for (int i = 0; i < deg; ++i)
+    freqs[i] = (i < deg / 2) ? 1.0f + step * (float)i : fmaf(-step, (float)(deg - 1 - i), end);
+  return NSR_OK;
+}
+
+extern "C" int nsr_posenc_e(const float* x, int64_t n, int deg, unsigned embed, float* out, void* stream) {
+  if (n < 0 || deg < 0 || deg > kEmbedMaxDeg || (embed & ~kEmbedBits) != 0u) return NSR_ERR_INVALID_ARG;
+  const int C = nsr_embed_cols(deg, embed);
+  if (n == 0 || C == 0) return NSR_OK;
   if (!x || !out) return NSR_ERR_INVALID_ARG;
-  const int64_t total = n * (3 + 6 * deg);
+  NsrBands bands;
+  if (nsr_bands(deg, embed, bands) != NSR_OK) return NSR_ERR_INVALID_ARG;
+  const int64_t total = n * C;
   const int threads = 256;
   hipLaunchKernelGGL(posenc_kernel, dim3((unsigned)((total + threads - 1) / threads)), dim3(threads), 0,
-                     nsr_stream(stream), x, n, deg, out);
+                     nsr_stream(stream), x, n, deg, embed, bands, out);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
+}
+
+extern "C" int nsr_posenc(const float* x, int64_t n, int deg, float* out, void* stream) {
+  return nsr_posenc_e(x, n, deg, 0u, out, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -562,6 +562,7 @@ struct SavedHeader {
   int64_t R, chunk;
   int nc, ni, flags, precision;
   nsr_arch arch;            // the network the forward ran (the default descriptor under a chain precision)
+  unsigned embed;           // ... and the embedding's option word it ran with (include/nsr.h)
 };
 static_assert(sizeof(SavedHeader) <= kSavedHeaderFloats * 4 && sizeof(SavedHeader) % 4 == 0, "header");
 struct SavedLayout {
@@ -600,20 +601,20 @@ bool sizes_ok(int64_t ray_chunk, int nc, int ni) { return ray_chunk > 0 && nc >=
 
 // ---- the forward / backward pair: nsr_train_* with the default descriptor and every precision, nsr_train_arch_* with the
 // caller's descriptor and the layer-by-layer precisions only (by_arch) -------------------------------------------------------
-size_t saved_bytes_of(const nsr_arch* arch, bool by_arch, int precision, int64_t R, int nc, int ni, int64_t ray_chunk) {
+size_t saved_bytes_of(const nsr_arch* arch, unsigned embed, bool by_arch, int precision, int64_t R, int nc, int ni, int64_t ray_chunk) {
   Shape S;
-  if (make_shape(arch, S) != NSR_OK) return 0;
+  if (make_shape(arch, S, embed) != NSR_OK) return 0;
   if (R <= 0 || check_shape(R, 1, nc, ni, precision, ray_chunk, by_arch) != NSR_OK) return 0;
   return (size_t)saved_layout(S, precision, R, nc, ni, ray_chunk).total * sizeof(float);
 }
 
-int train_forward(const nsr_arch* arch, bool by_arch, const float* const* w_coarse, const float* const* w_fine, const float* rays,
+int train_forward(const nsr_arch* arch, unsigned embed, bool by_arch, const float* const* w_coarse, const float* const* w_fine, const float* rays,
                   int ray_stride, int64_t R, int n_coarse, int n_importance, int render_flags, int lindisp, const float* u_coarse,
                   const float* u_fine, const float* noise_coarse, const float* noise_fine, float noise_std, int precision,
                   int64_t ray_chunk, float* const* outs, void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes,
                   void* stream) {
   Run c{};
-  NSR_TRY(make_shape(arch, c.net));
+  NSR_TRY(make_shape(arch, c.net, embed));
   c.R = R; c.chunk = ray_chunk; c.nc = n_coarse; c.ni = n_importance; c.flags = render_flags; c.precision = precision;
   c.lindisp = lindisp; c.ray_stride = ray_stride; c.noise_std = noise_std;
   NSR_TRY(check_args({{w_coarse, w_fine, outs}, {w_coarse, w_fine}, outs, {rays, workspace, saved}, {workspace, saved},
@@ -627,7 +628,7 @@ int train_forward(const nsr_arch* arch, bool by_arch, const float* const* w_coar
   float* sv = static_cast<float*>(saved);
   if (c.chain)   // the backward weight streams are packed into the saved state: the backward call uses them as they are
     for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
-  const SavedHeader h{kSavedMagic, (uint64_t)L.total, R, c.chunk, n_coarse, n_importance, render_flags, precision, c.net.arch};
+  const SavedHeader h{kSavedMagic, (uint64_t)L.total, R, c.chunk, n_coarse, n_importance, render_flags, precision, c.net.arch, embed};
   hipLaunchKernelGGL(saved_header_kernel, dim3(1), dim3(64), 0, st, h, reinterpret_cast<unsigned*>(sv));
   NSR_CHECK_LAUNCH();
   NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream));
@@ -642,11 +643,11 @@ int train_forward(const nsr_arch* arch, bool by_arch, const float* const* w_coar
   });
 }
 
-int train_backward(const nsr_arch* arch, bool by_arch, const float* const* w_coarse, const float* const* w_fine,
+int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const float* const* w_coarse, const float* const* w_fine,
                    const float* const* g_outs, float* const* g_coarse, float* const* g_fine, void* workspace, size_t workspace_bytes,
                    const void* saved, size_t saved_bytes, void* stream) {
   Run c{};   // no sampling in this half: lindisp, ray_stride and noise_std stay unused
-  NSR_TRY(make_shape(arch, c.net));
+  NSR_TRY(make_shape(arch, c.net, embed));
   NSR_TRY(check_args({{w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, saved}, {w_coarse, w_fine, g_coarse, g_fine},
                       nullptr, {}, {workspace, saved}, c.net.n_tensors(), by_arch}, nullptr, 1));
   if (saved_bytes < (size_t)kSavedHeaderFloats * sizeof(float)) return NSR_ERR_WORKSPACE;
@@ -657,7 +658,7 @@ int train_backward(const nsr_arch* arch, bool by_arch, const float* const* w_coa
   if (hipStreamSynchronize(st) != hipSuccess) return NSR_ERR_LAUNCH;
   if (h.magic != kSavedMagic) return NSR_ERR_INVALID_ARG;
   if (h.floats > saved_bytes / sizeof(float)) return NSR_ERR_WORKSPACE;   // the header says the state is larger than the buffer
-  if (!same_arch(h.arch, c.net.arch)) return NSR_ERR_INVALID_ARG;         // the forward ran another network
+  if (!same_arch(h.arch, c.net.arch) || h.embed != embed) return NSR_ERR_INVALID_ARG;   // the forward ran another network
   // bounds before anything loops over them (a damaged header may hold anything): every ray and every chunk takes at least
   // 64 floats of the layout, so neither count can exceed what the buffer holds
   if (h.R <= 0 || h.chunk <= 0 || h.chunk > h.R || (uint64_t)h.R > h.floats / 64 ||
@@ -704,8 +705,12 @@ extern "C" size_t nsr_train_workspace_bytes(int64_t ray_chunk, int n_coarse, int
 
 extern "C" size_t nsr_train_arch_workspace_bytes(const nsr_arch* arch, int precision, int64_t ray_chunk, int n_coarse,
                                                  int n_importance) {
+  return nsr_train_arch_workspace_bytes_e(arch, 0u, precision, ray_chunk, n_coarse, n_importance);
+}
+extern "C" size_t nsr_train_arch_workspace_bytes_e(const nsr_arch* arch, unsigned embed, int precision, int64_t ray_chunk,
+                                                   int n_coarse, int n_importance) {
   Shape S;
-  if (make_shape(arch, S) != NSR_OK || !sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) ||
+  if (make_shape(arch, S, embed) != NSR_OK || !sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) ||
       chain_selected(precision))
     return 0;
   return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, split_selected(precision), false, nullptr, nullptr) * sizeof(float);
@@ -717,9 +722,10 @@ extern "C" int nsr_arch_n_tensors(const nsr_arch* arch) {
   return rc != NSR_OK ? rc : S.n_tensors();
 }
 
-extern "C" int64_t nsr_arch_tensor_numel(const nsr_arch* arch, int t) {
+extern "C" int64_t nsr_arch_tensor_numel(const nsr_arch* arch, int t) { return nsr_arch_tensor_numel_e(arch, 0u, t); }
+extern "C" int64_t nsr_arch_tensor_numel_e(const nsr_arch* arch, unsigned embed, int t) {
   Shape S;
-  if (make_shape(arch, S) != NSR_OK) return 0;
+  if (make_shape(arch, S, embed) != NSR_OK) return 0;
   return tensor_numel_of(S, t);
 }
 
@@ -789,11 +795,15 @@ extern "C" int nsr_train_loss_and_grads(const float* const* w_coarse, const floa
 }
 
 extern "C" size_t nsr_train_saved_bytes(int precision, int64_t R, int n_coarse, int n_importance, int64_t ray_chunk) {
-  return saved_bytes_of(&kDefaultArch, false, precision, R, n_coarse, n_importance, ray_chunk);
+  return saved_bytes_of(&kDefaultArch, 0u, false, precision, R, n_coarse, n_importance, ray_chunk);
 }
 extern "C" size_t nsr_train_arch_saved_bytes(const nsr_arch* arch, int precision, int64_t R, int n_coarse, int n_importance,
                                              int64_t ray_chunk) {
-  return saved_bytes_of(arch, true, precision, R, n_coarse, n_importance, ray_chunk);
+  return saved_bytes_of(arch, 0u, true, precision, R, n_coarse, n_importance, ray_chunk);
+}
+extern "C" size_t nsr_train_arch_saved_bytes_e(const nsr_arch* arch, unsigned embed, int precision, int64_t R, int n_coarse,
+                                               int n_importance, int64_t ray_chunk) {
+  return saved_bytes_of(arch, embed, true, precision, R, n_coarse, n_importance, ray_chunk);
 }
 
 extern "C" int nsr_train_forward(const float* const* w_coarse, const float* const* w_fine, const float* rays, int ray_stride,
@@ -801,7 +811,7 @@ extern "C" int nsr_train_forward(const float* const* w_coarse, const float* cons
                                  const float* u_coarse, const float* u_fine, const float* noise_coarse, const float* noise_fine,
                                  float noise_std, int precision, int64_t ray_chunk, float* const* outs, void* workspace,
                                  size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream) {
-  return train_forward(&kDefaultArch, false, w_coarse, w_fine, rays, ray_stride, R, n_coarse, n_importance, render_flags, lindisp,
+  return train_forward(&kDefaultArch, 0u, false, w_coarse, w_fine, rays, ray_stride, R, n_coarse, n_importance, render_flags, lindisp,
                        u_coarse, u_fine, noise_coarse, noise_fine, noise_std, precision, ray_chunk, outs, workspace, workspace_bytes,
                        saved, saved_bytes, stream);
 }
@@ -810,7 +820,16 @@ extern "C" int nsr_train_arch_forward(const nsr_arch* arch, const float* const* 
                                       int lindisp, const float* u_coarse, const float* u_fine, const float* noise_coarse,
                                       const float* noise_fine, float noise_std, int precision, int64_t ray_chunk, float* const* outs,
                                       void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream) {
-  return train_forward(arch, true, w_coarse, w_fine, rays, ray_stride, R, n_coarse, n_importance, render_flags, lindisp, u_coarse,
+  return nsr_train_arch_forward_e(arch, 0u, w_coarse, w_fine, rays, ray_stride, R, n_coarse, n_importance, render_flags, lindisp,
+                                  u_coarse, u_fine, noise_coarse, noise_fine, noise_std, precision, ray_chunk, outs, workspace,
+                                  workspace_bytes, saved, saved_bytes, stream);
+}
+extern "C" int nsr_train_arch_forward_e(const nsr_arch* arch, unsigned embed, const float* const* w_coarse, const float* const* w_fine,
+                                        const float* rays, int ray_stride, int64_t R, int n_coarse, int n_importance, int render_flags,
+                                        int lindisp, const float* u_coarse, const float* u_fine, const float* noise_coarse,
+                                        const float* noise_fine, float noise_std, int precision, int64_t ray_chunk, float* const* outs,
+                                        void* workspace, size_t workspace_bytes, void* saved, size_t saved_bytes, void* stream) {
+  return train_forward(arch, embed, true, w_coarse, w_fine, rays, ray_stride, R, n_coarse, n_importance, render_flags, lindisp, u_coarse,
                        u_fine, noise_coarse, noise_fine, noise_std, precision, ray_chunk, outs, workspace, workspace_bytes, saved,
                        saved_bytes, stream);
 }
@@ -818,13 +837,20 @@ extern "C" int nsr_train_arch_forward(const nsr_arch* arch, const float* const* 
 extern "C" int nsr_train_backward(const float* const* w_coarse, const float* const* w_fine, const float* const* g_outs,
                                   float* const* g_coarse, float* const* g_fine, void* workspace, size_t workspace_bytes,
                                   const void* saved, size_t saved_bytes, void* stream) {
-  return train_backward(&kDefaultArch, false, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved,
+  return train_backward(&kDefaultArch, 0u, false, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved,
                         saved_bytes, stream);
 }
 extern "C" int nsr_train_arch_backward(const nsr_arch* arch, const float* const* w_coarse, const float* const* w_fine,
                                        const float* const* g_outs, float* const* g_coarse, float* const* g_fine, void* workspace,
                                        size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream) {
-  return train_backward(arch, true, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved, saved_bytes,
+  return nsr_train_arch_backward_e(arch, 0u, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved,
+                                   saved_bytes, stream);
+}
+extern "C" int nsr_train_arch_backward_e(const nsr_arch* arch, unsigned embed, const float* const* w_coarse,
+                                         const float* const* w_fine, const float* const* g_outs, float* const* g_coarse,
+                                         float* const* g_fine, void* workspace, size_t workspace_bytes, const void* saved,
+                                         size_t saved_bytes, void* stream) {
+  return train_backward(arch, embed, true, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved, saved_bytes,
                         stream);
 }
 

@@ -45,7 +45,7 @@ struct EncodeDst {
 };
 __global__ void __launch_bounds__(256) encode_arch_kernel(const float* __restrict__ rays, int stride, const float* __restrict__ z,
                                                           int64_t P, int N, int deg, int view_dir, EncodeDst dst, int64_t ld,
-                                                          int n_groups) {
+                                                          int n_groups, unsigned embed, NsrBands bands) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t p = idx / n_groups;
   const int g = (int)(idx % n_groups);
@@ -60,19 +60,19 @@ __global__ void __launch_bounds__(256) encode_arch_kernel(const float* __restric
 #pragma unroll
     for (int c = 0; c < 3; ++c) x[c] = __fadd_rn(q.o[c], __fmul_rn(zk, q.d[c]));   // cast_rays, models/utils.py:5-14
   }
-  const int n_valid = 3 + 6 * deg;
+  const int first = nsr_embed_first(embed), n_valid = first + 6 * deg;
   float out[4];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const int c = 4 * g + e;
     float v = 0.0f;
-    if (c < 3) {
+    if (c < first) {
       v = c == 0 ? x[0] : (c == 1 ? x[1] : x[2]);
     } else if (c < n_valid) {
-      const int f = (c - 3) / 6, r = (c - 3) % 6, comp = r % 3;
+      const int f = (c - first) / 6, r = (c - first) % 6, comp = r % 3;
       const float xc = comp == 0 ? x[0] : (comp == 1 ? x[1] : x[2]);
       float sn, cs;
-      nsr_sincos(ldexpf(xc, f), sn, cs);
+      nsr_sincos(nsr_band_arg(xc, f, bands, embed), sn, cs);
       v = r < 3 ? sn : cs;
     }
     out[e] = v;
@@ -274,7 +274,7 @@ int fwd(hipStream_t st, const Pack& q, bool split, int e, const float* x, int64_
 
 }  // namespace
 
-int nsr::make_shape(const nsr_arch* a, Shape& S) {
+int nsr::make_shape(const nsr_arch* a, Shape& S, unsigned embed) {
   if (!a) return NSR_ERR_INVALID_ARG;
   if (a->D < 1 || a->W < 2 || (a->W & 1) || a->deg_pos < 0 || a->deg_dir < 0 || (a->no_dir != 0 && a->no_dir != 1))
     return NSR_ERR_INVALID_ARG;
@@ -283,7 +283,11 @@ int nsr::make_shape(const nsr_arch* a, Shape& S) {
     return NSR_ERR_UNSUPPORTED;
   S.arch = *a;
   S.D = a->D; S.W = a->W; S.H = a->W / 2; S.skips = a->skips; S.no_dir = a->no_dir;
-  S.in_xyz = 3 + 6 * a->deg_pos; S.in_dir = 3 + 6 * a->deg_dir;
+  NSR_TRY(nsr_embed_check_net(embed, a->deg_pos, a->deg_dir, a->no_dir));
+  S.embed = embed;
+  NSR_TRY(nsr_bands(a->deg_pos, embed, S.bands_pos));
+  NSR_TRY(nsr_bands(a->deg_dir, embed, S.bands_dir));
+  S.in_xyz = nsr_embed_cols(a->deg_pos, embed); S.in_dir = nsr_embed_cols(a->deg_dir, embed);
   S.Kx = r32(S.in_xyz); S.Wp = r32(S.W); S.Hp = r32(S.H); S.Dp = a->no_dir ? 0 : r32(S.in_dir);
   S.Ci = S.Wp + S.Dp; S.Xs = S.Kx + S.Wp;
   int ns = 0;
@@ -384,13 +388,14 @@ int nsr::prepare_weights(hipStream_t st, const Shape& S, const float* const* w, 
 
 // one encoded row per sample point, columns [0, 4 n_groups), into each of the n_dst destinations (row stride ld floats)
 int nsr::encode_arch(hipStream_t st, const float* rays, int ray_stride, const float* z, int64_t P, int N, int deg, int view_dir,
-                     float* const* dst_rows, int n_dst, int64_t ld, int n_groups) {
+                     float* const* dst_rows, int n_dst, int64_t ld, int n_groups, unsigned embed, const NsrBands* bands) {
+  if ((embed & NSR_EMBED_LINEAR_FREQS) && !bands) return NSR_ERR_INVALID_ARG;
   EncodeDst dst{};
   for (int j = 0; j < n_dst; ++j) dst.p[j] = dst_rows[j];
   dst.n = n_dst;
   const int64_t n = P * n_groups;
   hipLaunchKernelGGL(encode_arch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rays, ray_stride, z, P, N, deg,
-                     view_dir, dst, ld, n_groups);
+                     view_dir, dst, ld, n_groups, embed, bands ? *bands : NsrBands{});
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
@@ -398,10 +403,10 @@ int nsr::encode_arch(hipStream_t st, const float* rays, int ray_stride, const fl
 // E1 + cast_rays of the P = rays x N sample points, then the network with everything kept for the backward pass
 int nsr::net_forward(hipStream_t st, const Shape& S, const float* rays, int ray_stride, const float* z, int N, const float* const* w,
                 const Pack& q, const Kept& s, int64_t P, bool split, int color_none) {
-  NSR_TRY(encode_arch(st, rays, ray_stride, z, P, N, S.arch.deg_pos, 0, s.x, S.n_x, (int64_t)S.ldx, S.Kx / 4));
+  NSR_TRY(encode_arch(st, rays, ray_stride, z, P, N, S.arch.deg_pos, 0, s.x, S.n_x, (int64_t)S.ldx, S.Kx / 4, S.embed, &S.bands_pos));
   if (!S.no_dir) {
     float* const dir_rows = s.ci + S.Wp;
-    NSR_TRY(encode_arch(st, rays, ray_stride, z, P, N, S.arch.deg_dir, 1, &dir_rows, 1, (int64_t)S.Ci, S.Dp / 4));
+    NSR_TRY(encode_arch(st, rays, ray_stride, z, P, N, S.arch.deg_dir, 1, &dir_rows, 1, (int64_t)S.Ci, S.Dp / 4, S.embed, &S.bands_dir));
   }
   for (int l = 0; l < S.D; ++l) {
     const Mat x = in_of(S, s, l), y = out_of(S, s, l);

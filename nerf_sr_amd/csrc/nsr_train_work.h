@@ -4,6 +4,7 @@
 #pragma once
 #include <initializer_list>
 #include "nsr_common.h"
+#include "nsr_embed.h"
 #include "../../include/nsr_train.h"
 
 namespace nsr {
@@ -46,7 +47,8 @@ struct Carver {   // hands out consecutive 256-byte granules of `base` (null: on
 // ---- the layer-by-layer network (nsr_train_gemm.hip): everything is a function of the descriptor at run time -----------
 // Layout of a pass over P sample points, r32 = rounded up to 32 (the K tile of the GEMM kernels; padding columns hold zeros
 // and meet zero weight columns):
-//   Kx = r32(3 + 6 deg_pos), Wp = r32(W), Hp = r32(W / 2), Dp = r32(3 + 6 deg_dir) (0 under no_dir)
+//   Kx = r32(in_xyz), Wp = r32(W), Hp = r32(W / 2), Dp = r32(in_dir) (0 under no_dir); in_xyz = 3 + 6 deg_pos, in_dir =
+//   3 + 6 deg_dir, without the 3 under NSR_EMBED_NO_XYZ of the embedding's option word (include/nsr.h)
 //   x[j]  (P, Kx + Wp)   one per skip layer: [pe | h of the layer below]: cat([pe, h]) is the buffer itself; layer 0 reads
 //                        columns 0 .. Kx of x[0].  A network without skips has one (P, Kx) buffer.
 //   h[l]  (P, Wp)        output of trunk layer l, unless layer l + 1 is a skip layer (then it lies in that layer's x)
@@ -60,6 +62,8 @@ struct Shape {
   int x_of[kMaxD];        // the x buffer that is layer l's input (layer 0 and skip layers), else -1
   int64_t part_stride;    // floats of one split-K slice: >= every padded weight-gradient shape
   nsr_arch arch;
+  unsigned embed;          // the embedding's option word, and the bands of the two encodings (nsr_posenc_freqs)
+  NsrBands bands_pos, bands_dir;
   bool skip(int l) const { return l > 0 && ((skips >> l) & 1u); }
   int n_tensors() const { return 2 * D + 8; }
   int kin(int l) const { return l == 0 ? Kx : (skip(l) ? Xs : Wp); }             // padded fan-in of trunk layer l
@@ -170,7 +174,8 @@ struct Need {   // the pointers a driver requires of its caller
 
 // ---- nsr_train_gemm.hip: the layer-by-layer network
 // malformed descriptor -> NSR_ERR_INVALID_ARG, beyond the stated limits -> NSR_ERR_UNSUPPORTED (include/nsr_train.h)
-NSR_INTERNAL int make_shape(const nsr_arch* a, Shape& S);
+// embed: an unknown bit, or NO_XYZ on an encoding of degree 0 that the network reads -> NSR_ERR_INVALID_ARG
+NSR_INTERNAL int make_shape(const nsr_arch* a, Shape& S, unsigned embed = 0u);
 NSR_INTERNAL int64_t tensor_numel_of(const Shape& S, int t);
 NSR_INTERNAL void carve_net_kept(Carver& a, const Shape& S, int64_t P, Kept& q);   // x, h, ci, cc
 NSR_INTERNAL Pack carve_pack(Carver& a, const Shape& S, bool split);
@@ -180,9 +185,11 @@ NSR_INTERNAL int check_alignment(const Shape& S, const float* const* w);
 NSR_INTERNAL int prepare_weights(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, bool split);
 // the encoder with run-time degree: row p of each of the n_dst (<= kMaxD) destinations, row stride ld floats (a multiple of 4,
 // >= 4 n_groups; rows 16-byte aligned), gets columns [0, 4 n_groups) = [x, sin(2^0 x), cos(2^0 x), ..., 2^(deg - 1) | zeros] with
-// x = the sample point o + z d of ray p / N (view_dir: the ray's encoded view direction; z is then not read)
+// x = the sample point o + z d of ray p / N (view_dir: the ray's encoded view direction; z is then not read); embed / bands:
+// the option word's column map and band table (no identity columns under NO_XYZ, sin / cos of bands.f[k] * x under LINEAR_FREQS)
 NSR_INTERNAL int encode_arch(hipStream_t st, const float* rays, int ray_stride, const float* z, int64_t P, int N, int deg,
-                             int view_dir, float* const* dst_rows, int n_dst, int64_t ld, int n_groups);
+                             int view_dir, float* const* dst_rows, int n_dst, int64_t ld, int n_groups, unsigned embed = 0u,
+                             const NsrBands* bands = nullptr);   // bands: read under LINEAR_FREQS only
 // E1 + cast_rays of the P = rays x N sample points, then the network with everything kept for the backward pass; the raw
 // density goes to column 3 of s.rgb.  split: the forward products on the pack's split-fp16 halves
 NSR_INTERNAL int net_forward(hipStream_t st, const Shape& S, const float* rays, int ray_stride, const float* z, int N,

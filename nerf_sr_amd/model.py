@@ -24,6 +24,7 @@ def default_options(**kw) -> SimpleNamespace:
         N_coarse=64, N_importance=64, lindisp=False, white_bkgd=False, randomized=True, noise_std=0.0,
         deg_pos=10, deg_dir=4, dim_pos=3, dim_dir=3, dim_rgb=3, downscale=2, img_wh=(504, 378),
         D=8, W=256, skips=[4],                      # models/networks.py:124-128; other values run layer by layer (ops.GenericMLP)
+        no_xyz=False, no_logscale=False,            # models/embedding.py:17-18: True runs the descriptor routes (ops.GenericMLP)
         no_dir=False, color_activation="sigmoid",   # :128, :160-180 ('none'; True): options of VanillaMLP
         sigma_activation="relu", gamma_correct=False,   # models/rendering.py:69-73 ('softplus'); nerf_downX_model.py:271-276
         ray_chunk=4096, point_chunk=262144, precision="fp32",
@@ -36,7 +37,7 @@ def default_options(**kw) -> SimpleNamespace:
     )
     for k, v in kw.items():
         setattr(opt, k, v)
-    if opt.arch_fused and not ops.is_default_arch(ops.arch_of(opt)):      # refused here, on the host, not at the first launch
+    if opt.arch_fused and not (ops.is_default_arch(ops.arch_of(opt)) and not ops.embed_of(opt)):      # refused here, on the host, not at the first launch
         ops.check_arch_fused(ops.arch_of(opt), opt.precision)
     return opt
 
@@ -61,7 +62,7 @@ class NeRFDownXModel:
         # a GenericMLP pair on the fused descriptor kernel: its network passes can take (rays, z) too (opt.arch_fused_rays)
         self.arch_fused = isinstance(self.netCoarse, GenericMLP) and self.netCoarse.fused and self.netFine.fused
         self.models = {"coarse": self.netCoarse, "fine": self.netFine}
-        self.embeddings = {"pos": PositionalEncoding(3, self.opt.deg_pos), "dir": PositionalEncoding(3, self.opt.deg_dir)}
+        self.embeddings = {"pos": PositionalEncoding(3, self.opt.deg_pos, self.opt), "dir": PositionalEncoding(3, self.opt.deg_dir, self.opt)}
         self.randomized = False
         self._ws = None
         self._outs: Dict[str, torch.Tensor] = {}
@@ -93,6 +94,8 @@ class NeRFDownXModel:
             raise ValueError("early_stop needs colours in [0, 1]: color_activation='none' leaves them unbounded")
         if int(opt.N_coarse) + int(opt.N_importance) not in (64, 128):
             raise ValueError(f"early_stop needs 64 or 128 samples in the pass that is cut, not {int(opt.N_coarse) + int(opt.N_importance)}")
+        if ops.embed_of(opt):
+            raise ValueError(f"early_stop needs the 8 x 256 render kernel, which has no embedding options ({ops.embed_names(ops.embed_of(opt))})")
         if not ops.is_default_arch(ops.arch_of(opt)):
             raise ValueError("early_stop needs the architecture of the fused kernels (8 x 256, skip at 4, degrees 10 / 4)")
         return eps
@@ -111,6 +114,8 @@ class NeRFDownXModel:
             raise ValueError("coarse_rgb=False needs a fine pass (N_importance > 0): without one the coarse colour is the image")
         if int(opt.N_coarse) not in ops.FUSED_SAMPLES_F16X3:
             raise ValueError(f"coarse_rgb=False needs N_coarse of 64, 128, 192 or 256, not {int(opt.N_coarse)}")
+        if ops.embed_of(opt):
+            raise ValueError(f"coarse_rgb=False needs the 8 x 256 render kernel, which has no embedding options ({ops.embed_names(ops.embed_of(opt))})")
         if not ops.is_default_arch(ops.arch_of(opt)):
             raise ValueError("coarse_rgb=False needs the architecture of the fused kernels (8 x 256, skip at 4, degrees 10 / 4)")
         return False

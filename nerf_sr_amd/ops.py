@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from .weights import (STATE_DICT_SPEC, check_state_dict, pad_no_dir, DIR_W, IN_CH, arch_of, arch_spec, is_default_arch,
-                      check_state_dict_arch, normalize_arch, arch_key)
+                      check_state_dict_arch, normalize_arch, arch_key, embed_of, embed_names, check_embed, EMBED_NO_XYZ)
 
 __all__ = [
     "subpixel_rays", "PositionalEncoding", "sample_along_rays", "resample_along_rays", "cast_rays",
@@ -109,24 +109,32 @@ def subpixel_rays(c2w, img_wh: Tuple[int, int], focal: float, downscale: int, nd
 
 # ----------------------------------------------------------------------------- E1
 class PositionalEncoding:
-    """``x -> [x, sin(2^k x), cos(2^k x)]_k``; mirrors models/embedding.py:14-62
-    (log-scale bands, xyz included; 3 input channels)."""
+    """``x -> [x, sin(f_k x), cos(f_k x)]_k``; mirrors models/embedding.py:14-62 (3 input channels) with its two options read
+    from ``opt``: ``no_xyz`` drops the identity columns, ``no_logscale`` replaces the bands ``2^k`` by
+    ``linspace(1, 2^(N_freqs-1), N_freqs)`` (nsr_posenc_e, include/nsr.h); ``freq_bands`` is the library's table."""
 
     def __init__(self, in_channels: int = 3, N_freqs: int = 10, opt=None):
         if in_channels != 3:
             raise ValueError("the built path encodes 3-channel inputs only")
         self.in_channels, self.N_freqs = in_channels, int(N_freqs)
+        self.embed = embed_of(opt)
 
     @property
     def out_channels(self) -> int:
-        return self.in_channels * (2 * self.N_freqs + 1)
+        return self.in_channels * (2 * self.N_freqs + (0 if self.embed & EMBED_NO_XYZ else 1))
+
+    @property
+    def freq_bands(self) -> np.ndarray:
+        f = (c_float * max(self.N_freqs, 1))()
+        _lib.check(_lib.load().nsr_posenc_freqs(self.N_freqs, self.embed, f), "nsr_posenc_freqs")
+        return np.array(f[: self.N_freqs], dtype=np.float32)
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         x = _f32(x, "x")
         if x.ndim != 2 or x.shape[1] != 3:
             raise ValueError(f"x must be (B, 3), got {tuple(x.shape)}")
         out = torch.empty(x.shape[0], self.out_channels, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().nsr_posenc(_p(x), x.shape[0], self.N_freqs, _p(out), _stream()), "nsr_posenc")
+        _lib.check(_lib.load().nsr_posenc_e(_p(x), x.shape[0], self.N_freqs, self.embed, _p(out), _stream()), "nsr_posenc_e")
         return out
 
 
@@ -205,6 +213,8 @@ def check_mlp_options(opt, fused: bool = True) -> None:
     for name, choices in _MLP_CHOICES.items():
         if hasattr(opt, name) and getattr(opt, name) not in choices:
             bad.append(f"{name}={getattr(opt, name)!r} (built: {list(choices)!r})")
+    if fused and embed_of(opt):
+        bad.append(f"{embed_names(embed_of(opt))} (built: the full log-scale encoding; ops.make_mlp / GenericMLP serve the embedding options)")
     if bad:
         raise ValueError("VanillaMLP option(s) outside the built path (the MFMA kernels are laid out for the 8 x 256 network with "
                          "a skip at layer 5, models/networks.py:131-180): "
@@ -336,9 +346,13 @@ class GenericMLP:
 
     POINT_CHUNK = 262144          # rows per pass (the reference's point_chunk, options/base_options.py:70): bounds the buffers
 
-    def __init__(self, opt=None, device="cuda", precision: str = "fp32", fused: bool = False, **arch):
+    def __init__(self, opt=None, device="cuda", precision: str = "fp32", fused: bool = False, embed: Optional[int] = None, **arch):
         self.arch = normalize_arch(opt, **arch)             # validates
-        self.spec = arch_spec(**self.arch)
+        # the embedding's option word (--no_xyz / --no_logscale; default: read from opt): narrower layers under no_xyz, and the
+        # word every descriptor entry point of the fused route takes (the `_e` forms, include/nsr_train.h)
+        self.embed = check_embed(embed_of(opt) if embed is None else embed, self.arch)
+        self.no_xyz = bool(self.embed & EMBED_NO_XYZ)
+        self.spec = arch_spec(no_xyz=self.no_xyz, **self.arch)
         # fused=True (opt-in, precision 'f16x3'): the whole network in ONE launch per POINT_CHUNK, activations never leave the
         # chip (nsr_arch_fused_forward, include/nsr_train.h) -- the arithmetic of the layer-by-layer route in another summation
         # order.  Refused, before a device is touched, for a precision or an architecture the kernel does not cover.
@@ -354,7 +368,8 @@ class GenericMLP:
         self.gamma_correct = bool(getattr(opt, "gamma_correct", False)) if opt is not None else False
         self.device = torch.device(device)
         _check_device(self.device, "GenericMLP device")
-        self.in_xyz, self.in_dir = 3 + 6 * self.arch["deg_pos"], 3 + 6 * self.arch["deg_dir"]
+        first = 0 if self.no_xyz else 3
+        self.in_xyz, self.in_dir = first + 6 * self.arch["deg_pos"], first + 6 * self.arch["deg_dir"]
         # "fp32": every nn.Linear on the fp32 MFMA (nsr_linear); "f16x3" (round 6): on the split-fp16 MFMA, three terms per
         # product, products exact to ~2^-21 (nsr_linear_f16x3: the weights are split once at load time) -- the arithmetic of
         # the fused kernels' default precision, layer by layer.  The single-operand fast precisions have no layer-by-layer form.
@@ -363,8 +378,8 @@ class GenericMLP:
         self.precision = precision
         self._sd = None
         color_none = self.color_activation == "none"
-        self._route = _FusedRoute(self.arch, self.device, color_none) if self.fused else \
-            _LayerRoute(self.arch, self.device, precision, color_none)
+        self._route = _FusedRoute(self.arch, self.device, color_none, self.embed) if self.fused else \
+            _LayerRoute(self.arch, self.device, precision, color_none, self.embed)
 
     @property
     def _split(self):
@@ -372,7 +387,7 @@ class GenericMLP:
         return [rec for rec in getattr(self._route, "linears", ()) if rec[2] is not None]
 
     def load_state_dict(self, sd):
-        check_state_dict_arch(sd, **self.arch)
+        check_state_dict_arch(sd, no_xyz=self.no_xyz, **self.arch)
         dev = state_dict_to_device(sd, self.spec, self.device)
         self._sd = None                 # a load that raises leaves nothing usable behind
         self._route.load(dev)
@@ -413,9 +428,10 @@ class _LayerRoute:
     """``GenericMLP`` layer by layer: the zero-padded operands of every ``nn.Linear`` as one record ``(w, b, hi, lo)`` -- ``hi``
     / ``lo`` the fp16 halves of 64 w under 'f16x3', None under 'fp32' -- and the sticky non-finite-output flag."""
 
-    def __init__(self, arch: dict, device, precision: str, color_none: bool):
+    def __init__(self, arch: dict, device, precision: str, color_none: bool, embed: int = 0):
         self.arch, self.device, self.precision, self.color_none = arch, device, precision, color_none
-        self.in_xyz, self.in_dir = 3 + 6 * arch["deg_pos"], 3 + 6 * arch["deg_dir"]
+        first = 0 if embed & EMBED_NO_XYZ else 3      # the route sees the option word only as the width of the encoded rows
+        self.in_xyz, self.in_dir = first + 6 * arch["deg_pos"], first + 6 * arch["deg_dir"]
         r32 = lambda n: (n + 31) // 32 * 32
         self.Kx, self.Wp, self.Hp, self.Dp, self.Rp = r32(self.in_xyz), r32(arch["W"]), r32(arch["W"] // 2), r32(self.in_dir), r32(arch["dim_rgb"])
         self.linears = []
@@ -514,8 +530,8 @@ class _FusedRoute:
     """``GenericMLP(fused=True)``: the weights split and re-laid once into the kernel's stream (nsr_arch_fused_pack), the
     kernel's sticky ``NSR_FLAG_*`` word, and the descriptor every ``nsr_arch_fused_*`` call takes."""
 
-    def __init__(self, arch: dict, device, color_none: bool):
-        self.arch, self.device, self.color_none = arch, device, color_none
+    def __init__(self, arch: dict, device, color_none: bool, embed: int = 0):
+        self.arch, self.device, self.color_none, self.embed = arch, device, color_none, int(embed)
         self._c_arch = _lib.NsrArch.from_arch(arch)
         self._packed = self._status = None
 
@@ -525,13 +541,13 @@ class _FusedRoute:
     def load(self, dev):
         lib, arch = _lib.load(), ctypes.byref(self._c_arch)
         self._packed = None
-        nbytes = lib.nsr_arch_fused_packed_bytes(arch)
+        nbytes = lib.nsr_arch_fused_packed_bytes_e(arch, self.embed)
         if nbytes == 0:
-            raise _lib.NsrError(f"nsr_arch_fused_packed_bytes refuses {self.arch}")
+            raise _lib.NsrError(f"nsr_arch_fused_packed_bytes_e refuses {self.arch} with embedding option word {self.embed:#x}")
         packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._status = torch.zeros(1, dtype=torch.int32, device=self.device)
         ptrs = (c_void_p * len(dev))(*[_p(t) for t in dev.values()])
-        _lib.check(lib.nsr_arch_fused_pack(arch, ptrs, _p(packed), _p(self._status), _stream()), "nsr_arch_fused_pack")
+        _lib.check(lib.nsr_arch_fused_pack_e(arch, self.embed, ptrs, _p(packed), _p(self._status), _stream()), "nsr_arch_fused_pack_e")
         if int(self._status.item()) & 1:    # the stream holds the out-of-range network: nothing usable is loaded
             self._status.zero_()
             raise _lib.NsrNumericsError(
@@ -553,15 +569,15 @@ class _FusedRoute:
 
     def forward(self, x: torch.Tensor, out: torch.Tensor, sigma_only: bool) -> None:
         """One launch, no intermediate buffers."""
-        _lib.check(_lib.load().nsr_arch_fused_forward(ctypes.byref(self._c_arch), _p(self._packed), _p(x), x.shape[1], x.shape[0],
-                                                      self._flags(sigma_only), _p(out), out.shape[1], _p(self._status), _stream()),
-                   "nsr_arch_fused_forward")
+        _lib.check(_lib.load().nsr_arch_fused_forward_e(ctypes.byref(self._c_arch), self.embed, _p(self._packed), _p(x), x.shape[1],
+                                                        x.shape[0], self._flags(sigma_only), _p(out), out.shape[1], _p(self._status),
+                                                        _stream()), "nsr_arch_fused_forward_e")
 
     def render_rays(self, rays: torch.Tensor, z_vals: torch.Tensor, raw: torch.Tensor, sigma_only: bool) -> None:
         R, N = z_vals.shape
-        _lib.check(_lib.load().nsr_arch_fused_render_rays(ctypes.byref(self._c_arch), _p(self._packed), _p(rays), rays.shape[1], _p(z_vals),
-                                                          R, N, self._flags(sigma_only), _p(raw), raw.shape[2], _p(self._status),
-                                                          _stream()), "nsr_arch_fused_render_rays")
+        _lib.check(_lib.load().nsr_arch_fused_render_rays_e(ctypes.byref(self._c_arch), self.embed, _p(self._packed), _p(rays),
+                                                            rays.shape[1], _p(z_vals), R, N, self._flags(sigma_only), _p(raw),
+                                                            raw.shape[2], _p(self._status), _stream()), "nsr_arch_fused_render_rays_e")
 
 
 def check_arch_fused(arch: dict, precision: str) -> None:
@@ -589,32 +605,37 @@ def make_mlp(opt=None, precision: str = "fp32", device="cuda", arch_fused: Optio
     ``arch_fused`` (default: ``opt.arch_fused``, off) under precision 'f16x3', in one fused launch (``GenericMLP(fused=True)``)."""
     if arch_fused is None:
         arch_fused = bool(getattr(opt, "arch_fused", False)) if opt is not None else False
-    if is_default_arch(arch_of(opt)):
+    embed = embed_of(opt)
+    if is_default_arch(arch_of(opt)) and not embed:
         return VanillaMLP(opt, precision=precision, device=device)
+    if embed and precision not in ("fp32", "f16x3"):     # an option is never served by another precision than the one asked for
+        raise ValueError(f"{embed_names(embed)} with precision={precision!r}: the embedding options run on the descriptor routes "
+                         "(ops.GenericMLP), which have 'fp32' and 'f16x3' only; the single-operand fast paths are the 8 x 256 kernels'")
     if arch_fused:
         return GenericMLP(opt, device=device, precision=precision, fused=True)
-    warn_generic_mlp(arch_of(opt), precision)
+    warn_generic_mlp(arch_of(opt), precision, embed)
     return GenericMLP(opt, device=device, precision="f16x3" if precision == "f16x3" else "fp32")
 
 
 _GENERIC_WARNED = set()
 
 
-def warn_generic_mlp(arch: dict, precision: str = "fp32") -> None:
+def warn_generic_mlp(arch: dict, precision: str = "fp32", embed: int = 0) -> None:
     """One warning per architecture and process: a non-default ``--D --W --skips`` / encoding degree leaves the fused MFMA
     kernels (whose register, LDS and weight-stream layouts ARE the 8 x 256 network with a skip at layer 5) for the
     layer-by-layer fp32 GEMM route -- correct (tests/golden/arch.npz, made by the reference's own forward), but every
     activation matrix travels through HBM: `bench.py --arch D,W,skips` times it (README: ~an order of magnitude slower per
     sample point than the fused f16x3 kernel at the default size) -- on the fp32 MFMA, or under precision 'f16x3' on the split-fp16 MFMA (three terms per product, nsr_linear_f16x3)."""
     import warnings
-    key = arch_key(arch)
-    if key in _GENERIC_WARNED:
+    key = arch_key(arch) + ((embed_names(embed),) if embed else ())     # an embedding option makes any network, the default
+    if key in _GENERIC_WARNED:                                           # one included, "a non-default architecture"
         return
     _GENERIC_WARNED.add(key)
+    with_embed = f" with {embed_names(embed)} (models/embedding.py:17-18)" if embed else ""
     note = "" if precision in ("fp32", "f16x3") else f"; precision={precision!r} has no layer-by-layer form: running fp32"
     how = "split-fp16 (three-term)" if precision == "f16x3" else "fp32"
-    warnings.warn(f"NeRF-SR network D={key[0]} W={key[1]} skips={list(key[2])} deg_pos={key[3]} deg_dir={key[4]} is not the "
-                  f"architecture of the fused kernels (8 x 256, skip at 4, degrees 10 / 4): running the layer-by-layer {how} GEMM "
+    warnings.warn(f"NeRF-SR network D={key[0]} W={key[1]} skips={list(key[2])} deg_pos={key[3]} deg_dir={key[4]}{with_embed} is not the "
+                  f"architecture of the fused kernels (8 x 256, skip at 4, degrees 10 / 4, full log-scale encodings): running the layer-by-layer {how} GEMM "
                   f"path (ops.GenericMLP), several times slower per sample point{note}", RuntimeWarning, stacklevel=3)
 
 
@@ -709,6 +730,9 @@ def check_early_stop(early_stop: float, net, n_last: int, sigma_activation: str 
         raise ValueError(f"early_stop={early_stop!r}: a transmittance threshold in [0, 1) (0 = off)")
     if eps == 0.0:
         return eps
+    if getattr(net, "embed", 0):
+        raise ValueError(f"early_stop needs the 8 x 256 render kernel, which has no embedding options: the network was built with "
+                         f"{embed_names(net.embed)}")
     if not isinstance(net, VanillaMLP) or net.precision != "f16x3":
         raise ValueError(f"early_stop needs precision 'f16x3' (the split-fp16 render kernel), not {getattr(net, 'precision', None)!r}")
     if sigma_activation != "relu":
@@ -761,6 +785,9 @@ FUSED_SAMPLES_F16X3 = (64, 128, 192, 256)     # sample counts of the split-fp16 
 def check_density_coarse(net, n_coarse: int, n_importance: Optional[int] = None) -> None:
     """Validates the test-time mode (``coarse_rgb=False`` / ``render_rays_density``): a ``ValueError`` names the condition
     that fails -- the option is never ignored silently.  ``n_importance`` None: a direct density launch (no fine pass)."""
+    if getattr(net, "embed", 0):
+        raise ValueError(f"coarse_rgb=False (the density-only pass) needs the 8 x 256 render kernel, which has no embedding options: "
+                         f"the network was built with {embed_names(net.embed)}")
     if not isinstance(net, VanillaMLP) or net.precision != "f16x3":
         raise ValueError(f"coarse_rgb=False (the density-only pass) needs precision 'f16x3' (the split-fp16 render kernel), "
                          f"not {getattr(net, 'precision', None)!r}")

@@ -31,6 +31,7 @@ from . import _lib
 from .ops import OUT_KEYS, _f32, _p, _ray_stride, _stream, renderer_flags, state_dict_to_device
 from .weights import STATE_DICT_SPEC, check_state_dict_arch, pad_no_dir, DIR_W, arch_key, arch_spec
 from .weights import normalize_arch as _normalize_arch
+from .weights import check_embed, embed_names, EMBED_NO_XYZ
 
 
 def _ptr_array(tensors):
@@ -96,11 +97,11 @@ class TrainWorkspace:
 _DEFAULT_WS: Dict[torch.device, TrainWorkspace] = {}
 
 
-def _weights(params, name: str, arch: Optional[dict] = None):
+def _weights(params, name: str, arch: Optional[dict] = None, no_xyz: bool = False):
     """A network's tensors in state_dict order for ``arch`` (None: the default network's 24): an nn.Module such as the
     reference's own ``netCoarse`` built with those flags (``parameters()`` has the state_dict's order), a dict keyed like
     ``weights.arch_spec``, or a sequence.  Count and shapes are checked before anything else about the tensors."""
-    spec = STATE_DICT_SPEC if arch is None else arch_spec(**arch)
+    spec = STATE_DICT_SPEC if arch is None else arch_spec(no_xyz=no_xyz, **arch)
     if isinstance(params, torch.nn.Module):
         ts = list(params.parameters())
     elif isinstance(params, dict):
@@ -160,6 +161,15 @@ def arch_precision(arch: dict, precision: str) -> str:
     return "f16x3_gemm"
 
 
+def embed_precision(embed: int, precision: str) -> str:
+    """``arch_precision`` for a network with an embedding option: the layer-by-layer precisions as they are; every chain name
+    raises ``ValueError`` naming the option (the chain kernels compute the full log-scale encodings)."""
+    if precision in ARCH_PRECISIONS:
+        return precision
+    raise ValueError(f"precision={precision!r} with {embed_names(embed)}: the embedding options train layer by layer under "
+                     f"{list(ARCH_PRECISIONS)}; the chain kernels are the default network's, with its encodings")
+
+
 def train_flags(white_bkgd: bool = False, gamma_correct: bool = False, sigma_activation: str = "relu",
                 color_activation: str = "sigmoid", stop_grad: bool = False) -> int:
     """The option word of the training entry points (include/nsr_train.h): the renderer's word (``ops.renderer_flags``) plus
@@ -189,15 +199,19 @@ class _TrainRun:
     """The arguments of one forward_rays_train call that are not tensors, and the pair of entry points it runs: the default
     network's, or with ``arch`` (struct nsr_arch) the layer-by-layer pair, which differs by that leading argument only."""
 
-    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace, arch=None):
+    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace, arch=None, embed: int = 0):
         self.nc, self.ni, self.flags, self.lindisp = nc, ni, flags, lindisp
         self.noise_std, self.prec, self.chunk, self.workspace = noise_std, prec, chunk, workspace
         self.arch = arch
         self.lead = () if arch is None else (ctypes.byref(arch),)
+        self.embed = int(embed)
         self.names = {"saved_bytes": "nsr_train_saved_bytes", "workspace_bytes": "nsr_train_workspace_bytes_for",
                       "forward": "nsr_train_forward", "backward": "nsr_train_backward"} if arch is None else \
             {"saved_bytes": "nsr_train_arch_saved_bytes", "workspace_bytes": "nsr_train_arch_workspace_bytes",
              "forward": "nsr_train_arch_forward", "backward": "nsr_train_arch_backward"}
+        if self.embed:      # the embedding's option word behind the descriptor: the `_e` forms of the same four (include/nsr_train.h)
+            self.lead += (self.embed,)
+            self.names = {k: v + "_e" for k, v in self.names.items()}
 
     def call(self, what: str, *args):
         """``(name, result)`` of this run's entry point ``what`` on ``args`` behind the leading descriptor."""
@@ -255,7 +269,7 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
                        N_coarse: int = 64, N_importance: int = 64, white_bkgd: bool = False, lindisp: bool = False,
                        noise_std: float = 0.0, gamma_correct: bool = False, sigma_activation: str = "relu",
                        color_activation: str = "sigmoid", stop_grad: bool = False, precision: str = "f16x3",
-                       ray_chunk: int = 0, workspace: Optional[TrainWorkspace] = None, arch=None) -> Dict[str, torch.Tensor]:
+                       ray_chunk: int = 0, workspace: Optional[TrainWorkspace] = None, arch=None, embed: int = 0) -> Dict[str, torch.Tensor]:
     """Train-mode ``forward_rays`` (``models/nerf_downX_model.py:280-313``) that autograd differentiates with respect to the
     24 + 24 weight tensors of ``params_c`` / ``params_f`` (the reference's ``netCoarse`` / ``netFine`` modules, their
     parameter lists, or state-dict-like dicts such as ``Trainer.params``).  Returns the eight ``OUT_KEYS`` outputs; any loss
@@ -270,14 +284,23 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     object carrying ``--D --W --skips --deg_pos --deg_dir --no_dir``): the layer-by-layer pair ``nsr_train_arch_forward`` /
     ``nsr_train_arch_backward`` over the 2 D + 8 tensors of each network, e.g. the reference's own ``netCoarse`` /
     ``netFine`` built with those flags.  ``precision``: 'fp32' or 'f16x3_gemm' ('f16x3' maps to 'f16x3_gemm' with one
-    RuntimeWarning per architecture; the chain names raise ValueError).  None = the default network, as before."""
+    RuntimeWarning per architecture; the chain names raise ValueError).  None = the default network, as before.
+
+    ``embed``: the embedding's option word (``weights.embed_of(opt)``: ``--no_xyz`` / ``--no_logscale``).  A non-zero word runs the
+    layer-by-layer pair (``nsr_train_arch_forward_e`` / ``_backward_e``) -- on the default descriptor when ``arch`` is None -- over
+    networks whose layer 0, skip layers and ``dir_encoding`` have the option's widths (``weights.arch_spec(no_xyz=...)``)."""
     if rays.requires_grad:
         raise ValueError("forward_rays_train: rays must not require grad (there is no gradient with respect to rays)")
     flags = train_flags(white_bkgd, gamma_correct, sigma_activation, color_activation, stop_grad)
+    embed = int(embed)
+    if embed and arch is None:     # the chain kernels have no embedding options: the default network as a descriptor
+        arch = {}
     if arch is not None:      # everything about the architecture is checked before a device is touched
         arch = normalize_arch(arch)
-        precision = arch_precision(arch, precision)
-        wc, wf = _weights(params_c, "params_c", arch), _weights(params_f, "params_f", arch)
+        check_embed(embed, arch)
+        precision = embed_precision(embed, precision) if embed else arch_precision(arch, precision)
+        no_xyz = bool(embed & EMBED_NO_XYZ)
+        wc, wf = _weights(params_c, "params_c", arch, no_xyz), _weights(params_f, "params_f", arch, no_xyz)
     rays = _f32(rays, "rays")
     _ray_stride(rays)
     if precision not in _lib.TRAIN_PRECISIONS:
@@ -294,7 +317,7 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
         workspace = _DEFAULT_WS.setdefault(rays.device, TrainWorkspace())
     run = _TrainRun(int(N_coarse), int(N_importance), flags, int(bool(lindisp)), float(noise_std),
                     _lib.TRAIN_PRECISIONS[precision], int(ray_chunk), workspace,
-                    None if arch is None else _lib.NsrArch.from_arch(arch))
+                    None if arch is None else _lib.NsrArch.from_arch(arch), embed)
     outs = _ForwardRaysTrain.apply(run, rays, *d, *wc, *wf)
     return dict(zip(OUT_KEYS, outs))
 
@@ -318,13 +341,19 @@ class Trainer:
                  use_var_loss: bool = False, lambda_coarse_var: float = 0.01, lambda_fine_var: float = 0.01,
                  use_depth_var_loss: bool = False, lambda_coarse_depth_var: float = 0.01, lambda_fine_depth_var: float = 0.01,
                  no_dir: bool = False, sigma_activation: str = "relu", color_activation: str = "sigmoid", stop_grad: bool = False,
-                 grad_clip_val: float = 0.0, grad_clip_type: str = "norm", arch=None):
+                 grad_clip_val: float = 0.0, grad_clip_type: str = "norm", arch=None, embed: int = 0):
+        # embed: the embedding's option word (weights.embed_of(opt): --no_xyz / --no_logscale).  Non-zero: the architecture route
+        # below (on the default descriptor when arch is None) with the `_e` pair; precision 'fp32' or 'f16x3_gemm'
+        self.embed = int(embed)
+        if self.embed and arch is None:
+            arch = {}
         # arch: the architecture flags of both networks (see forward_rays_train); None = the default network and the fused step.
         # With an architecture the iteration is forward -> losses in torch -> backward -> Adam over the 2 D + 8 tensors
         # (nsr_train_arch_forward / _backward, nsr_adam_step_n), --no_dir runs natively as the narrow dir_encoding
         self.arch = None if arch is None else normalize_arch(arch)
         if self.arch is not None:
-            precision = arch_precision(self.arch, precision)
+            check_embed(self.embed, self.arch)
+            precision = embed_precision(self.embed, precision) if self.embed else arch_precision(self.arch, precision)
             if bool(no_dir) and not self.arch["no_dir"]:
                 self.arch["no_dir"] = True
         # --grad_clip_val / --grad_clip_type (models/nerf_downX_model.py:403-407): both networks' gradients together, between
@@ -352,8 +381,8 @@ class Trainer:
         desc = self.arch if self.arch is not None else _normalize_arch(no_dir=self.no_dir)
         self.params = []
         for sd in (sd_coarse, sd_fine):
-            check_state_dict_arch(sd, **desc)
-            p = state_dict_to_device(sd, arch_spec(**desc), self.device, own=True)
+            check_state_dict_arch(sd, no_xyz=bool(self.embed & EMBED_NO_XYZ), **desc)
+            p = state_dict_to_device(sd, arch_spec(no_xyz=bool(self.embed & EMBED_NO_XYZ), **desc), self.device, own=True)
             if self._padded:
                 p[DIR_W] = pad_no_dir(p[DIR_W])
             self.params.append(p)
@@ -539,7 +568,7 @@ class Trainer:
                                   white_bkgd=self.white_bkgd, lindisp=self.lindisp, noise_std=self.noise_std,
                                   gamma_correct=self.gamma_correct, sigma_activation=self.sigma_activation,
                                   color_activation=self.color_activation, stop_grad=self.stop_grad, precision=self.precision,
-                                  ray_chunk=self.ray_chunk, workspace=self._workspace, arch=self.arch)
+                                  ray_chunk=self.ray_chunk, workspace=self._workspace, arch=self.arch, embed=self.embed)
 
     def backward(self, loss: torch.Tensor):
         """d(loss)/d(weights) of the forwards behind ``loss`` into ``self.grads`` / ``self.flat_grads`` (OVERWRITTEN; scaled by

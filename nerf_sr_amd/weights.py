@@ -47,18 +47,48 @@ def arch_of(opt=None) -> dict:
             "no_dir": bool(g("no_dir", False))}
 
 
+EMBED_NO_XYZ, EMBED_LINEAR_FREQS = 1, 2      # include/nsr.h: NSR_EMBED_NO_XYZ, NSR_EMBED_LINEAR_FREQS
+
+
+def embed_of(opt=None) -> int:
+    """The embedding's option word of an options object (models/embedding.py:17-18 ``--no_xyz``, ``--no_logscale``; absent
+    options = 0, the reference's defaults).  It travels NEXT TO the architecture dict, whose keys stay as they are."""
+    if opt is None:
+        return 0
+    return (EMBED_NO_XYZ if bool(getattr(opt, "no_xyz", False)) else 0) | \
+        (EMBED_LINEAR_FREQS if bool(getattr(opt, "no_logscale", False)) else 0)
+
+
+def embed_names(embed: int) -> str:
+    """The reference's flag names of an option word, for messages."""
+    return " ".join(n for bit, n in ((EMBED_NO_XYZ, "--no_xyz"), (EMBED_LINEAR_FREQS, "--no_logscale")) if embed & bit)
+
+
+def check_embed(embed: int, arch: dict) -> int:
+    """``ValueError`` for a word the library refuses (include/nsr.h): an unknown bit, ``--no_xyz`` on an encoding of degree 0 that
+    the network reads.  Host only; returns the word."""
+    embed = int(embed)
+    if embed & ~(EMBED_NO_XYZ | EMBED_LINEAR_FREQS):
+        raise ValueError(f"embed={embed:#x}: an OR of EMBED_NO_XYZ (1) and EMBED_LINEAR_FREQS (2)")
+    if embed & EMBED_NO_XYZ and (arch["deg_pos"] == 0 or (arch["deg_dir"] == 0 and not arch["no_dir"])):
+        raise ValueError("no_xyz with an encoding of degree 0 leaves a layer without input columns "
+                         "(deg_pos must be >= 1, and deg_dir unless no_dir): the reference cannot build that network either")
+    return embed
+
+
 def is_default_arch(arch: dict) -> bool:
     """True when the fused kernels cover it (``no_dir`` rides them too: weights.pad_no_dir)."""
     return all(arch[k] == v for k, v in (("D", D_LAYERS), ("W", WIDTH), ("skips", (SKIP_LAYER,)), ("deg_pos", DEG_POS),
                                           ("deg_dir", DEG_DIR), ("dim_rgb", 3)))
 
 
-def arch_spec(D=D_LAYERS, W=WIDTH, skips=(SKIP_LAYER,), deg_pos=DEG_POS, deg_dir=DEG_DIR, dim_rgb=3, no_dir=False):
-    """key -> shape of ``VanillaMLP(opt).state_dict()`` for these flags, in the module's own order (models/networks.py:131-180)."""
+def arch_spec(D=D_LAYERS, W=WIDTH, skips=(SKIP_LAYER,), deg_pos=DEG_POS, deg_dir=DEG_DIR, dim_rgb=3, no_dir=False, no_xyz=False):
+    """key -> shape of ``VanillaMLP(opt).state_dict()`` for these flags, in the module's own order (models/networks.py:131-180).
+    ``no_xyz`` (models/embedding.py:17): the encodings lose their 3 identity columns (models/networks.py:143-163)."""
     if D < 1 or W < 2 or W % 2 or deg_pos < 0 or deg_dir < 0 or dim_rgb < 1 or any(s < 1 or s >= D for s in skips):
         raise ValueError("D >= 1, even W >= 2, degrees >= 0, dim_rgb >= 1 and skip layers inside 1 .. D - 1 "
                          "(a skip at layer 0 would double the input: the reference's constructor gives layer 0 the plain width)")
-    in_xyz, in_dir = 3 + 6 * deg_pos, 3 + 6 * deg_dir
+    in_xyz, in_dir = (0 if no_xyz else 3) + 6 * deg_pos, (0 if no_xyz else 3) + 6 * deg_dir
     spec = OrderedDict()
     for i in range(D):
         fan_in = in_xyz if i == 0 else (W + in_xyz if i in skips else W)
@@ -113,9 +143,10 @@ def _check(sd, spec, note: str) -> None:
             raise ValueError(f"state_dict[{k!r}] has shape {tuple(sd[k].shape)}, expected {tuple(shape)}{note}")
 
 
-def check_state_dict_arch(sd, **arch) -> None:
-    """Raise ``ValueError`` unless ``sd`` has exactly the keys and shapes of ``arch_spec(**arch)``."""
-    _check(sd, arch_spec(**arch), f" for {arch}")
+def check_state_dict_arch(sd, no_xyz: bool = False, **arch) -> None:
+    """Raise ``ValueError`` unless ``sd`` has exactly the keys and shapes of ``arch_spec(**arch)`` (``no_xyz``: of the ``--no_xyz``
+    network, and the message says so)."""
+    _check(sd, arch_spec(no_xyz=no_xyz, **arch), f" for {arch}" + (" with --no_xyz" if no_xyz else ""))
 
 
 def check_state_dict(sd, no_dir: bool = False) -> None:
@@ -143,7 +174,7 @@ FIELDS = {
 }
 
 
-def _generate(seed: int, field: str, bias_scale: float, arch: dict):
+def _generate(seed: int, field: str, bias_scale: float, arch: dict, no_xyz: bool = False):
     """One draw per tensor in ``arch_spec`` order (so a seed's arrays never change), then the field preset."""
     if field not in FIELDS:
         raise ValueError(f"field must be one of {list(FIELDS)}")
@@ -151,13 +182,14 @@ def _generate(seed: int, field: str, bias_scale: float, arch: dict):
     a = normalize_arch(arch)
     rng = np.random.Generator(np.random.PCG64(seed))
     sd = OrderedDict()
-    for key, shape in arch_spec(**a).items():
+    for key, shape in arch_spec(no_xyz=no_xyz, **a).items():
         scale = np.sqrt(2.0 / shape[1]) if key.endswith("weight") else bias_scale
         sd[key] = (rng.standard_normal(shape, dtype=np.float64) * scale).astype(np.float32)
     if decay > 0:
+        c0 = 0 if no_xyz else 3                 # first band column
         for i in (0,) + a["skips"]:             # the layers that read the positional encoding, in their first columns
             for k in range(a["deg_pos"]):
-                sd[f"xyz_encoding_{i + 1}.0.weight"][:, 3 + 6 * k: 9 + 6 * k] *= np.float32(2.0 ** (-decay * k))
+                sd[f"xyz_encoding_{i + 1}.0.weight"][:, c0 + 6 * k: c0 + 6 + 6 * k] *= np.float32(2.0 ** (-decay * k))
     sd["sigma.weight"] = (sd["sigma.weight"] * np.float32(sigma_scale)).astype(np.float32)
     if sigma_bias is not None:
         sd["sigma.bias"] = np.full((1,), sigma_bias, dtype=np.float32)
@@ -192,7 +224,8 @@ def make_state_dict(seed: int = 99, field: str = "smooth", bias_scale: float = 0
     return _generate(seed, field, bias_scale, {})
 
 
-def make_state_dict_arch(seed: int, bias_scale: float = 0.05, **arch):
+def make_state_dict_arch(seed: int, bias_scale: float = 0.05, no_xyz: bool = False, **arch):
     """``make_state_dict``'s "smooth" field for any architecture ``arch_spec`` describes: kaiming weights, small biases, the
-    density head (``sigma.weight`` x 10, ``sigma.bias`` -3) and 1/f positional-encoding columns."""
-    return _generate(seed, "smooth", bias_scale, arch)
+    density head (``sigma.weight`` x 10, ``sigma.bias`` -3) and 1/f positional-encoding columns.  ``no_xyz``: the shapes of the
+    ``--no_xyz`` network (one draw per tensor in the same order)."""
+    return _generate(seed, "smooth", bias_scale, arch, no_xyz)
