@@ -171,6 +171,11 @@ if os.path.exists(_REFINE_WGRAD_HOOKS_SRC):
 _ENCODE_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_encode.hip")
 if os.path.exists(_ENCODE_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_ENCODE_HOOKS_SRC)
+# ... and the launchers of the gradient reduction and placement kernels of both training paths, and chain_weight_grads as a
+# whole (tests/test_gpu_train_reduce_units.py, test_gpu_train_finish_jobs.py, test_gpu_chain_weight_grads.py); same condition
+_REDUCE_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_reduce.hip")
+if os.path.exists(_REDUCE_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_REDUCE_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

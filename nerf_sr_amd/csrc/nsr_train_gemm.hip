@@ -167,16 +167,56 @@ __global__ void __launch_bounds__(256) reduce_place_kernel(float* __restrict__ d
   float* d = dst + (int64_t)i * dst_ld + dc0 + j;
   *d = (accumulate ? *d : 0.0f) + (float)(s * (double)scale);   // scale: a power of two (pre-scaled operands)
 }
-// ---- host wrappers over the kernels above: one linear layer's three products, the deterministic reductions behind them
-int place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* src, int src_ld, int rows, int cols,
-          int col0, int transpose) {
+}  // namespace
+
+// ---- host wrappers over the kernels above (nsr_train_work.h; the unit tests launch them one by one): the deterministic
+// reductions and placements behind a linear layer's products
+int nsr::place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* src, int src_ld, int rows, int cols,
+               int col0, int transpose) {
   const int n = rows * cols;
   hipLaunchKernelGGL(place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, dst_ld, r0, c0, src, src_ld, rows, cols,
                      col0, transpose);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
+int nsr::scatter_heads(hipStream_t st, const float* d4, int64_t P, float* drgb, float* gsig, int64_t ldg) {
+  hipLaunchKernelGGL(scatter_heads_kernel, dim3((unsigned)((P * 8 + 255) / 256)), dim3(256), 0, st,
+                     reinterpret_cast<const float4*>(d4), P, drgb, gsig, ldg);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int nsr::tile_sums(hipStream_t st, float* col_tiles, int64_t n_tiles, int N, int n_bias, float* bias_grad, int acc) {
+  double* part = reinterpret_cast<double*>(col_tiles + n_tiles * N);   // behind the tile sums
+  const int slices = 64;
+  hipLaunchKernelGGL(tilesum_partial_kernel, dim3((N + 63) / 64, slices), dim3(256), 0, st, col_tiles, n_tiles, N, N, part);
+  NSR_CHECK_LAUNCH();
+  const int nb = n_bias > 0 ? n_bias : N;
+  hipLaunchKernelGGL(sum_finish_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, part, slices, N, nb, bias_grad, acc);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int nsr::reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows, int cols, const float* partial, int splits,
+                      int p_ld, int pr0, int pc0, int accumulate, float scale, int64_t stride) {
+  const int n = rows * cols;
+  hipLaunchKernelGGL(reduce_place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, dst_ld, dc0, rows, cols, partial,
+                     splits, stride, p_ld, pr0, pc0, accumulate, scale);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+int nsr::colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, float* dst, int accumulate,
+                float* scratch) {
+  if (cols > 4) return NSR_ERR_INVALID_ARG;
+  double* part = reinterpret_cast<double*>(scratch);
+  hipLaunchKernelGGL(colsum_few_kernel, dim3(kSumBlocks), dim3(256), 0, st, src, ld, P, col0, cols, part);
+  NSR_CHECK_LAUNCH();
+  hipLaunchKernelGGL(sum_finish_kernel, dim3((cols + 3) / 4), dim3(256), 0, st, part, kSumBlocks, 4, cols, dst, accumulate);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
 
+namespace {
+
+// ---- one linear layer's three products
 // y (P, N) = act(x (P, K) w (N, K)^T + b); hi / lo (the weights' split-fp16 halves, row stride ldh) select the split-fp16 product
 int lin_fwd_at(hipStream_t st, const float* x, int64_t ldx, int K, const float* w, int ldw, const float* b, int act,
                float* y, int64_t ldy, int64_t P, int N, int n_valid, const unsigned short* hi, const unsigned short* lo,
@@ -205,15 +245,7 @@ int lin_dgrad(hipStream_t st, float* col_tiles, const float* dy, int64_t lddy, i
   g.col_sums = bias_grad ? col_tiles : nullptr;
   const int rc = gemm(g, st);
   if (rc != NSR_OK || !bias_grad) return rc;
-  double* part = reinterpret_cast<double*>(col_tiles + ((P + 127) / 128) * N);   // behind the tile sums
-  const int slices = 64;
-  hipLaunchKernelGGL(tilesum_partial_kernel, dim3((N + 63) / 64, slices), dim3(256), 0, st, col_tiles, (P + 127) / 128, N,
-                     N, part);
-  NSR_CHECK_LAUNCH();
-  const int nb = n_bias > 0 ? n_bias : N;
-  hipLaunchKernelGGL(sum_finish_kernel, dim3((nb + 3) / 4), dim3(256), 0, st, part, slices, N, nb, bias_grad, acc);
-  NSR_CHECK_LAUNCH();
-  return NSR_OK;
+  return tile_sums(st, col_tiles, (P + 127) / 128, N, n_bias, bias_grad, acc);
 }
 // partial[z] (M x N) = sum over the z-th slice of the points of dy[p][0..M) x[p][0..N)^T
 // (slice z at partial + z * stride)
@@ -223,25 +255,6 @@ int lin_wgrad(hipStream_t st, const float* dy, int64_t lddy, int M, const float*
   g.A = dy; g.lda = lddy; g.a_kmajor = 1; g.B = x; g.ldb = ldx; g.b_kmajor = 1; g.C = partial; g.ldc = N;
   g.M = M; g.N = N; g.K = P; g.n_valid = N; g.act = kActNone; g.splits = splits; g.split_stride = stride;
   return gemm(g, st);
-}
-int reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows, int cols, const float* partial, int splits,
-                 int p_ld, int pr0, int pc0, int accumulate, float scale, int64_t stride) {
-  const int n = rows * cols;
-  hipLaunchKernelGGL(reduce_place_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dst, dst_ld, dc0, rows, cols, partial,
-                     splits, stride, p_ld, pr0, pc0, accumulate, scale);
-  NSR_CHECK_LAUNCH();
-  return NSR_OK;
-}
-// `scratch`: >= kSumBlocks * 4 doubles (the split-K partial buffer is free between two weight gradients)
-int colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, float* dst, int accumulate,
-           float* scratch) {
-  if (cols > 4) return NSR_ERR_INVALID_ARG;
-  double* part = reinterpret_cast<double*>(scratch);
-  hipLaunchKernelGGL(colsum_few_kernel, dim3(kSumBlocks), dim3(256), 0, st, src, ld, P, col0, cols, part);
-  NSR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(sum_finish_kernel, dim3((cols + 3) / 4), dim3(256), 0, st, part, kSumBlocks, 4, cols, dst, accumulate);
-  NSR_CHECK_LAUNCH();
-  return NSR_OK;
 }
 
 // ---- the network
@@ -430,9 +443,7 @@ int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, con
   const int64_t ps = S.part_stride;
   float* part = k.partial;
   const int ldg = S.Wp + 32;
-  hipLaunchKernelGGL(scatter_heads_kernel, dim3((unsigned)((P * 8 + 255) / 256)), dim3(256), 0, st,
-                     reinterpret_cast<const float4*>(k.d4), P, k.drgb, k.g1 + S.Wp, (int64_t)ldg);
-  NSR_CHECK_LAUNCH();
+  NSR_TRY(scatter_heads(st, k.d4, P, k.drgb, k.g1 + S.Wp, ldg));
   // rgb head
   NSR_TRY(lin_wgrad(st, k.drgb, 32, 32, s.cc, S.Hp, S.Hp, P, part, sp, ps));
   NSR_TRY(reduce_place(st, g[S.rgb_w()], S.H, 0, 3, S.H, part, sp, S.Hp, 0, 0, acc, 1.0f, ps));

@@ -83,14 +83,8 @@ __device__ __forceinline__ int enc_panel_row(int enc_rows, int j) {
 //           bias gradients of the two heads, composite_bwd_kernel): one wavefront per element, lanes stride over z
 // Twenty-odd launches of a few microseconds of work each (one wave of latency-bound workgroups) became the tail of
 // the step once the GEMMs before them had shrunk; together they keep the memory system busy.
-struct FinishJob {
-  float* dst;
-  const float* partial;
-  int64_t stride;
-  int kind, dst_ld, dc0, rows, cols, splits, p_ld, accumulate, enc_rows;
-  float scale;
-};
-constexpr int kMaxFinishJobs = 32;
+// (FinishJob, kMaxFinishJobs: nsr_train_work.h.)  One job's threads are the 256 x 256 of its grid row: kinds 0 and 1 (up to 64
+// slices) own one element each, so rows * cols <= 65,536 (finish_jobs checks it).
 struct FinishJobs {
   FinishJob j[kMaxFinishJobs];
   int n;
@@ -158,6 +152,37 @@ __global__ void __launch_bounds__(256) finish_jobs_kernel(FinishJobs jobs) {
 }
 }  // namespace
 
+// the slice plan of a head stream: 4 slices per CU (round 6).  With one 256-thread workgroup per CU (rounds 3-5: `sp` slices) a
+// CU had 4-16 KiB of loads in flight and the streams ran at 1.5-2.3 TB/s (28 + 21 us coarse, 44 + 31 us fine: 4 % of the step)
+int nsr::panel_wsums(hipStream_t st, int R, int NW, const char* panel, int64_t P, const float* w, int w_stride, float* partial,
+                     int* slices) {
+  if (!((R == 128 && NW == 3) || (R == 256 && NW == 1))) return NSR_ERR_UNSUPPORTED;
+  const int64_t n_pg = P / 32;
+  const int hs = (int)(n_pg < 1024 ? (n_pg < 1 ? 1 : n_pg) : 1024);
+  const int64_t per = (n_pg + hs - 1) / hs;
+  if (R == 128) hipLaunchKernelGGL((panel_wsums_kernel<128, 3>), dim3(hs), dim3(256), 0, st, panel, P, w, w_stride, per, partial);
+  else hipLaunchKernelGGL((panel_wsums_kernel<256, 1>), dim3(hs), dim3(256), 0, st, panel, P, w, w_stride, per, partial);
+  NSR_CHECK_LAUNCH();
+  *slices = hs;
+  return NSR_OK;
+}
+
+// nothing is launched unless every job fits the kernel: a job beyond its grid row would be cut off silently
+int nsr::finish_jobs(hipStream_t st, const FinishJob* j, int n) {
+  if (!j || n < 1 || n > kMaxFinishJobs) return NSR_ERR_INVALID_ARG;
+  FinishJobs jobs{};
+  for (int i = 0; i < n; ++i) {
+    const FinishJob& q = j[i];
+    if (q.kind < 0 || q.kind > 2 || !q.dst || !q.partial || q.rows < 0 || q.cols < 0 || q.splits < 0) return NSR_ERR_INVALID_ARG;
+    if (q.kind == 2 ? q.rows > 4 : ((q.kind == 0 || q.splits <= 64) && (int64_t)q.rows * q.cols > 65536)) return NSR_ERR_UNSUPPORTED;
+    jobs.j[i] = q;
+  }
+  jobs.n = n;
+  hipLaunchKernelGGL(finish_jobs_kernel, dim3(256, n), dim3(256), 0, st, jobs);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
 // zpan = the forward activations, dpan = the input gradients at each point's power-of-two scale (k.pscale); d_rgb_pre and
 // d_sigma in k.d4 (P, 4).  ~256 workgroups share the products' point groups by bytes: a 256 x 256 product ends up with ~21
 // partial tiles instead of the 256 a launch of its own needed to fill the chip -- 12 x fewer partial sums to write, and for
@@ -167,7 +192,7 @@ int nsr::chain_weight_grads(hipStream_t st, const Work& k, int64_t P, int64_t n_
   constexpr int64_t kTile = (int64_t)256 * 256;
   const int64_t n_groups = ((P + 127) / 128) * 4;
   auto panel = [&](char* set, int p) { return set + panel_offset_bytes(n_groups, p); };
-  FinishJobs jobs{};
+  struct { FinishJob j[kMaxFinishJobs]; int n; } jobs{};
   WgradJobs wj{};
   int fin_tiles[kMaxWgradJobs], fin_rows[kMaxWgradJobs];   // the finish jobs of product p's partial tiles / row sums (-1: none)
   bool overflow = false;
@@ -201,16 +226,11 @@ int nsr::chain_weight_grads(hipStream_t st, const Work& k, int64_t P, int64_t n_
     wj.j[pj].w.row_sums = k.row_part;          // placeholder, like `partial`
     fin_rows[pj] = finish(1, dst, rows, 1, nullptr, 0, 0);
   };
-  // the two head streams: 4 slices per CU (round 6).  With one 256-thread workgroup per CU (rounds 3-5: `sp` slices) a CU had
-  // 4-16 KiB of loads in flight and the streams ran at 1.5-2.3 TB/s (28 + 21 us coarse, 44 + 31 us fine: 4 % of the step);
-  // the slot the partials go to holds sp x 256 x 256 floats, a slice writes 384 or 256
-  const int64_t n_pg = P / 32;
-  const int hs = (int)(n_pg < 1024 ? (n_pg < 1 ? 1 : n_pg) : 1024);
-  const int64_t per = (n_pg + hs - 1) / hs;
+  // the two head streams (panel_wsums): the slot the partials go to holds sp x 256 x 256 floats, a slice writes 384 or 256
+  int hs = 0;
   // rgb head: d_rgb_pre^T relu(zcc), a stream over the panel; its bias from the per-ray partials of composite_bwd_kernel
   float* part = k.slots;
-  hipLaunchKernelGGL((panel_wsums_kernel<128, 3>), dim3(hs), dim3(256), 0, st, panel(k.kept.zpan, 9), P, k.d4, 4, per, part);
-  NSR_CHECK_LAUNCH();
+  NSR_TRY(panel_wsums(st, 128, 3, panel(k.kept.zpan, 9), P, k.d4, 4, part, &hs));
   finish(1, g[kRgbW], 3 * 128, 1, part, hs, 0);
   finish(2, g[kRgbB], 3, 1, k.bias_part, (int)n_rays, 4);
   // dir_encoding: dzc^T [g | de]
@@ -219,8 +239,7 @@ int nsr::chain_weight_grads(hipStream_t st, const Work& k, int64_t P, int64_t n_
   // xyz_encoding_final: dg^T relu(z8); sigma: d_sigma^T relu(z8)
   bias(product(8, 7, g[kFinalW], 256, 0, 256, 256, kW, 0), g[kFinalB], kW);
   part = k.slots + sp * kTile;
-  hipLaunchKernelGGL((panel_wsums_kernel<256, 1>), dim3(hs), dim3(256), 0, st, panel(k.kept.zpan, 7), P, k.d4 + 3, 4, per, part);
-  NSR_CHECK_LAUNCH();
+  NSR_TRY(panel_wsums(st, 256, 1, panel(k.kept.zpan, 7), P, k.d4 + 3, 4, part, &hs));
   finish(1, g[kSigmaW], 256, 1, part, hs, 0);
   finish(2, g[kSigmaB], 1, 1, k.bias_part + 3, (int)n_rays, 4);
   // trunk layers 8..1: dz_L^T (input of layer L); layers 1 and 5 read the encoded position (panel 10, 64 rows in register order)
@@ -256,7 +275,5 @@ int nsr::chain_weight_grads(hipStream_t st, const Work& k, int64_t P, int64_t n_
   if (next_big > k.slots + kChainSlots * sp * kTile || next_row > k.row_part + (int64_t)kChainRowSlots * sp * 256)
     return NSR_ERR_WORKSPACE;   // cannot happen (see `want`)
   NSR_TRY(wgrad_jobs_f16(wj, n_wg, st));
-  hipLaunchKernelGGL(finish_jobs_kernel, dim3(256, jobs.n), dim3(256), 0, st, jobs);
-  NSR_CHECK_LAUNCH();
-  return NSR_OK;
+  return finish_jobs(st, jobs.j, jobs.n);
 }

@@ -197,6 +197,24 @@ NSR_INTERNAL int net_forward(hipStream_t st, const Shape& S, const float* rays, 
 // backward of the network from k.d4 (composite_bwd's rows); g: its 2 D + 8 gradient tensors
 NSR_INTERNAL int net_backward(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, const Work& k, int64_t P,
                               float* const* g, int acc, int stop_grad);
+// ---- nsr_train_gemm.hip: the launchers of the reduction and placement kernels behind the layer-by-layer products
+// dst[(r0 + i) * dst_ld + c0 + j] = src[i * src_ld + col0 + j], i < rows, j < cols (transpose: dst[(r0 + j) * dst_ld + c0 + i]):
+// a copy of bits
+NSR_INTERNAL int place(hipStream_t st, float* dst, int dst_ld, int r0, int c0, const float* src, int src_ld, int rows, int cols,
+                       int col0, int transpose);
+// d4 (P, 4) = (d rgb_pre 0..2, d sigma) -> drgb (P, 32) = [d rgb_pre | 0], gsig[p * ldg + 0 .. 32) = [d sigma | 0]
+NSR_INTERNAL int scatter_heads(hipStream_t st, const float* d4, int64_t P, float* drgb, float* gsig, int64_t ldg);
+// bias_grad[c] (+)= sum over the n_tiles rows of col_tiles (n_tiles, N) of column c, c < n_bias (0: N), summed in double;
+// scratch: 64 * N doubles behind the n_tiles * N tile sums
+NSR_INTERNAL int tile_sums(hipStream_t st, float* col_tiles, int64_t n_tiles, int N, int n_bias, float* bias_grad, int acc);
+// dst[i * dst_ld + dc0 + j] (+)= scale * sum_z partial[z * stride + (pr0 + i) * p_ld + pc0 + j], i < rows, j < cols, z < splits;
+// summed in double, rows * cols < 2^31
+NSR_INTERNAL int reduce_place(hipStream_t st, float* dst, int dst_ld, int dc0, int rows, int cols, const float* partial,
+                              int splits, int p_ld, int pr0, int pc0, int accumulate, float scale, int64_t stride);
+// dst[c] (+)= sum over the P rows of src[r * ld + col0 + c], c < cols <= 4 (more: NSR_ERR_INVALID_ARG), summed in double;
+// `scratch`: >= 256 * 4 doubles (the split-K partial buffer is free between two weight gradients)
+NSR_INTERNAL int colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, float* dst, int accumulate,
+                        float* scratch);
 // ---- nsr_train.hip: the launchers of the kernels between the rendered colours and the network's backward
 // compositing backward: (P, 4) rows d4 = (d rgb_pre 0..2, d sigma) of R rays x N samples (N <= 256, else NSR_ERR_UNSUPPORTED);
 // `white`: the training option word; gmax (10 words, cleared), bias_part (R, 4), g_depth (R), g_opacity (R), g_weights (R, N)
@@ -218,6 +236,28 @@ NSR_INTERNAL int lr_loss(hipStream_t st, const float* comp, const float* target,
 NSR_INTERNAL int loss_finish(hipStream_t st, const double* block_sums, int n, double scale, float lambda, float* losses, int slot,
                              double* carry, float lambda_var, float lambda_dvar, float* var_losses);
 // ---- nsr_train_wgrad.hip: weight and bias gradients of the chain path from the panels
+// reads k.dpan, k.kept.zpan (both zero-padded to 128 points), k.gmax, k.pscale, k.d4, k.bias_part; scratch: k.slots, k.row_part
 NSR_INTERNAL int chain_weight_grads(hipStream_t st, const Work& k, int64_t P, int64_t n_rays, float* const* g, int acc);
+// a head's weight gradient as a stream over one R-row forward panel: partial[z * NW * R + c * R + row] = sum over the points p of
+// slice z of w[p * w_stride + c] * panel[p][row], c < NW.  (R, NW) = (128, 3) or (256, 1), else NSR_ERR_UNSUPPORTED.  *slices
+// = min(max(P / 32, 1), 1024) slices of ceil(P / 32 / slices) point groups each; a slice behind the last group writes zeros
+NSR_INTERNAL int panel_wsums(hipStream_t st, int R, int NW, const char* panel, int64_t P, const float* w, int w_stride,
+                             float* partial, int* slices);
+// One second pass of the chain path's gradients (finish_jobs_kernel), sums in double:
+//   kind 0: dst[i * dst_ld + dc0 + j] (+)= scale * sum_z partial[z * stride + i * p_ld + col(j)], i < rows, j < cols, z < splits;
+//           col = enc_panel_row(enc_rows, .): 0 identity, 1 / 2 the panel row of column j of the encoded position / direction
+//   kind 1: dst[i] (+)= scale * sum_z partial[z * rows + i], i < rows (cols = 1)
+//   kind 2: dst[i] (+)= sum_z partial[z * stride + i], i < rows <= 4
+struct FinishJob {
+  float* dst;
+  const float* partial;
+  int64_t stride;
+  int kind, dst_ld, dc0, rows, cols, splits, p_ld, accumulate, enc_rows;
+  float scale;
+};
+constexpr int kMaxFinishJobs = 32;
+// n jobs (1 .. kMaxFinishJobs, else NSR_ERR_INVALID_ARG) in ONE launch.  NSR_ERR_UNSUPPORTED before anything is launched where a
+// job exceeds its 65,536 threads: kind 0, and kind 1 with splits <= 64, need rows * cols <= 65,536; kind 2 rows <= 4
+NSR_INTERNAL int finish_jobs(hipStream_t st, const FinishJob* jobs, int n);
 
 }  // namespace nsr

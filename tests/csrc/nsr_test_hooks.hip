@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include "nsr_gemm.h"
 #include "nsr_f16x3_core.h"
+#include "nsr_train_work.h"
 
 #define NSR_TEST_API extern "C" __attribute__((visibility("default")))
 
@@ -33,7 +34,7 @@ NSR_TEST_API int nsr_test_wgrad_jobs(const WgradJobs* jobs, int n_wg, void* stre
 }
 
 // sizeof / offsetof of the argument structs, in declaration order, so that the ctypes mirrors are checked and not trusted:
-// which = 0 GemmArgs, 1 GemmF16Args, 2 WgradArgs, 3 WgradJob, 4 WgradJobs, 5 ConvGather.  out[0] = sizeof, out[1..] = the
+// which = 0 GemmArgs, 1 GemmF16Args, 2 WgradArgs, 3 WgradJob, 4 WgradJobs, 5 ConvGather, 6 FinishJob (nsr_train_work.h).  out[0] = sizeof, out[1..] = the
 // offsets; returns the number of entries (written up to cap), -1 for an unknown struct.
 NSR_TEST_API int nsr_test_layout(int which, int64_t* out, int cap) {
   int64_t v[32];
@@ -79,6 +80,13 @@ NSR_TEST_API int nsr_test_layout(int which, int64_t* out, int cap) {
       NSR_SZ(ConvGather);
       NSR_OFF(ConvGather, cin); NSR_OFF(ConvGather, Hs); NSR_OFF(ConvGather, Ws); NSR_OFF(ConvGather, Ho); NSR_OFF(ConvGather, Wo);
       NSR_OFF(ConvGather, stride); NSR_OFF(ConvGather, up);
+      break;
+    case 6:
+      NSR_SZ(FinishJob);
+      NSR_OFF(FinishJob, dst); NSR_OFF(FinishJob, partial); NSR_OFF(FinishJob, stride); NSR_OFF(FinishJob, kind);
+      NSR_OFF(FinishJob, dst_ld); NSR_OFF(FinishJob, dc0); NSR_OFF(FinishJob, rows); NSR_OFF(FinishJob, cols);
+      NSR_OFF(FinishJob, splits); NSR_OFF(FinishJob, p_ld); NSR_OFF(FinishJob, accumulate); NSR_OFF(FinishJob, enc_rows);
+      NSR_OFF(FinishJob, scale);
       break;
     default:
       return -1;

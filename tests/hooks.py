@@ -1,6 +1,6 @@
 """Loader of the test-hook library (ab/libnsr_testhooks.so = the product's objects + tests/csrc/nsr_test_hooks.hip, built by
 ``nerf_sr_amd.build.build_test_hooks`` / ``__graft_entry__.build()``) and ctypes mirrors of the library-internal argument
-structs of csrc/nsr_gemm.h.  The mirrors are checked against the C++ structs (``nsr_test_layout``) when the library is
+structs of csrc/nsr_gemm.h (and FinishJob of csrc/nsr_train_work.h).  The mirrors are checked against the C++ structs (``nsr_test_layout``) when the library is
 loaded: a field added or moved in the header fails every test that uses the hooks instead of silently shifting arguments.
 
 There is no fallback: without the library (and without hipcc to make it) ``load()`` raises and the tests that need it fail.
@@ -62,7 +62,15 @@ class WgradJobs(Structure):
                 ("per_wg", c_int64)]
 
 
-MIRRORS = {0: GemmArgs, 1: GemmF16Args, 2: WgradArgs, 3: WgradJob, 4: WgradJobs, 5: ConvGather}   # nsr_test_layout's `which`
+class FinishJob(Structure):      # csrc/nsr_train_work.h: one second pass of finish_jobs
+    _fields_ = [("dst", c_void_p), ("partial", c_void_p), ("stride", c_int64)] + \
+               [(n, c_int) for n in ("kind", "dst_ld", "dc0", "rows", "cols", "splits", "p_ld", "accumulate", "enc_rows")] + \
+               [("scale", c_float)]
+
+
+MAX_FINISH_JOBS = 32             # kMaxFinishJobs: 32 jobs are launched, 33 refused (tests/test_gpu_train_finish_jobs.py)
+# nsr_test_layout's `which`
+MIRRORS = {0: GemmArgs, 1: GemmF16Args, 2: WgradArgs, 3: WgradJob, 4: WgradJobs, 5: ConvGather, 6: FinishJob}
 
 SIGNATURES = {
     "nsr_test_gemm": (c_int, [POINTER(GemmArgs), c_void_p]),
@@ -113,6 +121,17 @@ SIGNATURES = {
     "nsr_test_encode_arch": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_int, POINTER(c_void_p), c_int, c_int64, c_int,
                                      c_void_p]),
     "nsr_test_f16x3_train_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int] + [c_void_p] * 5),
+    # tests/csrc/nsr_test_hooks_reduce.hip (the last argument of each but the scratch query is the stream)
+    "nsr_test_place": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "nsr_test_scatter_heads": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "nsr_test_colsum": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "nsr_test_tile_sums": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "nsr_test_reduce_place": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                      c_int64, c_void_p]),
+    "nsr_test_panel_wsums": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_void_p, POINTER(c_int), c_void_p]),
+    "nsr_test_finish_jobs": (c_int, [POINTER(FinishJob), c_int, c_void_p]),
+    "nsr_test_chain_weight_grads": (c_int, [c_void_p] * 8 + [c_int64, c_int64, POINTER(c_void_p), c_int, c_void_p]),
+    "nsr_test_chain_weight_grads_scratch": (c_int, [c_int64, POINTER(c_int64)]),
 }
 
 # nsr::GemmF16Route (csrc/nsr_gemm.h): the instantiation gemm_f16x3 launches

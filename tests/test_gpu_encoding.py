@@ -22,6 +22,7 @@ import torch
 
 from tests import encoding_ref as enc
 from tests import hooks
+from tests.panel_layout import dircol as _dircol, panel_rows as _panel_rows, pecol as _pecol   # the panels' row order
 
 pytestmark = pytest.mark.gpu
 
@@ -252,43 +253,6 @@ def test_onehot_columns(ops, precision, place):
 # ---------------------------------------------------------------------------------------------------------------------
 # (e) the TRAIN forward's encoding panels
 # ---------------------------------------------------------------------------------------------------------------------
-def _pecol(t, h):                # csrc/nsr_mlp_layout.h: the column register t of lane half h holds (None: padding)
-    if t == 0:
-        return 0 if h == 0 else 2
-    if t == 1:
-        return 1 if h == 0 else None
-    return 3 + 30 * h + (t - 2)
-
-
-def _dircol(t, h):
-    if t == 0:
-        return 0 if h == 0 else 2
-    if t == 1:
-        return 1 if h == 0 else None
-    if t >= 14:
-        return None
-    return 3 + 12 * h + (t - 2)
-
-
-def _enc_row(t, h):              # csrc/nsr_panels.h
-    return 32 * (t >> 4) + 16 * ((t >> 3) & 1) + 8 * ((t >> 2) & 1) + 4 * h + (t & 3)
-
-
-def _panel_rows(rows, n_regs, col_of, col0):
-    """(P, 64) float16: the encoding panel's rows in enc_row() order; rows no register maps to stay zero."""
-    out = np.zeros((rows.shape[0], 64), dtype=np.float16)
-    used = set()
-    for t in range(n_regs):
-        for h in (0, 1):
-            c = col_of(t, h)
-            r = _enc_row(t, h)
-            assert r not in used
-            used.add(r)
-            if c is not None:
-                out[:, r] = rows[:, col0 + c].astype(np.float16)
-    return out, used
-
-
 @pytest.mark.parametrize("shape", enc.SHAPES, ids=[f"{R}x{N}" for R, N in enc.SHAPES])
 @pytest.mark.parametrize("stride", enc.STRIDES)
 def test_train_forward_panels(ops, hk, shape, stride):
