@@ -206,8 +206,26 @@ def build_test_hooks(force: bool = False, verbose: bool = True) -> str:
 #    SGPRs with v_readlane, a VMEM read of a VALU-written SGPR needs five wait states, and the hazard pass cannot see through
 #    inline asm: every global_load_lds / global_store inside an asm block must read a pair written by an s_mov_b64 inside the
 #    SAME block.
-ISA_UNITS = ["nsr_mlp_f16.hip", "nsr_train_chain.hip", "nsr_gemm_f16.hip", "nsr_wgrad_f16.hip", "nsr_mlp.hip", "nsr_mlp_h1.hip",
-             "nsr_mlp_arch_f16.hip"]
+# Both rules live in csrc/nsr_lds_dma.h, the one file with such statements (tests/test_lds_primitives_cpu.py), so the units
+# to check are the ones whose #include "..." closure reaches it.
+ISA_HEADER = "nsr_lds_dma.h"
+
+
+def include_closure(path: str) -> set:
+    """Paths of the file and of everything it reaches through #include "..." lines (text scan, no preprocessor)."""
+    import re
+    seen, todo = set(), [os.path.normpath(path)]
+    while todo:
+        p = todo.pop()
+        if p in seen or not os.path.exists(p):
+            continue
+        seen.add(p)
+        with open(p) as f:
+            todo += [os.path.normpath(os.path.join(os.path.dirname(p), inc)) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), re.M)]
+    return seen
+
+
+ISA_UNITS = [u for u, _ in UNITS if os.path.join(CSRC, ISA_HEADER) in include_closure(os.path.join(CSRC, u))]
 ISA_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-S",
              "--cuda-device-only"]
 

@@ -3,11 +3,13 @@
 // per chunk, fragments software-pipelined ahead of the MFMAs.  See nsr_mlp_f16.hip for the arithmetic.
 #pragma once
 #include "nsr_common.h"
+#include "nsr_lds_dma.h"
 #include "nsr_mlp_layout.h"
 #include "nsr_panels.h"
 
 using namespace nsr;
 using namespace nsr::hx;
+using namespace nsr::dma;
 
 // NSR_ABL_*: ablation switches for the measurement ladder in profiles/r1_f16x3_pmc.txt (scripts/ablate.sh builds
 // variant libraries with them); never defined in the product build.
@@ -20,11 +22,6 @@ using namespace nsr::hx;
 // weights and biases enter the stream multiplied by 2^6 (see the header); |w| < 1023 stays inside fp16
 constexpr float kWScale = 64.0f, kWInvScale = 1.0f / 64.0f;
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ unsigned pack_hl(float a, float b, int part) {
   _Float16 ha = (_Float16)a, hb = (_Float16)b;               // round to nearest even
   if (part) {
@@ -33,72 +30,6 @@ __device__ __forceinline__ unsigned pack_hl(float a, float b, int part) {
   }
   return (unsigned)__builtin_bit_cast(unsigned short, ha) | ((unsigned)__builtin_bit_cast(unsigned short, hb) << 16);
 }
-
-// ---------------------------------------------------------------------------
-// kernel
-// ---------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
-// LDS byte address (32-bit) of a __shared__ object
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(size_t)((const __attribute__((address_space(3))) char*)p);
-}
-
-// Weight DMA (global -> LDS, 64 lanes x 16 B) issued from inline asm: wave-uniform 64-bit base in SGPRs
-// + one 32-bit lane offset.  Why not __builtin_amdgcn_global_load_lds: hipcc's waitcnt insertion treats
-// an in-flight LDS-DMA as a FLAT-like event and from then on waits lgkmcnt(0) — i.e. for the fragment
-// loads issued two instructions earlier — before every MFMA group.  The asm form is invisible to that
-// pass; its completion is waited for by hand (dma_drain) right before the barrier that publishes the
-// chunk.  OFF (0..3072) is added to BOTH the global and the LDS address, so one (base, M0) pair serves
-// four consecutive 1 KiB pieces.  M0 is written in the same statement that consumes it (hipcc reserves
-// M0 and uses it nowhere else in this kernel).
-// The base is copied into a scratch SGPR pair INSIDE the statement: when hipcc has spilled the descriptor to VGPR lanes
-// it restores it with v_readlane right in front of the statement, and a VMEM instruction that reads a VALU-written SGPR
-// needs five wait states which hipcc's hazard pass cannot see through inline asm (round 4: a persistent-loop build read
-// a stale pair and faulted).  An SALU read is interlocked, and the copy doubles as the wait state after the M0 write.
-// M0 is a reserved register for hipcc (it never allocates it: naming it in a clobber list is a warning), so the pieces
-// 4q+1 .. 4q+3 of a 4 KiB group reuse the M0 piece 4q wrote (glds16_keep_asm).
-template <int OFF>
-__device__ __forceinline__ void glds16_asm(const char* base_uniform, unsigned lane_off, unsigned lds_dst_uniform) {
-  unsigned long long tmp;
-  asm volatile(
-      "s_mov_b32 m0, %3\n\t"
-      "s_mov_b64 %0, %2\n\t"
-      "global_load_lds_dwordx4 %1, %0 offset:%4"
-      : "=&s"(tmp)
-      : "v"(lane_off), "s"(base_uniform), "s"(lds_dst_uniform), "i"(OFF)
-      : "memory");
-}
-// a further piece of the 4 KiB group whose first piece set M0 (same base, same M0)
-template <int OFF>
-__device__ __forceinline__ void glds16_keep_asm(const char* base_uniform, unsigned lane_off) {
-  unsigned long long tmp;
-  asm volatile(
-      "s_mov_b64 %0, %2\n\t"
-      "global_load_lds_dwordx4 %1, %0 offset:%3"
-      : "=&s"(tmp)
-      : "v"(lane_off), "s"(base_uniform), "i"(OFF)
-      : "memory");
-}
-// two consecutive pieces (OFF, OFF + 1024) with ONE M0 write
-template <int OFF>
-__device__ __forceinline__ void glds16x2_asm(const char* base_uniform, unsigned lane_off, unsigned lds_dst_uniform) {
-  unsigned long long tmp;
-  asm volatile(
-      "s_mov_b32 m0, %3\n\t"
-      "s_mov_b64 %0, %2\n\t"
-      "global_load_lds_dwordx4 %1, %0 offset:%4\n\t"
-      "global_load_lds_dwordx4 %1, %0 offset:%5"
-      : "=&s"(tmp)
-      : "v"(lane_off), "s"(base_uniform), "s"(lds_dst_uniform), "i"(OFF), "i"(OFF + 1024)
-      : "memory");
-}
-__device__ __forceinline__ void dma_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// vector memory operations complete in issue order: with N younger operations (loads / stores issued AFTER the last DMA
-// piece that must have landed) allowed to stay in flight
-template <int N>
-__device__ __forceinline__ void dma_drain_but() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
 
 // ---------------------------------------------------------------------------
 // weight-stream loader: 3-slot LDS ring, the chunk at sequence position j lives in slot j % 3.
@@ -201,7 +132,7 @@ template <int YOUNGER = 0, bool PREPARE = true>
 __device__ __forceinline__ void loader_publish(Loader& ld, const ChunkRef& c2, bool strict = false) {
 #ifndef NSR_ABL_NO_DRAIN
   if (YOUNGER > 0 && strict) dma_drain();
-  else dma_drain_but<YOUNGER>();
+  else dma_wait<YOUNGER>();
 #endif
 #ifndef NSR_ABL_NO_BARRIER
 #ifndef NSR_ABL_FENCED_BARRIER
@@ -215,16 +146,6 @@ __device__ __forceinline__ void loader_publish(Loader& ld, const ChunkRef& c2, b
 #endif
 #endif
   if (PREPARE) loader_prepare_dma(ld, c2, ld.slot_free);
-}
-
-__device__ __forceinline__ h8 as_h8(const u32x4& v) { return __builtin_bit_cast(h8, v); }
-__device__ __forceinline__ const u32x4* lds_vec(unsigned byte_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (const u32x4*)(const __attribute__((address_space(3))) u32x4*)(size_t)byte_addr;
-#else
-  (void)byte_addr;
-  return nullptr;   // host pass of the single-source compile; never executed
-#endif
 }
 
 struct Acc {
@@ -413,11 +334,9 @@ __device__ __forceinline__ void unit_store(const u32x4& v, const char* blk, unsi
 #ifdef NSR_ABL_FWD_NO_STORE   // ablation (scripts/): how much of the TRAIN forward kernel is its panel writes
   if (voff != 0xffffffffu) return;
 #endif
-  // base through an in-statement SALU copy: see glds16_asm (VALU-restored SGPR -> VMEM hazard behind inline asm).  Cache
-  // policy: write-once streams far larger than the caches, so non-temporal (round 2, same box, 2,048-ray training step:
-  // default policy 7.51-7.54 ms, "sc0 sc1" 7.38 ms, "nt" 6.50 ms)
-  unsigned long long tmp;
-  asm volatile("s_mov_b64 %0, %3\n\tglobal_store_dwordx4 %1, %2, %0 offset:%4 nt" : "=&s"(tmp) : "v"(voff), "v"(v), "s"(blk), "n"(U * 1024) : "memory");
+  // Cache policy: write-once streams far larger than the caches, so non-temporal (round 2, same box, 2,048-ray training
+  // step: default policy 7.51-7.54 ms, "sc0 sc1" 7.38 ms, "nt" 6.50 ms)
+  gstore16_nt_asm<U * 1024>(v, blk, voff);
 }
 
 // Sign panels: one bit per pre-activation ([z < 0], i.e. "the ReLU zeroes it"; +0.0 counts as active) of the layers whose
@@ -437,6 +356,5 @@ __device__ __forceinline__ void sign_push(unsigned& bits, float v) {
   asm volatile("v_alignbit_b32 %0, %0, %1, 31" : "+v"(bits) : "v"(v));
 }
 __device__ __forceinline__ void sign_store(unsigned bits, const unsigned* blk, unsigned lane4) {
-  unsigned long long tmp;
-  asm volatile("s_mov_b64 %0, %3\n\tglobal_store_dword %1, %2, %0" : "=&s"(tmp) : "v"(lane4), "v"(bits), "s"(blk) : "memory");
+  gstore4_asm(bits, blk, lane4);
 }

@@ -13,13 +13,12 @@
 #include "nsr_gemm.h"
 #include "../../include/nsr_train.h"
 #include "nsr_gemm_epilogue.h"
+#include "nsr_lds_dma.h"
 
 namespace nsr {
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace dma;
 
 constexpr int kTM = 128, kTK = 32;   // row tile; default K tile (the kernels pad LDS rows by 8 halves)
 
@@ -460,33 +459,9 @@ gemm_f16x3_kernel(GemmF16Args a, int n_col_tiles, int64_t n_blocks) {
 
 
 // ---------------------------------------------------------------------------------------------------------------
-// LDS-DMA helpers of conv_halo_kernel below (the data movement of the inference MLP kernel, nsr_mlp_f16.hip): one piece =
-// 64 lanes x 16 B, global -> LDS at M0 + 16 lane, counted by vmcnt like any load.
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void stream_dma_piece(const char* base_uniform, unsigned lane_off, unsigned lds_dst_uniform) {
-  unsigned long long tmp;     // in-statement copy of the base: see nsr_f16x3_core.h (VALU-restored SGPR -> VMEM hazard)
-  asm volatile(
-      "s_mov_b32 m0, %3\n\t"
-      "s_mov_b64 %0, %2\n\t"
-      "global_load_lds_dwordx4 %1, %0"
-      : "=&s"(tmp)
-      : "v"(lane_off), "s"(base_uniform), "s"(lds_dst_uniform)
-      : "memory");
-}
-template <int N>
-__device__ __forceinline__ void stream_vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
-__device__ __forceinline__ const u32x4* stream_lds(unsigned byte_addr) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return (const u32x4*)(const __attribute__((address_space(3))) u32x4*)(size_t)byte_addr;
-#else
-  (void)byte_addr;
-  return nullptr;
-#endif
-}
-__device__ __forceinline__ h8 stream_h8(const u32x4& v) { return __builtin_bit_cast(h8, v); }
-
-// ---------------------------------------------------------------------------------------------------------------
-// Stride-1 3 x 3 convolutions with the input patch resident in LDS.
+// Stride-1 3 x 3 convolutions with the input patch resident in LDS.  Data movement of the inference MLP kernel
+// (nsr_mlp_f16.hip) with the primitives of nsr_lds_dma.h: one piece (glds16_asm<0>) = 64 lanes x 16 B, global -> LDS at
+// M0 + 16 lane, counted by vmcnt like any load (dma_wait).
 //
 // The kernels above fetch an activation once per tap: nine times.  At one wave per SIMD and the whole register file as
 // the accumulator (256 x 256 or 512 x 128 outputs per workgroup) that is 21-32 B per CU and clock from L2 with the
@@ -592,7 +567,7 @@ conv_halo_kernel(GemmF16Args a, int n_col_tiles, int64_t n_blocks) {
   const int oy0 = (ti / tiles_x) * Geo::TH, ox0 = (ti % tiles_x) * Geo::TW;
   const int cin = a.conv.cin, ncc = cin / 16;
   const int n_img = MULTI ? (int)(g.M / ((int64_t)Ho * Wo)) : 0;
-  const unsigned lds0 = (unsigned)(size_t)((const __attribute__((address_space(3))) unsigned char*)lds);
+  const unsigned lds0 = lds_addr(lds);
   const unsigned ring0 = lds0 + (unsigned)(Geo::PATCH0 + Geo::PATCH1);
   const unsigned lane16 = (unsigned)lane * 16u;
 
@@ -663,7 +638,7 @@ conv_halo_kernel(GemmF16Args a, int n_col_tiles, int64_t n_blocks) {
   auto patch_piece = [&](int reg, int cc, int i) {
     const int c = cc >= ncc ? cc - ncc : cc;
     const unsigned src = (S == 2 && reg) ? psrc1[S == 1 ? 0 : i] : psrc0[i];
-    stream_dma_piece(a_base, src + (unsigned)c * 32u, lds0 + (unsigned)reg * Geo::PATCH0 + (unsigned)(4 * i + wave) * 1024u);
+    glds16_asm<0>(a_base, src + (unsigned)c * 32u, lds0 + (unsigned)reg * Geo::PATCH0 + (unsigned)(4 * i + wave) * 1024u);
   };
 
   // ---- B: piece P = PB wave + i of a k-step = column block P / 2, plane P & 1 = one contiguous KiB of the stream-ordered
@@ -673,7 +648,7 @@ conv_halo_kernel(GemmF16Args a, int n_col_tiles, int64_t n_blocks) {
     const int c = cc >= ncc ? cc - ncc : cc;
     const int P = Geo::PB * wave + i;
     const char* src = b_base + ((int64_t)(P >> 1) * (9 * ncc) + c * 9 + tap) * 2048 + (P & 1) * 1024;
-    stream_dma_piece(src, lane16, ring0 + (unsigned)((cc * 9 + j) & 3) * Geo::SLOT + (unsigned)P * 1024u);
+    glds16_asm<0>(src, lane16, ring0 + (unsigned)((cc * 9 + j) & 3) * Geo::SLOT + (unsigned)P * 1024u);
   };
 
   f32x16 acc[BM][1][BN];
@@ -693,8 +668,8 @@ conv_halo_kernel(GemmF16Args a, int n_col_tiles, int64_t n_blocks) {
     for (int bi = 0; bi < BM; ++bi) {
       const unsigned e = e0[reg > 0 ? 1 : 0][bi] + (unsigned)Geo::eoff(j);
       const unsigned ad = pbuf + e * 64u + ((((unsigned)h) ^ ((e >> 2) & 3u)) << 4);
-      fh[bi] = stream_lds(ad)[0];
-      fl[bi] = stream_lds(ad ^ 32u)[0];
+      fh[bi] = lds_vec(ad)[0];
+      fl[bi] = lds_vec(ad ^ 32u)[0];
     }
   };
 
@@ -705,11 +680,11 @@ conv_halo_kernel(GemmF16Args a, int n_col_tiles, int64_t n_blocks) {
   for (int k = 0; k < 3; ++k)
 #pragma unroll
     for (int i = 0; i < Geo::PB; ++i) b_piece(0, k, Geo::wtap(k), i);
-  stream_vm_wait<0>();
+  dma_wait<0>();
   __syncthreads();
   a_frags(0, std::integral_constant<int, 0>{}, ah, al);
-  bh = stream_lds(ring0 + lane16)[0];
-  bl = stream_lds(ring0 + 1024u + lane16)[0];
+  bh = lds_vec(ring0 + lane16)[0];
+  bl = lds_vec(ring0 + 1024u + lane16)[0];
 
   auto kstep = [&](auto J_c, int cc) {
     constexpr int j = decltype(J_c)::value, tap = Geo::wtap(j);
@@ -740,22 +715,22 @@ conv_halo_kernel(GemmF16Args a, int n_col_tiles, int64_t n_blocks) {
         }
       }
       if (bj == BN / 2) {
-        stream_vm_wait<Geo::publish_wait(j)>();
+        dma_wait<Geo::publish_wait(j)>();
 #ifndef NSR_ABL_HALO_NO_BARRIER
         asm volatile("s_barrier" ::: "memory");
 #endif
       }
       const unsigned nxt = (bj < BN - 1 ? slot + (unsigned)(2 * (bj + 1)) * 1024u : slot_next) + lane16;
-      const u32x4 nbh = stream_lds(nxt)[0], nbl = stream_lds(nxt + 1024u)[0];
+      const u32x4 nbh = lds_vec(nxt)[0], nbl = lds_vec(nxt + 1024u)[0];
       if (bj == BN / 2) {
         if (j < 8) a_frags(cc, std::integral_constant<int, (j < 8 ? j + 1 : 0)>{}, nah, nal);
         else a_frags(cc + 1, std::integral_constant<int, 0>{}, nah, nal);
       }
 #pragma unroll
       for (int bi = 0; bi < BM; ++bi) {
-        acc[bi][0][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(stream_h8(al[bi]), stream_h8(bh), acc[bi][0][bj], 0, 0, 0);   // small terms first
-        acc[bi][0][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(stream_h8(ah[bi]), stream_h8(bl), acc[bi][0][bj], 0, 0, 0);
-        acc[bi][0][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(stream_h8(ah[bi]), stream_h8(bh), acc[bi][0][bj], 0, 0, 0);
+        acc[bi][0][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(al[bi]), as_h8(bh), acc[bi][0][bj], 0, 0, 0);   // small terms first
+        acc[bi][0][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(ah[bi]), as_h8(bl), acc[bi][0][bj], 0, 0, 0);
+        acc[bi][0][bj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(ah[bi]), as_h8(bh), acc[bi][0][bj], 0, 0, 0);
 #ifndef NSR_ABL_HALO_NO_BDMA
         if (bi == 0 && bj >= BN / 2) b_piece(cc + (j + 3) / 9, (j + 3) % 9, Geo::wtap((j + 3) % 9), bj - BN / 2);
 #endif
@@ -781,7 +756,7 @@ conv_halo_kernel(GemmF16Args a, int n_col_tiles, int64_t n_blocks) {
     kstep(std::integral_constant<int, 7>{}, cc);
     kstep(std::integral_constant<int, 8>{}, cc);
   }
-  stream_vm_wait<0>();     // the wrapped fetches of the last k-steps
+  dma_wait<0>();     // the wrapped fetches of the last k-steps
 
 #ifdef NSR_ABL_HALO_NO_EPILOGUE     // what the k-steps alone cost: every accumulator stays live, nothing is stored
   {

@@ -14,13 +14,12 @@
 //   * sigma (256->1) and rgb (128->3) heads are VALU dot products on the
 //     register-resident activations; bias enters as the accumulator init.
 #include "nsr_common.h"
+#include "nsr_lds_dma.h"
 #include "nsr_mlp_layout.h"
 #include "nsr_composite.h"
 
 using namespace nsr;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace nsr::dma;
 
 // ---------------------------------------------------------------------------
 // weight packing (device side gather into the fragment-ordered stream)
@@ -231,34 +230,8 @@ extern "C" int nsr_weights_set_gamma(void* packed_dev, int precision, int enable
 // ---------------------------------------------------------------------------
 // fused MLP kernel, fp32 MFMA
 // ---------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-
-// LDS byte address (32-bit) of a __shared__ object
-__device__ __forceinline__ unsigned lds_addr(const void* p) {
-  return (unsigned)(size_t)((const __attribute__((address_space(3))) char*)p);
-}
-
-// One wave-instruction: 64 lanes x 16 B, global -> LDS (dst = wave-uniform M0 + OFF + lane*16), issued from
-// inline asm with a wave-uniform 64-bit base + one 32-bit lane offset.  Why not
-// __builtin_amdgcn_global_load_lds: with an LDS-DMA in flight hipcc's waitcnt pass waits lgkmcnt(0) before
-// every MFMA group (see nsr_mlp_f16.hip); the asm form is invisible to it and is drained by hand
-// (dma_drain) right before the barrier that publishes the chunk.
-template <int OFF>
-__device__ __forceinline__ void glds16_asm(const char* base_uniform, unsigned lane_off, unsigned lds_dst_uniform) {
-  // base through an in-statement SALU copy (a VALU-restored SGPR feeding VMEM needs wait states hipcc cannot add inside
-  // inline asm): see nsr_f16x3_core.h
-  unsigned long long tmp;
-  asm volatile(
-      "s_mov_b32 m0, %3\n\t"
-      "s_mov_b64 %0, %2\n\t"
-      "global_load_lds_dwordx4 %1, %0 offset:%4"
-      : "=&s"(tmp)
-      : "v"(lane_off), "s"(base_uniform), "s"(lds_dst_uniform), "i"(OFF)
-      : "memory");
-}
-__device__ __forceinline__ void dma_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
+// The weights stream global -> LDS by DMA (glds16_asm, one wave-instruction = 64 lanes x 16 B to M0 + OFF + lane*16) and
+// are waited for by hand (dma_drain) right before the barrier that publishes the chunk: nsr_lds_dma.h.
 struct Stream {
   const float* base;   // packed stream
   int q;               // next chunk to CONSUME
@@ -496,7 +469,7 @@ mlp_fp32_kernel(const float* __restrict__ packed, const float* __restrict__ x, c
   if (p < P) nsr_raise(tail, flags);
   if (out && h == 0 && p < P) reinterpret_cast<float4*>(out)[p] = make_float4(rgb[0], rgb[1], rgb[2], sigma);
   if (NSC > 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no weight DMA may still be landing in the ring that is re-used below
+    dma_drain();   // no weight DMA may still be landing in the ring that is re-used below
     composite_tile<(NSC > 0 ? NSC : 64)>(ring, h == 0, wave, m, lane, make_float4(rgb[0], rgb[1], rgb[2], sigma), zv[pc], P / (NSC > 0 ? NSC : 1), co, (int64_t)blockIdx.x);
   }
 }

@@ -9,12 +9,12 @@
 // a chunk carries TWO 32-feature output blocks per k-step instead of the (hi, lo) halves of one, so each k-step
 // is two independent MFMAs sharing the B operand and the stream keeps the same 2-pieces-per-k-step shape.
 #include "nsr_common.h"
+#include "nsr_lds_dma.h"
 #include "nsr_mlp_layout.h"
-#include "nsr_mlp_stream.h"
 #include "nsr_mlp_encode.h"
 
 using namespace nsr;
-using namespace nsr::stream;
+using namespace nsr::dma;
 
 namespace h1 {
 
@@ -70,6 +70,70 @@ NSR_HD Chunk chunk_info(int q) {
     c.tensor = 18; c.nb0 = 2 * (q - 34); c.steps = 18; c.piece0 = kDirPiece0 + 37 * (q - 34); c.pieces = 37;
   }
   return c;
+}
+
+// ---- weight-stream loader (the 8-wave ring; the f16x3 kernels have their own in nsr_f16x3_core.h, with measured differences:
+// pieces that keep M0, a bare-barrier publish point, 32-bit stream offsets) ----------------------------------------------
+// a chunk of the stream as this wave sees it: where it starts, how many 1 KiB pieces it has, and the
+// contiguous 1/NW of it this wave moves (NW = waves per workgroup; all wave-uniform, SGPRs)
+struct ChunkRef {
+  int piece0, pieces;
+  int first, count;
+};
+template <int NW>
+__device__ __forceinline__ ChunkRef make_ref(int piece0, int pieces, int wave) {
+  static_assert(NW == 4 || NW == 8, "4 or 8 waves per workgroup");
+  constexpr int sh = NW == 4 ? 2 : 3;
+  ChunkRef c;
+  c.piece0 = piece0;
+  c.pieces = pieces;
+  c.first = (wave * pieces) >> sh;
+  c.count = (((wave + 1) * pieces) >> sh) - c.first;
+  return c;
+}
+
+// 3-slot LDS ring, chunk j in slot j % 3.  Protocol per wave while chunk j is consumed: at the publish point
+// wait for the own DMA of chunk j+1, barrier (chunk j+1 published, chunk j-1's slot free), then fetch chunk
+// j+2 into that slot; the last k-steps prefetch chunk j+1's first fragments, so nothing stalls at a boundary.
+struct Loader {
+  const float* stream;   // packed blob viewed as 32-bit words
+  int wave;
+  unsigned lane_off;     // lane * 16
+  unsigned slot_cur, slot_next, slot_free;
+  const char* dma_base;
+  unsigned dma_lds;
+  int dma_count;
+};
+__device__ __forceinline__ void loader_prepare_dma(Loader& ld, const ChunkRef& c, unsigned slot_lds) {
+  ld.dma_count = c.count;
+  ld.dma_base = reinterpret_cast<const char*>(ld.stream) + (size_t)(c.piece0 + c.first) * 1024;
+  ld.dma_lds = slot_lds + (unsigned)c.first * 1024u;
+}
+// issue this wave's DMA piece number i of the chunk being fetched (no-op past its end); every wave owns at
+// least MINP pieces of every chunk (32-piece minimum chunk / waves), so the first MINP issues are branch-free
+template <int MINP>
+__device__ __forceinline__ void loader_issue(const Loader& ld, int i) {
+  if (i < MINP || i < ld.dma_count) {
+    const char* base = ld.dma_base + (i >> 2) * 4096;
+    const unsigned dst = ld.dma_lds + (unsigned)(i >> 2) * 4096u;
+    switch (i & 3) {
+      case 0: glds16_asm<0>(base, ld.lane_off, dst); break;
+      case 1: glds16_asm<1024>(base, ld.lane_off, dst); break;
+      case 2: glds16_asm<2048>(base, ld.lane_off, dst); break;
+      default: glds16_asm<3072>(base, ld.lane_off, dst); break;
+    }
+  }
+}
+__device__ __forceinline__ void loader_advance(Loader& ld) {
+  const unsigned t = ld.slot_cur;
+  ld.slot_cur = ld.slot_next;
+  ld.slot_next = ld.slot_free;
+  ld.slot_free = t;
+}
+__device__ __forceinline__ void loader_publish(Loader& ld, const ChunkRef& c2) {
+  dma_drain();
+  __syncthreads();
+  loader_prepare_dma(ld, c2, ld.slot_free);
 }
 
 __device__ __forceinline__ ChunkRef mkref(int piece0, int pieces, int wave) { return make_ref<kWaves>(piece0, pieces, wave); }
@@ -161,7 +225,6 @@ __global__ void __launch_bounds__(256) pack_kernel(PackPtrs w, unsigned* __restr
 }
 
 // ---- kernel ----------------------------------------------------------------------------------------------
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 
 template <bool BF>

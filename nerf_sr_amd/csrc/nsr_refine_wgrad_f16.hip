@@ -8,7 +8,7 @@
 // owns a 128 (cout) x 128 (one tap, 128 input channels) tile of dW and one SLICE of the pixels.  Per K tile of 32 pixels it
 // stages the 32 dZ rows and the 32 tap-shifted input rows (the gather of nsr_gemm_f16.hip's ConvGather, restated for one tap)
 // as fp16 (hi, lo) planes [pixel][128 + 32 pad], split from fp32 on the way (refine_dgrad_kernel's staging), and feeds
-// v_mfma_f32_32x32x16_f16 through ds_read_b64_tr_b16 (nsr_wgrad_f16.hip): a 16-lane group reads a block of 4 pixels x 16
+// v_mfma_f32_32x32x16_f16 through ds_read_b64_tr_b16 (tr16, nsr_lds_dma.h): a 16-lane group reads a block of 4 pixels x 16
 // channels and lane i receives channel i of the 4 pixels, i.e. its half of an operand's k run.  Three MFMAs per product,
 // small terms first (lo hi, hi lo, hi hi): the forward's and refine_dgrad_kernel's arithmetic.
 //
@@ -27,13 +27,12 @@
 #include "nsr_refine_train_work.h"
 #include "nsr_gemm.h"
 #include "nsr_gemm_epilogue.h"
+#include "nsr_lds_dma.h"
 
 namespace nsr {
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+using namespace dma;
 
 constexpr int kTM = 128, kTN = 128, kTK = 32;
 constexpr int kRow = kTM + 32;               // halves per LDS row (see the header)
@@ -47,12 +46,6 @@ struct WgArgs {
   float* part; int64_t slice_stride;       // partial of slice z (of this launch): part + z slice_stride, (rows, 9 cin)
   int64_t k_begin, slice_len, K;           // this launch's first pixel, pixels per slice, pixels of the call
 };
-
-// the transposing LDS read (nsr_wgrad_f16.hip): lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3 of a
-// 4 x 16 block; lane i receives column i of the four rows
-__device__ __forceinline__ h4 tr16(unsigned byte_addr) {
-  return __builtin_bit_cast(h4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp4*)(size_t)byte_addr));
-}
 
 // grid: x = column tile (tap, 128 input channels), y = row tile (128 outputs), z = slice
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) refine_wgrad_kernel(WgArgs a) {
@@ -132,7 +125,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   // ---- this lane's address for the transposing reads: its 16-lane group (columns 16 (g4 & 1) .., k half g4 >> 1 = h) reads
   // the block of pixels 16 s + 8 h + 4 t .. + 3; lane 4 q + p supplies pixel row q, columns 4 p .. 4 p + 3
   const int i16 = lane & 15, g4 = lane >> 4;
-  const unsigned lds0 = (unsigned)(size_t)((const __attribute__((address_space(3))) char*)lds);
+  const unsigned lds0 = lds_addr(lds);
   const unsigned rd = lds0 + 2u * (unsigned)((8 * h + (i16 >> 2)) * kRow + 16 * (g4 & 1) + 4 * (i16 & 3));
   const unsigned rd_a = rd + 2u * (unsigned)(64 * wm), rd_b = rd + 2u * (unsigned)(2 * kPlane + 64 * wn);
   auto frag = [&](unsigned base, int s) {            // rows 16 s + 8 h + 0 .. 7 of this lane's column

@@ -291,19 +291,7 @@ __device__ __forceinline__ void bwd_store_step(int s, const u32x4& h0, const u32
 // operations it sees, i.e. not the asm DMA pieces issued behind the load, so its wait at the first use may also cover the
 // chunk's youngest DMA pieces and stores.  Measured, interleaved on one box: 676.8 -> 671.7 us per pass -- the wait was rarely
 // exposed; what the DMA form buys is that the publish points' vmcnt accounting has no compiler-visible load left in it.)
-__device__ __forceinline__ void mask_dma(const unsigned* blk, unsigned lane4, unsigned lds_dst) {
-  unsigned long long tmp;
-  asm volatile(
-      "s_mov_b32 m0, %3\n\t"
-      "s_mov_b64 %0, %2\n\t"
-      "global_load_lds_dword %1, %0"
-      : "=&s"(tmp)
-      : "v"(lane4), "s"(blk), "s"(lds_dst)
-      : "memory");
-}
-__device__ __forceinline__ unsigned mask_read(unsigned lds_addr_lane) {
-  return *(const __attribute__((address_space(3))) unsigned*)(size_t)lds_addr_lane;
-}
+__device__ __forceinline__ void mask_dma(const unsigned* blk, unsigned lane4, unsigned lds_dst) { glds4_asm(blk, lane4, lds_dst); }
 
 struct BwdCtx {
   const unsigned* sgn;   // sign panels of the forward pass (masks)
@@ -311,7 +299,7 @@ struct BwdCtx {
   unsigned voff0, voff1; // this lane's slot in unit 0 / 1 of a block (unit_voff)
   int lane;
   unsigned lane4;     // lane * 4
-  unsigned lmask;     // LDS byte address of this wave's 256-byte mask area (mask_dma / mask_read)
+  unsigned lmask;     // LDS byte address of this wave's 256-byte mask area (mask_dma / lds_load)
   unsigned* lmax;     // LDS, 16 words: per gradient panel, float bits of the largest magnitude this workgroup wrote
   float* pscale;      // (10 panels, padded points): stored value x pscale = true gradient
   int64_t pidx;       // this lane's point slot (group * 32 + m); lanes of the upper half do not write
@@ -401,7 +389,7 @@ __device__ __forceinline__ void bwd_layer(int lam, int prev_panel, int panel, in
             if (g == 2) bwd_store_step(s, oh[2 * nb - 2], oh[2 * nb - 1], panel_block(cx.dp, panel, nb - 1), cx.voff0, cx.voff1);
           }
           if (load_next && g == 1 && s == 6) mask_dma(next_blk, cx.lane4, cx.lmask);         // the pair that opens with block nb + 1
-          if (MASK && !(nb & 1) && g == 1 && s == 14) mz[(nb >> 1) & 1] = mask_read(cx.lmask + cx.lane4);   // this block opens a pair
+          if (MASK && !(nb & 1) && g == 1 && s == 14) mz[(nb >> 1) & 1] = lds_load<unsigned>(cx.lmask + cx.lane4);   // this block opens a pair
         },
         [&](int k, int g) {
           if (g == 0) prefetch_frag(nxt, k, ld.slot_next + ld.lane_off);
@@ -816,7 +804,7 @@ __device__ __forceinline__ void bwd_layer_h(int lam, int prev_panel, int panel, 
               if (g == LG) bwd_store_step(s, oh[2 * nb - 2], oh[2 * nb - 1], panel_block(cx.dp, panel, nb - 1), cx.voff0, cx.voff1);
             }
             if (load_next && g == LG && s == 6) mask_dma(next_blk, cx.lane4, cx.lmask);
-            if (MASK && !(nb & 1) && g == LG && s == 14) mz[(nb >> 1) & 1] = mask_read(cx.lmask + cx.lane4);
+            if (MASK && !(nb & 1) && g == LG && s == 14) mz[(nb >> 1) & 1] = lds_load<unsigned>(cx.lmask + cx.lane4);
           },
           [&](int k) { prefetch_frag_h<decltype(pre_nt)::value>(nxt, k, ld.slot_next + ld.lane_off); });
     };

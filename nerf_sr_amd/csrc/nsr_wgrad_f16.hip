@@ -30,9 +30,6 @@ namespace nsr {
 namespace {
 
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef NSR_SLICE_INLINE
 #define NSR_SLICE_INLINE __forceinline__
@@ -43,26 +40,6 @@ constexpr int kStageData = 32 * 1024;          // A rows then B rows of one poin
 constexpr int kStageBytes = kStageData + 256;  // + the group's pscale (one 256-byte DMA piece: 32 floats, twice)
 constexpr int kFac0 = kStages * kStageBytes;   // per wave: F1[32], F2[32] fp16 factors of the current group
 constexpr int kLdsBytes = kFac0 + 8 * 128;
-
-// 64 lanes x 4 B, lane-linear, global -> LDS (the dword form of glds16_asm, nsr_f16x3_core.h)
-__device__ __forceinline__ void glds4_asm(const char* base_uniform, unsigned lane_off, unsigned lds_dst_uniform) {
-  unsigned long long tmp;
-  asm volatile(
-      "s_mov_b32 m0, %3\n\t"
-      "s_mov_b64 %0, %2\n\t"
-      "global_load_lds_dword %1, %0"
-      : "=&s"(tmp)
-      : "v"(lane_off), "s"(base_uniform), "s"(lds_dst_uniform)
-      : "memory");
-}
-// the transposing LDS read: lane l of a 16-lane group receives, of the sixteen 8-byte pieces the group's lanes address,
-// half (l & 3) of the pieces of lanes (l >> 2), 4 + (l >> 2), 8 + (l >> 2), 12 + (l >> 2)
-__device__ __forceinline__ h4 tr16(unsigned byte_addr) {
-  return __builtin_bit_cast(h4, __builtin_amdgcn_ds_read_tr16_b64_v4f16((__attribute__((address_space(3))) fp4*)(size_t)byte_addr));
-}
-__device__ __forceinline__ u32x2 lds_u2(unsigned byte_addr) {
-  return *(const __attribute__((address_space(3))) u32x2*)(size_t)byte_addr;
-}
 
 // TM x TN (BM, BN) = 256 x 256 (4, 2): trunk layers; 128 x 256 (2, 2): dir_encoding over g; 256 x 64 (1, 2): a trunk
 // layer over the encoded position; 128 x 64 (1, 1): dir_encoding over the encoded direction
@@ -142,12 +119,12 @@ __device__ NSR_SLICE_INLINE void wgrad_slice(const WgradArgs& w, int64_t g_begin
       const unsigned sb = lds0 + (unsigned)st * kStageBytes;
       // ---- per-point factors of this group, made once per wave: e = log2(pscale * S) as 2^(e >> 1) * 2^(e - (e >> 1))
       if (lane < 32) {
-        const unsigned pb = *(const __attribute__((address_space(3))) unsigned*)(size_t)(sb + kStageData + 4u * (unsigned)lane);
+        const unsigned pb = lds_load<unsigned>(sb + kStageData + 4u * (unsigned)lane);
         int e = (int)((pb >> 23) & 255u) - 127 + eS;
         e = e < -28 ? -28 : (e > 28 ? 28 : e);
         const int e1 = e >> 1, e2 = e - e1;
-        *(__attribute__((address_space(3))) unsigned short*)(size_t)(fac + 2u * (unsigned)lane) = (unsigned short)((15 + e1) << 10);
-        *(__attribute__((address_space(3))) unsigned short*)(size_t)(fac + 64u + 2u * (unsigned)lane) = (unsigned short)((15 + e2) << 10);
+        lds_store<unsigned short>(fac + 2u * (unsigned)lane, (unsigned short)((15 + e1) << 10));
+        lds_store<unsigned short>(fac + 64u + 2u * (unsigned)lane, (unsigned short)((15 + e2) << 10));
       }
       asm volatile("" ::: "memory");   // the wave's own LDS writes are seen by its later reads (DS operations stay in order)
       h2 f1[2][2][2], f2[2][2][2];     // [k-step][t][pair]
@@ -156,7 +133,7 @@ __device__ NSR_SLICE_INLINE void wgrad_slice(const WgradArgs& w, int64_t g_begin
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const unsigned o = 2u * (unsigned)(16 * s + 8 * hh + 4 * t);
-          const u32x2 a = lds_u2(fac + o), b = lds_u2(fac + 64u + o);
+          const u32x2 a = lds_load<u32x2>(fac + o), b = lds_load<u32x2>(fac + 64u + o);
           // through scalars: __builtin_bit_cast applied to a vector ELEMENT expression reads element 0 whatever the index
           // (hipcc 7.2; found in the ISA: one ds_read_b32 per pair of points)
           const unsigned a0 = a[0], a1 = a[1], b0 = b[0], b1 = b[1];
