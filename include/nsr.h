@@ -307,7 +307,9 @@ int nsr_resample_along_rays(const float* rays, int ray_stride, const float* z, c
  * NSR_F16X3 also with 192 or 256: the
  * launch composites its own rays and the (R, N, 4) network output never exists); 16 * (Nc + Nf) bytes per ray more when
  * a pass has to go through nsr_render_rays + nsr_composite.  nsr_forward_rays_workspace_bytes is the precision-agnostic
- * upper bound (always sufficient). */
+ * upper bound (always sufficient).  For every render driver (this one, _profiled, _ert, _density_coarse) the contents of the
+ * workspace on entry do not matter and are unspecified on return: one buffer may serve calls of any shapes and precisions, one
+ * at a time per stream. */
 size_t nsr_forward_rays_workspace_bytes_for(int precision, int64_t R, int n_coarse, int n_importance);
 size_t nsr_forward_rays_workspace_bytes(int64_t R, int n_coarse, int n_importance);
 int nsr_forward_rays(const void* packed_coarse, const void* packed_fine, int precision, const float* rays,

@@ -8,7 +8,9 @@
  * identical calls give identical bits.
  *
  * Same conventions as nsr.h (device pointers, caller-owned workspace, enqueue on the caller's stream, int status, nothing
- * allocated, no host synchronisation, every argument checked before anything is enqueued).
+ * allocated, no host synchronisation, every argument checked before anything is enqueued).  A workspace is scratch: its contents
+ * on entry do not matter and are unspecified on return (one buffer may serve calls of any kinds and shapes, one at a time per
+ * stream).
  *
  * A workgroup owns a 32 x 32 tile of one image plane and stages it with its halo once in LDS, as fp32:
  *   forward   TV, gradient: 33 x 33 per image (one element right and down);  Laplacian: 34 x 34 (one element all round);

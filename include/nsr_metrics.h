@@ -7,7 +7,9 @@
  * fp64.  No float atomics: a frame gives the same bits alone, at any batch size and in any slot of the batch.
  *
  * Same conventions as nsr.h (device pointers, caller-owned workspace, enqueue on the caller's stream, int status,
- * nothing allocated, no host synchronisation).
+ * nothing allocated, no host synchronisation).  A workspace is scratch: its contents on entry do not matter and are
+ * unspecified on return (one buffer may serve calls of any shapes, one at a time per stream); its size depends on the size
+ * function's arguments only.
  */
 #ifndef NSR_METRICS_H_
 #define NSR_METRICS_H_

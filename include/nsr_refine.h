@@ -41,7 +41,9 @@ int nsr_refine_pack_weights(const float* const* tensors, void* packed, int preci
 /* H and W multiples of 8 (three stride-2 levels); 0 on invalid arguments.  The plain form is the NSR_FP32 size (the larger
  * one: that mode materialises im2col matrices); `_for` gives the size a precision actually needs (NSR_F16X3: activations
  * + 128 bytes per input pixel for the first layer -- its input staged as pre-split 16-channel planes when the patch is whole
- * 16 x 16 blocks, a 32-column im2col matrix otherwise --, ~21 MB per 64 x 64 patch set with 8 references). */
+ * 16 x 16 blocks, a 32-column im2col matrix otherwise --, ~21 MB per 64 x 64 patch set with 8 references).
+ * The workspace is scratch: its contents on entry do not matter and are unspecified on return (one buffer may serve calls of
+ * any shapes and precisions, one at a time per stream); a size depends on the function's arguments only. */
 size_t nsr_refine_workspace_bytes(int B, int R, int H, int W);
 size_t nsr_refine_workspace_bytes_for(int precision, int B, int R, int H, int W);
 /* x_synth (B, 3, H, W), x_candi (B, R, 3, H, W), out (B, 3, H, W): NCHW fp32 DEVICE (the reference's tensors) */
@@ -78,7 +80,10 @@ int nsr_refine_forward_noref(const void* packed, int precision, const float* x_s
  * NSR_ERR_INVALID_ARG, one shorter than its header says NSR_ERR_WORKSPACE.  The backward reads the header back (it waits
  * for the stream); everything is validated before anything is enqueued.  Every reduction runs in a fixed order without
  * float atomics: identical calls give identical bits.  No gradient with respect to the images; no status word
- * (non-finite values travel as in torch). */
+ * (non-finite values travel as in torch).
+ * `workspace` (256-byte aligned) is scratch in both calls: its contents on entry do not matter and are unspecified on return,
+ * nothing travels in it from a forward to its backward (one buffer may serve any number of pending forwards, of any shapes);
+ * `saved` need not be initialised before the forward. */
 #define NSR_REFINE_N_PARAMS 72
 size_t nsr_refine_train_workspace_bytes(int B, int R, int H, int W, int img_chunk);
 size_t nsr_refine_train_saved_bytes(int B, int R, int H, int W);

@@ -57,7 +57,9 @@ size_t nsr_train_workspace_bytes(int64_t ray_chunk, int n_coarse, int n_importan
 /* The same for the path `precision` selects (what nsr_train_loss_and_grads checks): NSR_F16X3 -> the chain path's 2-byte
  * panels, sign words and weight streams without the per-layer activation / gradient matrices of the GEMM path (~11 KB per
  * sample point); NSR_FP32 / NSR_F16X3_GEMM -> the GEMM path's buffers without the panels (~13 KB).
- * nsr_train_workspace_bytes is the union: sufficient whatever runs.  Both depend on their arguments only. */
+ * nsr_train_workspace_bytes is the union: sufficient whatever runs.  Both depend on their arguments only.
+ * Behind its first 64 bytes (the sticky status block, nsr_train_status below) a workspace is scratch for every entry point of
+ * this header: its contents on entry do not matter and are unspecified on return. */
 size_t nsr_train_workspace_bytes_for(int precision, int64_t ray_chunk, int n_coarse, int n_importance);
 
 /* Losses and d(loss_tot)/d(weights) of one batch.
