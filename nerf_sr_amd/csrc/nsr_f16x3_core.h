@@ -70,7 +70,9 @@ struct Loader {
   // matching LDS byte address, its piece count
   const char* dma_base;
   unsigned dma_lds;
-  int dma_count;
+  int dma_count;         // runtime shares only (loader_issue)
+  unsigned dma_bias;     // constant shares only (loader_issue_const): byte offset of this wave's quarter of the bias piece
+  unsigned dma_voff;     // ... and the lane offset of the 4 KiB group going out (lane_off + 4096 q, q = 1, 2)
 #ifdef NSR_ABL_TIMELINE
   unsigned long long* tk = nullptr;   // k-step stamps of ONE designated chunk (null elsewhere; compile-time after inlining)
 #endif
@@ -87,6 +89,69 @@ __device__ __forceinline__ void loader_prepare_dma(Loader& ld, const ChunkRef& c
   ld.dma_count = c.count;
   ld.dma_base = reinterpret_cast<const char*>(ld.stream) + ((unsigned)(c.piece0 + c.first) << 10);   // the stream is < 4 MiB
   ld.dma_lds = slot_lds + (unsigned)c.first * 1024u;
+  ld.dma_bias = ((unsigned)(c.pieces - 1 - c.first) << 10) + (unsigned)ld.wave * 256u;
+}
+
+// ---- constant shares (the render kernels; the training chains keep the runtime shares below).
+// Every chunk of the stream is 4 K fragment pieces + one bias piece, K = 8 (16 k-steps; L1's four blocks of 4), 9 (dir_encoding,
+// 18) or 10 (the skip layer, 20).  Wave w moves the fragment pieces w K .. w K + K - 1 -- where make_ref's quarter starts
+// anyway -- and, with the dword form, the 256 bytes w of the bias piece (64 lanes x 4 B, lane-linear: the LDS image is the
+// piece's).  So every wave issues the same K + 1 instructions for a chunk, K known where the chunk is named: no piece count,
+// no test, no branch in a k-step.  The 64-bit base and the LDS address are the share's, formed once per chunk
+// (loader_prepare_dma); the 4 KiB group of a piece rides in the lane offset (one VGPR add per group) and in the M0 value,
+// the piece in the immediate.
+constexpr bool shares_cover(int pieces) {
+  const int k = (pieces - 1) / 4;
+  if (pieces != 4 * k + 1 || k < 8 || k > 10) return false;
+  int seen[kSlotPieces] = {};
+  int bias_quarters = 0;
+  for (int w = 0; w < 4; ++w) {
+    if (((w * pieces) >> 2) != w * k) return false;             // make_ref's `first`
+    for (int t = 0; t < k; ++t) ++seen[w * k + t];
+    const int b = (pieces - 1 - w * k) * 1024 + w * 256;        // dma_bias, from the share's first byte
+    if (w * k * 1024 + b != (pieces - 1) * 1024 + 256 * bias_quarters) return false;
+    ++bias_quarters;
+  }
+  for (int i = 0; i < pieces - 1; ++i)
+    if (seen[i] != 1) return false;
+  return seen[pieces - 1] == 0 && bias_quarters == 4;
+}
+constexpr bool shares_cover_stream() {
+  for (int q = 0; q < kChunks; ++q) {
+    const Chunk c = chunk_info(q);
+    if (!shares_cover(chunk_pieces(c.steps, c.nnb))) return false;
+  }
+  return shares_cover(kFoldChunkPieces);
+}
+static_assert(shares_cover_stream(), "four equal shares + four bias quarters cover every piece of every chunk kind exactly once");
+
+// instruction t (0 .. K) of this wave's K + 1 for the chunk being fetched; K and t are constants where this is inlined
+__device__ __forceinline__ void loader_issue_const(Loader& ld, int t, int K) {
+#ifdef NSR_ABL_NO_DMA
+  return;
+#endif
+  if (t < K) {
+    // the group's lane offset is made where its first piece goes out and dies with its last (lane_offset_*: left to hipcc
+    // it is hoisted out of the window loop, one more register through the whole trunk, and the kernels have none)
+    if (t == 4) ld.dma_voff = lane_offset_group<4096>(ld.lane_off);
+    if (t == 8) ld.dma_voff = lane_offset_group<8192>(ld.lane_off);
+    const unsigned voff = t < 4 ? ld.lane_off : ld.dma_voff;
+    const unsigned dst = ld.dma_lds + (unsigned)(t >> 2) * 4096u;
+    // pieces are issued in order, piece 4q first: it writes M0 for its group
+    switch (t & 3) {
+      case 0: glds16_asm<0>(ld.dma_base, voff, dst); break;
+      case 1: glds16_keep_asm<1024>(ld.dma_base, voff); break;
+      case 2: glds16_keep_asm<2048>(ld.dma_base, voff); break;
+      default: glds16_keep_asm<3072>(ld.dma_base, voff); break;
+    }
+  } else if (t == K) {
+    glds4_asm(ld.dma_base, lane_offset_dword(ld.lane_off, ld.dma_bias), ld.dma_lds + ld.dma_bias);
+  }
+}
+// a whole chunk at once (the prologue and the restart behind an empty window: nothing to hide it behind)
+__device__ __forceinline__ void loader_issue_chunk(Loader& ld, int K) {
+#pragma unroll
+  for (int t = 0; t <= 10; ++t) loader_issue_const(ld, t, K);
 }
 
 // issue this wave's DMA piece number i of the chunk being fetched (no-op past its end)
@@ -244,9 +309,11 @@ __device__ __forceinline__ void block_mma(Acc& acc, const Pre& pre, unsigned a_a
 // DMA = false: the publish point stays, but no chunk is fetched behind it (the last two chunks of a one-tile workgroup:
 // there is no next tile to fetch L1 for).
 // MMA = false (ablation builds only, -DNSR_ABL_NO_DENSITY_MMA): the block runs without its MFMAs -- what they cost.
+// kpw (a constant at every call site): the fetched chunk's pieces per wave K, its K + 1 instructions going out by constant
+// shares (loader_issue_const); 0: by the runtime shares of loader_issue (the TRAIN forward).
 template <int NSTEP, int BAR, int YOUNGER = 0, bool DMA = true, bool MMA = true, class BOf, class Hook, class Next>
 __device__ __forceinline__ void block_mma3(Acc& acc, const Pre& pre, unsigned a_addr, Loader& ld, const ChunkRef& c2,
-                                           BOf&& b_of, Hook&& hook, Next&& next, bool strict = false) {
+                                           BOf&& b_of, Hook&& hook, Next&& next, bool strict = false, int kpw = 0) {
   static_assert(NSTEP >= kPF, "sequence shorter than the prefetch depth");
   const u32x4* a_pieces = lds_vec(a_addr);
   u32x4 ah[NSTEP], al[NSTEP];
@@ -278,13 +345,19 @@ __device__ __forceinline__ void block_mma3(Acc& acc, const Pre& pre, unsigned a_
     // ---- gap 1
     if (MMA) acc.m = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(ah[s]), as_h8(bl), acc.m, 0, 0, 0);
     hook(s, 1);
-    if (DMA && BAR >= 0 && s >= BAR && s < BAR + 6) loader_issue(ld, 2 * (s - BAR));
+    if (DMA && BAR >= 0 && s >= BAR && s < BAR + 6) {
+      if (kpw) loader_issue_const(ld, 2 * (s - BAR), kpw);
+      else loader_issue(ld, 2 * (s - BAR));
+    }
     __builtin_amdgcn_sched_barrier(0);
     // ---- gap 2
     if (MMA) acc.m = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(ah[s]), as_h8(bh), acc.m, 0, 0, 0);
     hook(s, 2);
     if (s + kPF >= NSTEP) next(s + kPF - NSTEP, 2);
-    if (DMA && BAR >= 0 && s >= BAR && s < BAR + 6) loader_issue(ld, 2 * (s - BAR) + 1);
+    if (DMA && BAR >= 0 && s >= BAR && s < BAR + 6) {
+      if (kpw) loader_issue_const(ld, 2 * (s - BAR) + 1, kpw);
+      else loader_issue(ld, 2 * (s - BAR) + 1);
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
 }

@@ -1,5 +1,5 @@
 // LDS-DMA and LDS access primitives of the matrix kernels: every inline-asm VMEM statement of the project (global -> LDS
-// pieces, the panel stores), the counted wait that goes with them, and LDS access by 32-bit byte address.  The only file
+// pieces, the panel stores), the counted wait and the lane offsets that go with them, and LDS access by 32-bit byte address.  The only file
 // of csrc/ that names the LDS address space or a global_load_lds / global_store in an asm string
 // (tests/test_lds_primitives_cpu.py); build.isa_contract checks the two rules below on the compiled listings.
 #pragma once
@@ -110,6 +110,25 @@ __device__ __forceinline__ void glds4_asm(const void* base_uniform, unsigned lan
       : "=&s"(tmp)
       : "v"(lane_off), "s"(base_uniform), "s"(lds_dst_uniform)
       : "memory");
+}
+// Lane offsets made at the issue site.  volatile: the value is a constant of the whole kernel and hipcc would keep it in a
+// register of its own from the prologue on; made here it lives from its group's first piece to its last.
+// lane_off + ADD (the 4 KiB group ADD / 4096 of a share)
+template <int ADD>
+__device__ __forceinline__ unsigned lane_offset_group(unsigned lane_off) {
+  unsigned r;
+  asm volatile("v_add_u32 %0, %1, %2" : "=v"(r) : "n"(ADD), "v"(lane_off));
+  return r;
+}
+// lane_off / 4 + add_uniform: the dword form's lane offset (lane * 4) from the 16-byte one, plus a wave-uniform byte offset
+__device__ __forceinline__ unsigned lane_offset_dword(unsigned lane_off, unsigned add_uniform) {
+  unsigned r;
+  asm volatile(
+      "v_lshrrev_b32 %0, 2, %1\n\t"
+      "v_add_u32 %0, %2, %0"
+      : "=&v"(r)
+      : "v"(lane_off), "s"(add_uniform));
+  return r;
 }
 // 16 B per lane to base + voff + OFF, non-temporal; 4 B per lane to base + voff (the training panels' two stores)
 template <int OFF>

@@ -404,7 +404,10 @@ __device__ __forceinline__ void prefetch_next_chunk(Pre& nxt, int k, int g, cons
 // which must see that DMA landed -- may leave those stores in flight (block_mma's YOUNGER); they have a whole further
 // chunk to reach HBM.  (Rounds 2-4 stored the sixteen raw fp32 accumulators of a block here.)
 // Only the TRAIN forward evaluates xyz_encoding_final (L == 8); everywhere else it is folded into dir_encoding.
-template <bool RELU_OUT, bool TRAIN = false>   // relu on L2..L8 (true), none on xyz_encoding_final (L == 8: false)
+// K0 / KA0 / KA1 (the render kernels): pieces per wave (nsr_f16x3_core.h, constant shares) of this layer's chunks and of the two
+// chunks behind it -- 8, 10 for the skip layer, 9 for dir_encoding's; the skip is then K0 == 10, not L == 4.  K0 == 0 (the
+// TRAIN forward): runtime shares, L alone says what the layer is.
+template <bool RELU_OUT, bool TRAIN = false, int K0 = 0, int KA0 = 0, int KA1 = 0>   // relu on L2..L8 (true), none on xyz_encoding_final (L == 8: false)
 __device__ __forceinline__ void trunk_layer(int L, u32x4 (&bh)[16], u32x4 (&bl)[16], u32x4 (&oh)[16], u32x4 (&ol)[16],
                                             const u32x4* stash, Loader& ld, int h, Acc& pend, Pre& pre,
                                             const ChunkRef& after0, const ChunkRef& after1, float& amax, unsigned& sbits,
@@ -413,6 +416,8 @@ __device__ __forceinline__ void trunk_layer(int L, u32x4 (&bh)[16], u32x4 (&bl)[
                                             , unsigned long long* ld_tk_buf = nullptr
 #endif
                                             ) {
+  static_assert(K0 == 0 ? (KA0 == 0 && KA1 == 0) : (!TRAIN && KA0 >= 8 && KA1 >= 8), "constant shares: all three counts, render kernels only");
+  const bool skip = K0 ? K0 == 10 : L == 4;
   const ChunkRef ref0 = layer_ref(L, 0, ld.wave);           // this layer's chunks: piece0 advances by `pieces`
 #pragma unroll
   for (int nb = 0; nb < 8; ++nb) {
@@ -431,9 +436,10 @@ __device__ __forceinline__ void trunk_layer(int L, u32x4 (&bh)[16], u32x4 (&bl)[
     ld.tk = (L == 7 && nb == 3) ? ld_tk_buf : nullptr;
     if (L == 7 && nb == 4) ld_tk_buf[5] = tl_now();
 #endif
-    const unsigned next_bias = (unsigned)(c1.pieces - 1) * 1024u;
+    const unsigned next_bias = K0 ? 4096u * (unsigned)(nb < 7 ? K0 : KA0) : (unsigned)(c1.pieces - 1) * 1024u;
+    const int kpw = nb < 6 ? K0 : (nb == 6 ? KA0 : KA1);   // of c2
     Pre nxt;
-    if (L == 4) {
+    if (skip) {
       // skip connection: the encoded position was parked in LDS by the prologue (8 fragments per lane);
       // its 4 k-steps run first and hand the act part's first fragments over through `mid`
       u32x4 pe8[8];
@@ -485,10 +491,21 @@ __device__ __forceinline__ void trunk_layer(int L, u32x4 (&bh)[16], u32x4 (&bl)[
         },
         [&](int k, int g) { prefetch_next_chunk(nxt, k, g, ld, next_bias, h); },
         // the block before the first trunk block is L1's last one, whose stores interleave with its DMA
-        TRAIN && L == 1 && nb == 0);
+        TRAIN && L == 1 && nb == 0, kpw);
     pend = cur;
     pre = nxt;
     loader_advance(ld);
+  }
+}
+
+// an L1 chunk (33 pieces) all at once: the prologue, and the restart behind an empty window
+template <bool TRAIN>
+__device__ __forceinline__ void issue_l1_chunk(Loader& ld) {
+  if (TRAIN) {
+#pragma unroll
+    for (int i = 0; i < 11; ++i) loader_issue(ld, i);
+  } else {
+    loader_issue_chunk(ld, 8);
   }
 }
 
@@ -618,11 +635,9 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   ld.slot_free = ld.slot_cur + 2 * kSlotBytes;
   // chunks 0 and 1 stream in behind the first tile's encoding
   loader_prepare_dma(ld, first_ref(0, wave), ld.slot_cur);
-#pragma unroll
-  for (int i = 0; i < 11; ++i) loader_issue(ld, i);
+  issue_l1_chunk<TRAIN>(ld);
   loader_prepare_dma(ld, first_ref(1, wave), ld.slot_next);
-#pragma unroll
-  for (int i = 0; i < 11; ++i) loader_issue(ld, i);
+  issue_l1_chunk<TRAIN>(ld);
 
   const int64_t n_rays = COMP ? P / (NS > 0 ? NS : 1) : 0;
   const int64_t n_tiles = COMP ? (n_rays + 3) / 4 : (P + 127) / 128;
@@ -828,7 +843,8 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
           cur, l1pre, a_addr, ld, first_ref(0, wv), [&](int s, int part) -> u32x4 { return part ? pel[s] : peh[s]; },
           [&](int s, int gp) {
             const int i = 4 * g + s;        // DMA of chunk j+2: one piece per k-step over the chunk's 16 k-steps
-            if (gp == 0 && i < 11) loader_issue(ld, i);
+            if (gp == 0 && TRAIN && i < 11) loader_issue(ld, i);
+            if (gp == 0 && !TRAIN) loader_issue_const(ld, i, 8);
             if (nb > 0) {
               // half-steps of the pending block: k-step 0 takes 0 | 1, 2 | 3, 4; k-step s >= 1 takes 4s+1 | 4s+2, 4s+3 | 4s+4
               const int first = (s == 0) ? (gp == 0 ? 0 : 2 * gp - 1) : 4 * s + (gp == 0 ? 1 : (gp == 1 ? 2 : 4));
@@ -867,6 +883,7 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
   // ---- L2..L8, two layers per trip so the register sets swap roles.  Three trips of relu layers (L2..L7); L8 is peeled:
   // what follows it differs (the density head; in the TRAIN forward xyz_encoding_final, which has no relu -- the
   // activation is a compile-time property of every re-split).
+  if (TRAIN) {
 #pragma unroll 1
   for (int pair = 0; pair < 3; ++pair) {
     const int L = 1 + 2 * pair;
@@ -874,14 +891,29 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
     trunk_layer<true, TRAIN>(L + 1, oh, ol, bh, bl, stash, ld, h, pend, pre, layer_ref(L + 2, 0, wv), layer_ref(L + 2, 1, wv), amax,
                              sbits, tr, voff0, voff1);
   }
+  } else {
+    // constant shares: the number of DMA instructions of a chunk is a property of the code that fetches it, so the pair around
+    // the skip layer (L4 fetches L5's 41-piece chunks, L5 runs them) has a body of its own: trips (L2, L3), then (L4, L5) once,
+    // (L6, L7)
+#pragma unroll 1
+    for (int t = 0; t < 2; ++t) {
+      const int L = 1 + 4 * t;
+      trunk_layer<true, false, 8, 8, 8>(L, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(L + 1, 0, wv), layer_ref(L + 1, 1, wv), amax, sbits);
+      trunk_layer<true, false, 8, 8, 8>(L + 1, oh, ol, bh, bl, stash, ld, h, pend, pre, layer_ref(L + 2, 0, wv), layer_ref(L + 2, 1, wv), amax, sbits);
+      if (t == 0) {
+        trunk_layer<true, false, 8, 10, 10>(3, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(4, 0, wv), layer_ref(4, 1, wv), amax, sbits);
+        trunk_layer<true, false, 10, 8, 8>(4, oh, ol, bh, bl, stash, ld, h, pend, pre, layer_ref(5, 0, wv), layer_ref(5, 1, wv), amax, sbits);
+      }
+    }
+  }
   if (SIGMA_ONLY) {   // L8 is followed by the density head, then nothing
-    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), first_ref(0, wv), amax, sbits);
+    trunk_layer<true, false, 8, 8, 8>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), first_ref(0, wv), amax, sbits);
   } else if (!TRAIN) {  // the density head comes next (SIGMA_ONLY's sequence), the folded dir_encoding after it
 #ifdef NSR_ABL_TIMELINE
-    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), fdir_ref(0, wv), amax, sbits, tr, voff0, voff1, tk);
+    trunk_layer<true, false, 8, 8, 9>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), fdir_ref(0, wv), amax, sbits, tr, voff0, voff1, tk);
     ld.tk = nullptr;
 #else
-    trunk_layer<true>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), fdir_ref(0, wv), amax, sbits);
+    trunk_layer<true, false, 8, 8, 9>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, sigma_ref(wv), fdir_ref(0, wv), amax, sbits);
 #endif
   } else {              // the training forward keeps xyz_encoding_final: its output (panel 8) feeds the weight gradients
     trunk_layer<true, TRAIN>(7, bh, bl, oh, ol, stash, ld, h, pend, pre, layer_ref(8, 0, wv), layer_ref(8, 1, wv), amax, sbits, tr, voff0, voff1);
@@ -920,7 +952,8 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
         [&](int k, int g) {
           // sigma_only: the tile ends here, the next chunk is L1 chunk 0 again (bias behind 32 weight pieces)
           prefetch_next_chunk(nxt, k, g, ld, SIGMA_ONLY ? 32u * 1024u : next_bias, h);
-        });
+        },
+        false, TRAIN ? 0 : (SIGMA_ONLY ? 8 : 9));
     sigma = cur.m[0] * kWInvScale;           // row 0 of the block lives in register 0 of the h == 0 lanes
     pre = nxt;
     loader_advance(ld);
@@ -950,11 +983,9 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
       __syncthreads();          // every wave's DMA has landed and nobody reads the ring
       if (win + 1 < kWindows) {
         loader_prepare_dma(ld, first_ref(0, wv), ld.slot_cur);
-#pragma unroll
-        for (int i = 0; i < 11; ++i) loader_issue(ld, i);
+        issue_l1_chunk<TRAIN>(ld);
         loader_prepare_dma(ld, first_ref(1, wv), ld.slot_next);
-#pragma unroll
-        for (int i = 0; i < 11; ++i) loader_issue(ld, i);
+        issue_l1_chunk<TRAIN>(ld);
       }
       if (co.skipped && threadIdx.x == 0) atomicAdd(co.skipped, 1u);
     }
@@ -996,11 +1027,12 @@ mlp_f16x3_kernel(const float* __restrict__ packed, const float* __restrict__ x, 
       if (nb < 3) prefetch_next_chunk(nxt, k, g, ld, next_bias, h);
     };
     // nothing is fetched behind the last two blocks: the tile's stream ends with them
+    const int kpw = TRAIN ? 0 : (nb < 2 ? 9 : 8);     // of c2: a folded dir_encoding chunk | an L1 chunk
     if (nb >= 2) {
-      if (COMP) block_mma3<18, kBar>(cur, pre, a_seq, ld, c2, b_of, hook, next);
+      if (COMP) block_mma3<18, kBar>(cur, pre, a_seq, ld, c2, b_of, hook, next, false, kpw);
       else if (!TRAIN) block_mma3<18, kBar, 0, false>(cur, pre, a_seq, ld, c2, b_of, hook, next);
       else block_mma3<18, kBar, kTrainYoung, false>(cur, pre, a_seq, ld, c2, b_of, hook, next);
-    } else if (!TRAIN || nb == 1) block_mma3<18, kBar>(cur, pre, a_seq, ld, c2, b_of, hook, next);
+    } else if (!TRAIN || nb == 1) block_mma3<18, kBar>(cur, pre, a_seq, ld, c2, b_of, hook, next, false, kpw);
     else if (nb == 0) block_mma3<18, kBar, 2>(cur, pre, a_seq, ld, c2, b_of, hook, next);
     else block_mma3<18, kBar, kTrainYoung>(cur, pre, a_seq, ld, c2, b_of, hook, next);
     pend = cur;

@@ -140,9 +140,9 @@ struct Chunk {
   int piece0;   // first piece of the chunk in the stream
 };
 
-NSR_HD int chunk_pieces(int steps, int nnb) { return 2 * steps * nnb + 1; }
+NSR_HD constexpr int chunk_pieces(int steps, int nnb) { return 2 * steps * nnb + 1; }
 
-NSR_HD Chunk chunk_info(int q) {
+NSR_HD constexpr Chunk chunk_info(int q) {
   Chunk c{};
   if (q < 2) {                       // L1: 63(+1) -> 256, 4 k-steps
     c.tensor = 0; c.nb0 = 4 * q; c.nnb = 4; c.steps = 4; c.piece0 = 33 * q;
