@@ -295,7 +295,8 @@ int nsr_arch_fused_render_rays(const nsr_arch* arch, const void* packed, const f
  *              deg_dir == 0 unless no_dir -- a layer without input columns, which the reference cannot build either.
  *   Training.  The encoder writes the word's columns, sin / cos (nsr_sincos) of band * x from the table of nsr_posenc_freqs (the
  *              largest band is 2^(deg-1) under both tables).  The saved header records the word next to the descriptor: a
- *              backward with another word is NSR_ERR_INVALID_ARG.  Nothing differentiates through the encoding.
+ *              backward with another word is NSR_ERR_INVALID_ARG.  The weight gradients do not differentiate through the encoding;
+ *              nsr_train_arch_backward_r below does, for the gradient with respect to the rays.
  *   Fused.     nsr_arch_fused_forward_e takes rows of the narrower widths (what nsr_posenc_e writes).  nsr_arch_fused_render_rays_e
  *              computes them in the kernel by nsr_posenc_e's expression: output and status word are bit-identical to the rows
  *              entry on nsr_posenc_e's rows under every word.  NSR_FLAG_INPUT_RANGE tests the columns the network sees: under
@@ -324,6 +325,33 @@ int nsr_arch_fused_forward_e(const nsr_arch* arch, unsigned embed, const void* p
 int nsr_arch_fused_render_rays_e(const nsr_arch* arch, unsigned embed, const void* packed, const float* rays, int ray_stride,
                                  const float* z, int64_t R, int n_samples, int flags, float* out, int64_t ldo, unsigned* status,
                                  void* stream);
+
+/* ---- The gradient with respect to the RAYS on the layer-by-layer pair (pose refinement, anything that produces rays).
+ * nsr_train_arch_backward_r with g_rays == NULL IS nsr_train_arch_backward_e: the same launches, the same bits, the same
+ * workspace.  With g_rays (R, g_ray_stride) it also OVERWRITES that matrix with d(loss) / d(rays) of the forward call's rays:
+ *   a sample point is x = o + z d; the encoded direction is v = d at stride 8, columns 8:11 at stride 11.  As in the reference
+ *   (models/nerf_downX_model.py:280-313) the depths z do not depend on o or d: the fine depths come from the DETACHED coarse
+ *   weights and from near / far only.
+ *   g_x[p]  = the positional encoding's backward at point p, from the gradients of the encoded columns of layer 0 and of every
+ *             skip layer: identity columns pass through (none under NSR_EMBED_NO_XYZ), band f contributes
+ *             f (cos(f x) g_sin - sin(f x) g_cos) with the sin / cos the forward saved and f of nsr_posenc_freqs' table;
+ *   columns 0:3 = sum_k g_x[r, k];   columns 3:6 = sum_k z[r, k] g_x[r, k], plus at stride 8 the direction encoding's backward of
+ *   sum_k g_dirpe[r, k]; at stride 11 that term goes to columns 8:11.  No direction term under no_dir, and none under
+ *   NSR_TRAIN_STOP_GRAD (dir_encoding's whole input is detached, models/networks.py:218-219).  Coarse part first, fine part added.
+ *   Columns 6:8 (near, far) get EXACT ZEROS: the gradient with respect to near / far needs the resampler's backward and is not
+ *   computed.
+ * Every reduction has a fixed order (no float atomics): a ray's row depends on that ray, its draws and the weights only, and
+ * not on ray_chunk; two identical calls give identical bits.  g_ray_stride must be the forward call's ray stride (the saved
+ * header records it); a mismatch, or a saved state of a chain precision, is NSR_ERR_INVALID_ARG before anything is enqueued
+ * (g_rays untouched).  The workspace must hold nsr_train_arch_workspace_bytes_r (>= the _e figure: one (P, r32(in_xyz)) matrix
+ * per layer that reads the encoded position, one (P, r32(in_dir)), one (P, 3)), else NSR_ERR_WORKSPACE.  The input gradients
+ * onto the encoded columns run on the fp32 MFMA under both precisions, like every other gradient. */
+size_t nsr_train_arch_workspace_bytes_r(const nsr_arch* arch, unsigned embed, int precision, int64_t ray_chunk, int n_coarse,
+                                        int n_importance);
+int nsr_train_arch_backward_r(const nsr_arch* arch, unsigned embed, const float* const* w_coarse, const float* const* w_fine,
+                              const float* const* g_outs, float* const* g_coarse, float* const* g_fine, float* g_rays,
+                              int g_ray_stride, void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes,
+                              void* stream);
 
 /* One nn.Linear (+ activation) on the training GEMM, exposed for testing the kernel on its own:
  *   y (P, N) = act(x (P, K) · w (N, K)^T + b),  act: 0 none, 1 relu, 2 sigmoid;  y_t (N, P) optional transpose.

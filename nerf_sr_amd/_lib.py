@@ -164,6 +164,11 @@ SIGNATURES = {
                                          POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "nsr_train_arch_backward_e": (c_int, [POINTER(NsrArch), c_uint, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                           POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    # the backward with the gradient with respect to the rays (g_rays, g_ray_stride behind the gradient arrays)
+    "nsr_train_arch_workspace_bytes_r": (c_size_t, [POINTER(NsrArch), c_uint, c_int, c_int64, c_int, c_int]),
+    "nsr_train_arch_backward_r": (c_int, [POINTER(NsrArch), c_uint, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                          POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
+                                          c_void_p]),
     "nsr_arch_fused_packed_bytes_e": (c_size_t, [POINTER(NsrArch), c_uint]),
     "nsr_arch_fused_pack_e": (c_int, [POINTER(NsrArch), c_uint, POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
     "nsr_arch_fused_forward_e": (c_int, [POINTER(NsrArch), c_uint, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64,

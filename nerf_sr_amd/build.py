@@ -176,6 +176,11 @@ if os.path.exists(_ENCODE_HOOKS_SRC):
 _REDUCE_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_reduce.hip")
 if os.path.exists(_REDUCE_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_REDUCE_HOOKS_SRC)
+# ... and the launchers of the two kernels of the gradient with respect to the rays (tests/test_gpu_ray_grad_units.py); same
+# condition
+_RAYGRAD_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_raygrad.hip")
+if os.path.exists(_RAYGRAD_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_RAYGRAD_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -298,7 +298,10 @@ Kept carve_kept(Carver& a, int64_t P, const Shape* net, bool chain_path) {
 // net (+ split: its split-fp16 weight halves) and / or the chain path: the buffers of what may run.  Both
 // (nsr_train_workspace_bytes): sufficient whatever runs; the chain path alone holds no per-layer activation / gradient
 // matrices (11 KB per sample point less)
-int64_t work_floats(int64_t chunk, int nc, int ni, const Shape* net, bool split, bool chain_path, Work* w, float* base) {
+// ray_grad: behind everything else (the layout in front of them is the same with and without), the three matrices of the
+// gradient with respect to the rays
+int64_t work_floats(int64_t chunk, int nc, int ni, const Shape* net, bool split, bool chain_path, Work* w, float* base,
+                    bool ray_grad = false) {
   const int64_t nf = nc + ni, P = chunk * nf;
   Carver a{base};
   Work tmp;
@@ -332,6 +335,10 @@ int64_t work_floats(int64_t chunk, int nc, int ni, const Shape* net, bool split,
     k.stream_f[n] = a.take((int64_t)(nsr_f16x3_packed_bytes() / 4), chain_path);
     k.stream_b[n] = a.take((int64_t)(nsr_chain_bwd_packed_bytes() / 4), chain_path);
   }
+  const bool rg = ray_grad && net;
+  k.gpe = a.take(rg ? net->n_pe() * P * net->Kx : 0, rg);
+  k.gdir = a.take(rg ? P * net->Dp : 0, rg && net->Dp > 0);
+  k.gx = a.take(P * 3, rg);
   return a.off;
 }
 
@@ -465,7 +472,7 @@ int check_args(const Need& need, Run* c, int s2) {
 // usable where they lie, large enough, then carved.  The nsr_train_* family always sizes the split halves
 // (nsr_train_workspace_bytes_for: one size for both layer-by-layer precisions), nsr_train_arch_* sizes by precision
 int open_work(Run& c, const float* const* w_coarse, const float* const* w_fine, bool by_precision, void* workspace,
-              size_t workspace_bytes, Work& k) {
+              size_t workspace_bytes, Work& k, bool ray_grad = false) {
   c.chain = chain_selected(c.precision);
   const Shape* net = c.chain ? nullptr : &c.net;
   if (net) {
@@ -473,9 +480,9 @@ int open_work(Run& c, const float* const* w_coarse, const float* const* w_fine, 
     NSR_TRY(check_alignment(*net, w_fine));
   }
   const bool split = !by_precision || split_selected(c.precision);
-  if (workspace_bytes < (size_t)work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, nullptr, nullptr) * sizeof(float))
+  if (workspace_bytes < (size_t)work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, nullptr, nullptr, ray_grad) * sizeof(float))
     return NSR_ERR_WORKSPACE;
-  work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, &k, static_cast<float*>(workspace));
+  work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, &k, static_cast<float*>(workspace), ray_grad);
   return NSR_OK;
 }
 
@@ -541,7 +548,7 @@ int pass_forward(hipStream_t st, const Work& k, const Run& c, const Pass& q, con
 // tensors, overwritten or accumulated (q.acc)
 int pass_backward(hipStream_t st, const Work& k, const Run& c, const Pass& q, const float* const* w, const float* z,
                   const float* g_comp, const float* g_depth, const float* g_opacity, const float* g_weights, float* const* g,
-                  void* stream) {
+                  void* stream, const RayGrad* rg = nullptr) {
   NSR_TRY(composite_bwd(st, k.kept.rgb, k.kept.sig, z, g_comp, q.rc, q.N, c.flags, k.d4, c.chain ? k.gmax : nullptr,
                         c.chain ? k.bias_part : nullptr, g_depth, g_opacity, g_weights));
   if (c.chain) {
@@ -549,7 +556,7 @@ int pass_backward(hipStream_t st, const Work& k, const Run& c, const Pass& q, co
                           chain_bwd_terms(c.precision), 1, stream));
     return chain_weight_grads(st, k, q.P, q.rc, g, q.acc);
   }
-  return net_backward(st, c.net, w, k.pack[q.net], k, q.P, g, q.acc, (c.flags & NSR_TRAIN_STOP_GRAD) != 0);
+  return net_backward(st, c.net, w, k.pack[q.net], k, q.P, g, q.acc, (c.flags & NSR_TRAIN_STOP_GRAD) != 0, rg);
 }
 
 // ---- saved state of a forward call (include/nsr_train.h) --------------------------------------------------------------
@@ -563,6 +570,7 @@ struct SavedHeader {
   int nc, ni, flags, precision;
   nsr_arch arch;            // the network the forward ran (the default descriptor under a chain precision)
   unsigned embed;           // ... and the embedding's option word it ran with (include/nsr.h)
+  int ray_stride;           // the forward call's ray stride: what a gradient with respect to the rays must be laid out for
 };
 static_assert(sizeof(SavedHeader) <= kSavedHeaderFloats * 4 && sizeof(SavedHeader) % 4 == 0, "header");
 struct SavedLayout {
@@ -628,7 +636,7 @@ int train_forward(const nsr_arch* arch, unsigned embed, bool by_arch, const floa
   float* sv = static_cast<float*>(saved);
   if (c.chain)   // the backward weight streams are packed into the saved state: the backward call uses them as they are
     for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
-  const SavedHeader h{kSavedMagic, (uint64_t)L.total, R, c.chunk, n_coarse, n_importance, render_flags, precision, c.net.arch, embed};
+  const SavedHeader h{kSavedMagic, (uint64_t)L.total, R, c.chunk, n_coarse, n_importance, render_flags, precision, c.net.arch, embed, ray_stride};
   hipLaunchKernelGGL(saved_header_kernel, dim3(1), dim3(64), 0, st, h, reinterpret_cast<unsigned*>(sv));
   NSR_CHECK_LAUNCH();
   NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream));
@@ -645,8 +653,9 @@ int train_forward(const nsr_arch* arch, unsigned embed, bool by_arch, const floa
 
 int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const float* const* w_coarse, const float* const* w_fine,
                    const float* const* g_outs, float* const* g_coarse, float* const* g_fine, void* workspace, size_t workspace_bytes,
-                   const void* saved, size_t saved_bytes, void* stream) {
-  Run c{};   // no sampling in this half: lindisp, ray_stride and noise_std stay unused
+                   const void* saved, size_t saved_bytes, void* stream, float* g_rays = nullptr, int g_ray_stride = 0) {
+  Run c{};   // no sampling in this half: lindisp and noise_std stay unused
+  if (g_rays && !nsr_ray_stride_ok(g_ray_stride)) return NSR_ERR_INVALID_ARG;
   NSR_TRY(make_shape(arch, c.net, embed));
   NSR_TRY(check_args({{w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, saved}, {w_coarse, w_fine, g_coarse, g_fine},
                       nullptr, {}, {workspace, saved}, c.net.n_tensors(), by_arch}, nullptr, 1));
@@ -669,8 +678,10 @@ int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const flo
     return NSR_ERR_INVALID_ARG;
   const SavedLayout L = saved_layout(c.net, c.precision, c.R, c.nc, c.ni, c.chunk);
   if ((uint64_t)L.total != h.floats) return NSR_ERR_INVALID_ARG;
+  if (g_rays && (h.ray_stride != g_ray_stride || chain_selected(c.precision))) return NSR_ERR_INVALID_ARG;   // laid out for another stride
+  c.ray_stride = h.ray_stride;
   Work k;
-  NSR_TRY(open_work(c, w_coarse, w_fine, by_arch, workspace, workspace_bytes, k));
+  NSR_TRY(open_work(c, w_coarse, w_fine, by_arch, workspace, workspace_bytes, k, g_rays != nullptr));
   float* sv = const_cast<float*>(static_cast<const float*>(saved));   // read only
   if (c.chain) {
     for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
@@ -683,8 +694,10 @@ int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const flo
     k.kept = saved_kept(sv, L, c, q);
     const float* const* go = g_outs + 4 * q.net;
     if (!go[0] && hipMemsetAsync(k.g_comp, 0, (size_t)q.rc * 3 * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
+    // the chunk's rows of the ray gradient: the coarse pass writes them, the fine pass adds its part
+    const RayGrad rg{rows_of(g_rays, q, g_ray_stride), g_ray_stride, q.rc, q.N, k.kept.z, q.net};
     return pass_backward(st, k, c, q, q.net ? w_fine : w_coarse, k.kept.z, rows_of(go[0], q, 3, k.g_comp), rows_of(go[1], q, 1),
-                         rows_of(go[2], q, 1), rows_of(go[3], q, q.N), q.net ? g_fine : g_coarse, stream);
+                         rows_of(go[2], q, 1), rows_of(go[3], q, q.N), q.net ? g_fine : g_coarse, stream, g_rays ? &rg : nullptr);
   });
 }
 
@@ -714,6 +727,15 @@ extern "C" size_t nsr_train_arch_workspace_bytes_e(const nsr_arch* arch, unsigne
       chain_selected(precision))
     return 0;
   return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, split_selected(precision), false, nullptr, nullptr) * sizeof(float);
+}
+
+extern "C" size_t nsr_train_arch_workspace_bytes_r(const nsr_arch* arch, unsigned embed, int precision, int64_t ray_chunk,
+                                                   int n_coarse, int n_importance) {
+  Shape S;
+  if (make_shape(arch, S, embed) != NSR_OK || !sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) ||
+      chain_selected(precision))
+    return 0;
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, split_selected(precision), false, nullptr, nullptr, true) * sizeof(float);
 }
 
 extern "C" int nsr_arch_n_tensors(const nsr_arch* arch) {
@@ -852,6 +874,14 @@ extern "C" int nsr_train_arch_backward_e(const nsr_arch* arch, unsigned embed, c
                                          size_t saved_bytes, void* stream) {
   return train_backward(arch, embed, true, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved, saved_bytes,
                         stream);
+}
+
+extern "C" int nsr_train_arch_backward_r(const nsr_arch* arch, unsigned embed, const float* const* w_coarse,
+                                         const float* const* w_fine, const float* const* g_outs, float* const* g_coarse,
+                                         float* const* g_fine, float* g_rays, int g_ray_stride, void* workspace, size_t workspace_bytes,
+                                         const void* saved, size_t saved_bytes, void* stream) {
+  return train_backward(arch, embed, true, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved, saved_bytes,
+                        stream, g_rays, g_ray_stride);
 }
 
 extern "C" int nsr_train_status_reset(void* workspace, void* stream) {

@@ -167,6 +167,124 @@ __global__ void __launch_bounds__(256) reduce_place_kernel(float* __restrict__ d
   float* d = dst + (int64_t)i * dst_ld + dc0 + j;
   *d = (accumulate ? *d : 0.0f) + (float)(s * (double)scale);   // scale: a power of two (pre-scaled operands)
 }
+
+// ---- the gradient with respect to the rays (nsr_train_arch_backward_r) ---------------------------------------------------
+// Backward of encode_arch_kernel's row (the same column map): g_x[p][0..3) = d(loss) / d(x) of sample point p from the
+// gradients of its encoded columns, summed over the n sources (layer 0 and every skip layer, in that order):
+//   identity column c (none under NO_XYZ): g;   band f, sin column: f cos(f x) g;   cos column: -f sin(f x) g
+// with sin / cos the values the forward kept in `enc` (row stride ld_enc).  `lanes` (8, 16 or 32, >= n_groups) lanes share a
+// point, one float4 of columns each; their three partial sums meet in a fixed xor-shuffle order (double arithmetic).
+struct EncodeSrc {
+  const float* p[kMaxD];
+  int n;
+};
+__global__ void __launch_bounds__(256) encode_bwd_kernel(EncodeSrc src, int64_t ld_src, const float* __restrict__ enc, int64_t ld_enc,
+                                                         int64_t P, int deg, int n_groups, int lanes, unsigned embed, NsrBands bands,
+                                                         float* __restrict__ g_x) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t p = idx / lanes;
+  const int g = (int)(idx % lanes);
+  const int first = nsr_embed_first(embed), n_valid = first + 6 * deg;
+  double a[3] = {0.0, 0.0, 0.0};
+  if (p < P && g < n_groups) {
+    double gs[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int j = 0; j < src.n; ++j) {
+      const float4 v = *reinterpret_cast<const float4*>(src.p[j] + p * ld_src + 4 * g);
+      gs[0] += (double)v.x; gs[1] += (double)v.y; gs[2] += (double)v.z; gs[3] += (double)v.w;
+    }
+    const float* row = enc + p * ld_enc;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = 4 * g + e;
+      if (c >= n_valid) continue;
+      double t;
+      int comp;
+      if (c < first) {
+        comp = c;
+        t = gs[e];
+      } else {
+        const int f = (c - first) / 6, r = (c - first) % 6;
+        comp = r % 3;
+        const double band = (embed & NSR_EMBED_LINEAR_FREQS) ? (double)bands.f[f] : (double)ldexpf(1.0f, f);
+        // the partner column of the same band and component: cos for a sin column, sin for a cos column
+        t = r < 3 ? band * (double)row[c + 3] * gs[e] : -(band * (double)row[c - 3] * gs[e]);
+      }
+      a[0] += comp == 0 ? t : 0.0;
+      a[1] += comp == 1 ? t : 0.0;
+      a[2] += comp == 2 ? t : 0.0;
+    }
+  }
+  // every lane of the wave takes part (lanes divides 64: the `lanes` lanes of a point lie in one wave)
+  for (int o = lanes >> 1; o > 0; o >>= 1) {
+    a[0] += __shfl_xor(a[0], o, 64);
+    a[1] += __shfl_xor(a[1], o, 64);
+    a[2] += __shfl_xor(a[2], o, 64);
+  }
+  if (p < P && g < 3) g_x[p * 3 + g] = (float)(g == 0 ? a[0] : (g == 1 ? a[1] : a[2]));
+}
+
+// One wavefront per ray, like the compositor: the ray's row of d(loss) / d(rays) from its N sample points x = o + z d,
+//   g_o = sum_k g_x[k],  g_d = sum_k z[k] g_x[k]     (z does not depend on o or d: include/nsr_train.h)
+// and, with g_dir (N rows of the gradients of the encoded view direction's columns, row stride ld_dir), the direction
+// encoding's backward applied ONCE to their column sums -- every point of a ray holds the same encoded direction, dir_enc is
+// the row of the ray's first point.  It joins g_d at stride 8 (the encoded direction is d) and goes to columns 8:11 at stride 11.
+// Columns 6:8 (near, far) get zeros.  acc: the row is added to (the fine pass after the coarse one).  Double sums, lanes
+// combined by wave_sum_d: a fixed order.
+__global__ void __launch_bounds__(256) ray_grad_kernel(const float* __restrict__ g_x, const float* __restrict__ z, int64_t R, int N,
+                                                       const float* __restrict__ g_dir, int64_t ld_dir,
+                                                       const float* __restrict__ dir_enc, int64_t ld_enc, int deg_dir, unsigned embed,
+                                                       NsrBands bands, float* __restrict__ g_rays, int stride, int acc) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (r >= R) return;   // wave-uniform
+  const int64_t base = r * N;
+  double so[3] = {0.0, 0.0, 0.0}, sd[3] = {0.0, 0.0, 0.0}, dv[3] = {0.0, 0.0, 0.0};
+  for (int k = lane; k < N; k += 64) {
+    const double zk = (double)z[base + k];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double v = (double)g_x[(base + k) * 3 + c];
+      so[c] += v;
+      sd[c] += zk * v;
+    }
+  }
+  if (g_dir) {
+    const int first = nsr_embed_first(embed), n_valid = first + 6 * deg_dir;
+    const float* row = dir_enc + base * ld_enc;
+    for (int c = lane; c < n_valid; c += 64) {
+      double s = 0.0;
+      for (int k = 0; k < N; ++k) s += (double)g_dir[(base + k) * ld_dir + c];
+      double t;
+      int comp;
+      if (c < first) {
+        comp = c;
+        t = s;
+      } else {
+        const int f = (c - first) / 6, q = (c - first) % 6;
+        comp = q % 3;
+        const double band = (embed & NSR_EMBED_LINEAR_FREQS) ? (double)bands.f[f] : (double)ldexpf(1.0f, f);
+        t = q < 3 ? band * (double)row[c + 3] * s : -(band * (double)row[c - 3] * s);
+      }
+      dv[0] += comp == 0 ? t : 0.0;
+      dv[1] += comp == 1 ? t : 0.0;
+      dv[2] += comp == 2 ? t : 0.0;
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    so[c] = wave_sum_d(so[c]);
+    sd[c] = wave_sum_d(sd[c]);
+    dv[c] = wave_sum_d(dv[c]);
+  }
+  // lane j writes column j of the row
+  if (lane >= stride) return;
+  float v = 0.0f;
+  if (lane < 3) v = (float)so[lane];
+  else if (lane < 6) v = (float)(stride == 8 ? sd[lane - 3] + dv[lane - 3] : sd[lane - 3]);
+  else if (lane >= 8) v = (float)dv[lane - 8];
+  float* dst = g_rays + r * stride + lane;
+  *dst = (acc && (lane < 6 || lane >= 8)) ? __fadd_rn(*dst, v) : v;
+}
 }  // namespace
 
 // ---- host wrappers over the kernels above (nsr_train_work.h; the unit tests launch them one by one): the deterministic
@@ -210,6 +328,36 @@ int nsr::colsum(hipStream_t st, const float* src, int64_t ld, int64_t P, int col
   hipLaunchKernelGGL(colsum_few_kernel, dim3(kSumBlocks), dim3(256), 0, st, src, ld, P, col0, cols, part);
   NSR_CHECK_LAUNCH();
   hipLaunchKernelGGL(sum_finish_kernel, dim3((cols + 3) / 4), dim3(256), 0, st, part, kSumBlocks, 4, cols, dst, accumulate);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+
+// g_x (P, 3) from the gradients of the encoded columns of n_src sources (each (P, ld_src), the first 4 n_groups columns read)
+// and the encoded rows the forward kept
+int nsr::encode_bwd(hipStream_t st, const float* const* src, int n_src, int64_t ld_src, const float* enc, int64_t ld_enc, int64_t P,
+                    int deg, int n_groups, unsigned embed, const NsrBands* bands, float* g_x) {
+  if (n_src < 1 || n_src > kMaxD || n_groups < 1 || n_groups > 32 || (ld_src & 3) != 0) return NSR_ERR_INVALID_ARG;
+  if (nsr_embed_first(embed) + 6 * deg > 4 * n_groups || ((embed & NSR_EMBED_LINEAR_FREQS) && !bands)) return NSR_ERR_INVALID_ARG;
+  EncodeSrc s{};
+  for (int j = 0; j < n_src; ++j) s.p[j] = src[j];
+  s.n = n_src;
+  const int lanes = n_groups <= 8 ? 8 : (n_groups <= 16 ? 16 : 32);
+  const int64_t n = P * lanes;
+  if (n == 0) return NSR_OK;
+  hipLaunchKernelGGL(encode_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, s, ld_src, enc, ld_enc, P, deg, n_groups,
+                     lanes, embed, bands ? *bands : NsrBands{}, g_x);
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
+}
+// the R rows of g_rays (R, stride) from g_x (R N, 3), z (R N) and (g_dir non-null) the direction columns' gradients
+int nsr::ray_grad(hipStream_t st, const float* g_x, const float* z, int64_t R, int N, const float* g_dir, int64_t ld_dir,
+                  const float* dir_enc, int64_t ld_enc, int deg_dir, unsigned embed, const NsrBands* bands, float* g_rays,
+                  int stride, int acc) {
+  if (!nsr_ray_stride_ok(stride) || N < 1 || (g_dir && !dir_enc) || ((embed & NSR_EMBED_LINEAR_FREQS) && g_dir && !bands))
+    return NSR_ERR_INVALID_ARG;
+  if (R == 0) return NSR_OK;
+  hipLaunchKernelGGL(ray_grad_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, g_x, z, R, N, g_dir, ld_dir, dir_enc, ld_enc,
+                     deg_dir, embed, bands ? *bands : NsrBands{}, g_rays, stride, acc);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
@@ -436,8 +584,10 @@ int nsr::net_forward(hipStream_t st, const Shape& S, const float* rays, int ray_
 }
 
 // backward of the network from k.d4 (composite_bwd's rows); g: its 2 D + 8 gradient tensors
+// rg (null: none): also this pass's rows of d(loss) / d(rays) -- the input gradients of layer 0, of every skip layer's pe
+// columns and of dir_encoding's direction columns (k.gpe, k.gdir), then encode_bwd and ray_grad
 int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, const Work& k, int64_t P,
-                      float* const* g, int acc, int stop_grad) {
+                      float* const* g, int acc, int stop_grad, const RayGrad* rg) {
   const Kept& s = k.kept;
   const int sp = n_splits(P);
   const int64_t ps = S.part_stride;
@@ -460,6 +610,9 @@ int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, con
   } else {
     NSR_TRY(lin_dgrad(st, k.col_tiles, k.g0, S.Hp, S.Hp, q.wdir, S.Ci, nullptr, 0, k.g1, ldg, P, S.Wp, g[F + 1], acc, S.W));
   }
+  // --stop_grad detaches dir_encoding's whole input, the encoded direction included
+  const bool dir_term = rg && !S.no_dir && !stop_grad;
+  if (dir_term) NSR_TRY(lin_dgrad(st, k.col_tiles, k.g0, S.Hp, S.Hp, q.wdir + S.Wp, S.Ci, nullptr, 0, k.gdir, S.Dp, P, S.Dp, nullptr, 0, 0));
   // xyz_encoding_final + sigma: the (Wp + 32)-row layer over the trunk's last activation
   const Mat hD = out_of(S, s, S.D - 1);
   NSR_TRY(lin_wgrad(st, k.g1, ldg, S.Wp, hD.p, hD.ld, S.Wp, P, part, sp, ps));
@@ -482,6 +635,11 @@ int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, con
     } else {
       NSR_TRY(reduce_place(st, gw, fi, 0, S.W, fi, part, sp, kin, 0, 0, acc, 1.0f, ps));
     }
+    if (rg && (l == 0 || S.skip(l))) {   // the layer reads the encoded position: the gradient of its pe columns
+      const Lin a = trunk_lin(S, q, w, l);
+      NSR_TRY(lin_dgrad(st, k.col_tiles, dy, S.Wp, S.Wp, a.w, a.ldw, nullptr, 0, k.gpe + (int64_t)(l == 0 ? 0 : 1 + S.x_of[l]) * P * S.Kx, S.Kx, P, S.Kx,
+                        nullptr, 0, 0));
+    }
     if (l == 0) break;
     // the layer's input h is the ReLU output of layer l - 1: its mask, and that layer's bias gradient
     const Mat m = out_of(S, s, l - 1);
@@ -490,7 +648,13 @@ int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, con
                       acc, S.W));
     const float* t0 = dy; dy = nx; nx = const_cast<float*>(t0);
   }
-  return NSR_OK;
+  if (!rg) return NSR_OK;
+  const float* src[kMaxD];
+  const int n_src = S.n_pe();   // layer 0 first, then the skip layers upwards
+  for (int j = 0; j < n_src; ++j) src[j] = k.gpe + (int64_t)j * P * S.Kx;
+  NSR_TRY(encode_bwd(st, src, n_src, S.Kx, s.x[0], S.ldx, P, S.arch.deg_pos, S.Kx / 4, S.embed, &S.bands_pos, k.gx));
+  return ray_grad(st, k.gx, rg->z, rg->rays, rg->N, dir_term ? k.gdir : nullptr, S.Dp, s.ci + S.Wp, S.Ci, S.arch.deg_dir, S.embed,
+                  &S.bands_dir, rg->rows, rg->stride, rg->acc);
 }
 
 // a trunk layer without a padded copy is the GEMMs' operand where the caller holds it: 16-byte aligned (include/nsr_train.h)

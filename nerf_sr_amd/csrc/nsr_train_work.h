@@ -66,6 +66,7 @@ struct Shape {
   NsrBands bands_pos, bands_dir;
   bool skip(int l) const { return l > 0 && ((skips >> l) & 1u); }
   int n_tensors() const { return 2 * D + 8; }
+  int n_pe() const { return 1 + __builtin_popcount(skips); }                      // layers that read the encoded position
   int kin(int l) const { return l == 0 ? Kx : (skip(l) ? Xs : Wp); }             // padded fan-in of trunk layer l
   int fan_in(int l) const { return l == 0 ? in_xyz : (skip(l) ? in_xyz + W : W); }
   int dir_in() const { return W + (no_dir ? 0 : in_dir); }
@@ -118,6 +119,19 @@ struct Work {   // the workspace of a call, sized for P_max = chunk * (Nc + Ni) 
   float *stream_f[2], *stream_b[2];
   float* pscale;    // per gradient panel and point: stored value x pscale = true gradient (written by the backward chain)
   unsigned* gmax;   // float bits of the largest magnitude in each gradient panel (written by the backward chain)
+  // the gradient with respect to the rays (nsr_train_arch_backward_r; null otherwise): the gradients of the encoded position's
+  // columns, n_pe() matrices (P, Kx) -- layer 0's, then each skip layer's --, of the encoded direction's columns (P, Dp), and
+  // d(loss) / d(sample point) (P, 3)
+  float *gpe, *gdir, *gx;
+};
+// the pass's rows of d(loss) / d(rays) for net_backward: `rays` rays of N samples at depths z; acc: added to (the fine pass)
+struct RayGrad {
+  float* rows;
+  int stride;
+  int64_t rays;
+  int N;
+  const float* z;
+  int acc;
 };
 
 struct Run {   // the validated arguments of one call
@@ -195,8 +209,24 @@ NSR_INTERNAL int encode_arch(hipStream_t st, const float* rays, int ray_stride, 
 NSR_INTERNAL int net_forward(hipStream_t st, const Shape& S, const float* rays, int ray_stride, const float* z, int N,
                              const float* const* w, const Pack& q, const Kept& s, int64_t P, bool split, int color_none);
 // backward of the network from k.d4 (composite_bwd's rows); g: its 2 D + 8 gradient tensors
+// rg (null: none): also the pass's rows of d(loss) / d(rays), through k.gpe / k.gdir / k.gx
 NSR_INTERNAL int net_backward(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, const Work& k, int64_t P,
-                              float* const* g, int acc, int stop_grad);
+                              float* const* g, int acc, int stop_grad, const RayGrad* rg = nullptr);
+// ---- nsr_train_gemm.hip: the two kernels of the gradient with respect to the rays
+// backward of encode_arch's row: g_x (P, 3) = d(loss) / d(x) from the gradients of the encoded columns, summed over the n_src
+// (1 .. kMaxD) sources src[j] (P, ld_src; ld_src a multiple of 4, rows 16-byte aligned; columns [0, 4 n_groups) are read,
+// n_groups <= 32) in the order given, and the encoded rows `enc` (row stride ld_enc) the forward kept: an identity column
+// passes through (none under NO_XYZ), band f gives f (cos(f x) g_sin - sin(f x) g_cos) with the kept sin / cos and f =
+// 2^k, or bands->f[k] under LINEAR_FREQS.  Sums in double, in a fixed order
+NSR_INTERNAL int encode_bwd(hipStream_t st, const float* const* src, int n_src, int64_t ld_src, const float* enc, int64_t ld_enc,
+                            int64_t P, int deg, int n_groups, unsigned embed, const NsrBands* bands, float* g_x);
+// one wavefront per ray: row r of g_rays (R, stride 8 | 11) (+)= [sum_k g_x[r, k] | sum_k z[r, k] g_x[r, k] | 0 0 | -] over
+// the ray's N samples; g_dir (R N, ld_dir; may be null): the gradients of the encoded direction's columns, whose column sums
+// go through the direction encoding's backward once per ray (dir_enc: the kept encoded direction, row stride ld_enc; the row
+// of the ray's first sample is read) into columns 3:6 at stride 8, columns 8:11 at stride 11.  acc: add to the row
+NSR_INTERNAL int ray_grad(hipStream_t st, const float* g_x, const float* z, int64_t R, int N, const float* g_dir, int64_t ld_dir,
+                          const float* dir_enc, int64_t ld_enc, int deg_dir, unsigned embed, const NsrBands* bands, float* g_rays,
+                          int stride, int acc);
 // ---- nsr_train_gemm.hip: the launchers of the reduction and placement kernels behind the layer-by-layer products
 // dst[(r0 + i) * dst_ld + c0 + j] = src[i * src_ld + col0 + j], i < rows, j < cols (transpose: dst[(r0 + j) * dst_ld + c0 + i]):
 // a copy of bits

@@ -199,7 +199,7 @@ class _TrainRun:
     """The arguments of one forward_rays_train call that are not tensors, and the pair of entry points it runs: the default
     network's, or with ``arch`` (struct nsr_arch) the layer-by-layer pair, which differs by that leading argument only."""
 
-    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace, arch=None, embed: int = 0):
+    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace, arch=None, embed: int = 0, ray_grad: bool = False):
         self.nc, self.ni, self.flags, self.lindisp = nc, ni, flags, lindisp
         self.noise_std, self.prec, self.chunk, self.workspace = noise_std, prec, chunk, workspace
         self.arch = arch
@@ -209,9 +209,12 @@ class _TrainRun:
                       "forward": "nsr_train_forward", "backward": "nsr_train_backward"} if arch is None else \
             {"saved_bytes": "nsr_train_arch_saved_bytes", "workspace_bytes": "nsr_train_arch_workspace_bytes",
              "forward": "nsr_train_arch_forward", "backward": "nsr_train_arch_backward"}
-        if self.embed:      # the embedding's option word behind the descriptor: the `_e` forms of the same four (include/nsr_train.h)
+        self.ray_grad = bool(ray_grad)      # rays that require grad: the `_r` backward and its workspace (always behind a descriptor)
+        if self.embed or self.ray_grad:      # the embedding's option word behind the descriptor: the `_e` forms of the same four (include/nsr_train.h)
             self.lead += (self.embed,)
             self.names = {k: v + "_e" for k, v in self.names.items()}
+        if self.ray_grad:
+            self.names.update(workspace_bytes="nsr_train_arch_workspace_bytes_r", backward="nsr_train_arch_backward_r")
 
     def call(self, what: str, *args):
         """``(name, result)`` of this run's entry point ``what`` on ``args`` behind the leading descriptor."""
@@ -242,7 +245,7 @@ class _ForwardRaysTrain(torch.autograd.Function):
             _p(ws), ws.numel(), _p(saved), saved.numel(), _stream())
         _lib.check(rc, what)
         ctx.save_for_backward(*weights)      # an in-place update of a weight before the backward fails autograd's version check
-        ctx.run, ctx.state = run, saved
+        ctx.run, ctx.state, ctx.rays_shape = run, saved, tuple(rays.shape)
         ctx.set_materialize_grads(False)     # an output the loss does not use arrives as None: a NULL upstream gradient
         return tuple(outs)
 
@@ -257,12 +260,14 @@ class _ForwardRaysTrain(torch.autograd.Function):
         grads = [torch.empty_like(w) for w in weights]
         ws = ctx.run.workspace.get(ctx.ws_need, saved.device)
         nt = len(weights) // 2
+        g_rays = torch.empty(ctx.rays_shape, dtype=torch.float32, device=saved.device) if ctx.run.ray_grad else None
+        to_rays = (_p(g_rays), ctx.rays_shape[1]) if ctx.run.ray_grad else ()      # the `_r` backward: g_rays, g_ray_stride
         what, rc = ctx.run.call(
             "backward", _ptr_array(weights[:nt]), _ptr_array(weights[nt:]), (c_void_p * 8)(*[_p(g) for g in g_outs]),
-            _ptr_array(grads[:nt]), _ptr_array(grads[nt:]), _p(ws), ws.numel(), _p(saved), saved.numel(), _stream())
+            _ptr_array(grads[:nt]), _ptr_array(grads[nt:]), *to_rays, _p(ws), ws.numel(), _p(saved), saved.numel(), _stream())
         _lib.check(rc, what)
         ctx.state = None
-        return (None,) * 6 + tuple(grads)
+        return (None, g_rays) + (None,) * 4 + tuple(grads)
 
 
 def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[Dict[str, Optional[torch.Tensor]]] = None, *,
@@ -286,15 +291,27 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     ``netFine`` built with those flags.  ``precision``: 'fp32' or 'f16x3_gemm' ('f16x3' maps to 'f16x3_gemm' with one
     RuntimeWarning per architecture; the chain names raise ValueError).  None = the default network, as before.
 
+    ``rays`` that require grad get ``d(loss)/d(rays)`` (``nsr_train_arch_backward_r``) when the run is the layer-by-layer pair's:
+    ``arch=`` or ``embed=`` given, or ``precision`` 'fp32' / 'f16x3_gemm' on the default network (which then runs as the default
+    descriptor, the same bits); the chain precisions raise ``ValueError``.  A sample point is ``o + z d`` with ``z`` independent
+    of ``o`` and ``d`` (the fine depths come from the detached coarse weights and near / far only, as in the reference); columns
+    6:8 (near, far) get exact zeros -- the gradient with respect to near / far needs the resampler's backward and is not computed.
+    At 11 columns the direction encoding's part goes to columns 8:11, at 8 it joins columns 3:6; none under ``stop_grad``.
+
     ``embed``: the embedding's option word (``weights.embed_of(opt)``: ``--no_xyz`` / ``--no_logscale``).  A non-zero word runs the
     layer-by-layer pair (``nsr_train_arch_forward_e`` / ``_backward_e``) -- on the default descriptor when ``arch`` is None -- over
     networks whose layer 0, skip layers and ``dir_encoding`` have the option's widths (``weights.arch_spec(no_xyz=...)``)."""
-    if rays.requires_grad:
-        raise ValueError("forward_rays_train: rays must not require grad (there is no gradient with respect to rays)")
+    ray_grad = bool(rays.requires_grad)
+    if ray_grad:      # the tensor the extra gradient is for is looked at first
+        _ray_stride(_f32(rays, "rays"))
+    if ray_grad and arch is None and not int(embed) and precision not in ARCH_PRECISIONS:
+        raise ValueError(f"forward_rays_train: rays require grad under precision={precision!r}: the gradient with respect to rays "
+                         f"is the layer-by-layer pair's, precision {list(ARCH_PRECISIONS)} (or arch= / embed=); the chain kernels "
+                         "do not differentiate through the encodings")
     flags = train_flags(white_bkgd, gamma_correct, sigma_activation, color_activation, stop_grad)
     embed = int(embed)
-    if embed and arch is None:     # the chain kernels have no embedding options: the default network as a descriptor
-        arch = {}
+    if (embed or ray_grad) and arch is None:     # the chain kernels have no embedding options and no ray gradient: the default
+        arch = {}                                # network as a descriptor
     if arch is not None:      # everything about the architecture is checked before a device is touched
         arch = normalize_arch(arch)
         check_embed(embed, arch)
@@ -317,7 +334,7 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
         workspace = _DEFAULT_WS.setdefault(rays.device, TrainWorkspace())
     run = _TrainRun(int(N_coarse), int(N_importance), flags, int(bool(lindisp)), float(noise_std),
                     _lib.TRAIN_PRECISIONS[precision], int(ray_chunk), workspace,
-                    None if arch is None else _lib.NsrArch.from_arch(arch), embed)
+                    None if arch is None else _lib.NsrArch.from_arch(arch), embed, ray_grad)
     outs = _ForwardRaysTrain.apply(run, rays, *d, *wc, *wf)
     return dict(zip(OUT_KEYS, outs))
 
@@ -564,6 +581,7 @@ class Trainer:
             draws = self.draw(rays.shape[0])
         draws = {k: v for k, v in draws.items() if k != "noise_std"}
         lc, lf = self._weight_leaves()
+        self._ray_grad_pending = getattr(self, "_ray_grad_pending", False) or bool(rays.requires_grad)
         return forward_rays_train(lc, lf, rays, draws, N_coarse=self.N_coarse, N_importance=self.N_importance,
                                   white_bkgd=self.white_bkgd, lindisp=self.lindisp, noise_std=self.noise_std,
                                   gamma_correct=self.gamma_correct, sigma_activation=self.sigma_activation,
@@ -573,11 +591,23 @@ class Trainer:
     def backward(self, loss: torch.Tensor):
         """d(loss)/d(weights) of the forwards behind ``loss`` into ``self.grads`` / ``self.flat_grads`` (OVERWRITTEN; scaled by
         1 / world like ``loss_and_grads``, see ``grad_scale``), where ``all_reduce_grads`` and ``optimizer_step`` find them.
-        A weight the loss does not reach gets a zero gradient."""
+        A weight the loss does not reach gets a zero gradient.  Where a forward behind ``loss`` took rays that require grad
+        (``precision`` 'fp32' / 'f16x3_gemm'), the gradient also flows on through them: ``rays.grad`` -- or the ``.grad`` of
+        whatever leaf produced the rays, a pose under ``cameras.rays_from_pose`` -- is accumulated as ``loss.backward()`` does."""
         gs = self._grad_scale()
         leaves = self._weight_leaves()
         flat = leaves[0] + leaves[1]
-        grads = torch.autograd.grad(loss, flat, grad_outputs=None if gs == 1.0 else torch.full_like(loss, gs), allow_unused=True)
+        g_out = None if gs == 1.0 else torch.full_like(loss, gs)
+        if getattr(self, "_ray_grad_pending", False):
+            self._ray_grad_pending = False
+            for l in flat:
+                l.grad = None
+            torch.autograd.backward(loss, g_out)
+            grads = [l.grad for l in flat]
+            for l in flat:
+                l.grad = None
+        else:
+            grads = torch.autograd.grad(loss, flat, grad_outputs=g_out, allow_unused=True)
         dst = list(self.grads[0].values()) + list(self.grads[1].values())
         torch._foreach_copy_([d for d, g in zip(dst, grads) if g is not None], [g for g in grads if g is not None])
         for d, g in zip(dst, grads):
