@@ -5,13 +5,19 @@ A teacher view of the synthetic field of nerf_sr_amd.weights is rendered from a 
 small se(3) offset (a rotation vector and a translation) and, with both networks frozen, the offset is recovered by Adam on the
 photometric loss, BARF / NeRF-- style: pose -> ``cameras.rays_from_pose`` (torch, differentiable) -> ``train.forward_rays_train``
 with rays that require grad (``precision='fp32'``: the layer-by-layer pair, ``nsr_train_arch_backward_r``) -> MSE against the
-teacher's colours -> ``loss.backward()`` fills the offset's gradient.  Prints the rotation / translation error before and after.
+teacher's colours -> ``loss.backward()`` fills the offset's gradient.  Prints the rotation / translation error before and after,
+and the iterations per second of the loop.
 
-    python examples/refine_pose.py [--iters 300] [--batch 512] [--rot 0.02] [--trans 0.02]
+``--chain`` runs the same recovery on ``precision='f16x3'`` with ``chain_ray_grad=True``: the chain pair, whose backward
+(``nsr_train_backward_r``) takes the ray gradient from the backward chain's panels and -- the field being frozen, no weight
+requires grad -- skips the weight-gradient launches (``NSR_BACKWARD_NO_WEIGHT_GRADS``).
+
+    python examples/refine_pose.py [--iters 300] [--batch 512] [--rot 0.02] [--trans 0.02] [--chain]
 """
 import argparse
 import os
 import sys
+import time
 
 import torch
 
@@ -45,11 +51,13 @@ def main():
     ap.add_argument("--rot", type=float, default=0.02, help="norm of the rotation offset (radians)")
     ap.add_argument("--trans", type=float, default=0.02, help="norm of the translation offset")
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--chain", action="store_true", help="the chain pair under precision 'f16x3' (chain_ray_grad=True)")
     a = ap.parse_args()
     W, H, s = 96, 72, 2
     focal = cameras.llff_focal(504) * W / 504
     field = [{k: torch.from_numpy(v).cuda() for k, v in make_state_dict(seed).items()} for seed in (99, 100)]
-    render = lambda rays: train.forward_rays_train(field[0], field[1], rays, None, precision="fp32", ray_chunk=4096)
+    route = dict(precision="f16x3", chain_ray_grad=True) if a.chain else dict(precision="fp32")
+    render = lambda rays: train.forward_rays_train(field[0], field[1], rays, None, ray_chunk=4096, **route)
     c2w_true = torch.from_numpy(cameras.spiral_pose(0.5)).float()
     with torch.no_grad():      # the teacher: the deterministic train-mode forward from the true pose
         out = render(cameras.rays_from_pose(c2w_true.cuda(), H, W, focal, s, True, 0.0, 1.0))
@@ -62,6 +70,8 @@ def main():
     opt = torch.optim.Adam([xi], lr=a.lr)
     r0, t0 = errors(c2w0, c2w_true)
     print(f"before: rotation error {r0:.4f} deg, translation error {t0:.5f}")
+    torch.cuda.synchronize()
+    t_start = time.perf_counter()
     for it in range(a.iters):
         rows = torch.randint(0, (H // s) * (W // s), (a.batch,), generator=gen)
         rows = (rows[:, None] * (s * s) + torch.arange(s * s)[None, :]).reshape(-1).cuda()      # whole LR pixels
@@ -74,6 +84,8 @@ def main():
         if it % 50 == 0 or it == a.iters - 1:
             r, t = errors(compose(c2w0, xi.detach()), c2w_true)
             print(f"iter {it:4d}  loss {float(loss):.3e}  rotation error {r:.4f} deg  translation error {t:.5f}")
+    torch.cuda.synchronize()
+    print(f"{a.iters / (time.perf_counter() - t_start):.2f} iterations/s ({'chain pair, f16x3' if a.chain else 'layer-by-layer pair, fp32'})")
     r1, t1 = errors(compose(c2w0, xi.detach()), c2w_true)
     print(f"after:  rotation error {r1:.4f} deg, translation error {t1:.5f}")
 

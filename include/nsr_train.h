@@ -353,6 +353,31 @@ int nsr_train_arch_backward_r(const nsr_arch* arch, unsigned embed, const float*
                               int g_ray_stride, void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes,
                               void* stream);
 
+/* ---- The same gradient on the CHAIN pair (nsr_train_forward / nsr_train_backward under NSR_F16X3 and its _BWD* variants; the
+ * default network).  After the backward chain the gradient panels hold the masked pre-activation gradients of trunk layer 1, of
+ * the skip layer and of dir_encoding as fp16 `hi` operands; csrc/nsr_train_raygrad_f16.hip multiplies them by the weight columns
+ * of the encoded position / direction (split fp16: W_hi g + W_lo g on v_mfma_f32_32x32x16_f16, fp32 accumulation, the point's
+ * power of two applied once per panel), runs the encodings' backward in registers on sin / cos RECOMPUTED from `rays` and the
+ * saved depths by the forward's own expression, and sums per ray in double: the row layout, the exact zeros of columns 6:8, the
+ * stop_grad rule, "coarse part first, fine part added" and the fixed reduction order are those of nsr_train_arch_backward_r above.
+ *   nsr_train_backward_r with g_rays == NULL and flags == 0 IS nsr_train_backward: the same launches, the same bits, the
+ *   workspace need of nsr_train_workspace_bytes_for (whatever the saved state's precision).
+ *   With g_rays (R, g_ray_stride) it also OVERWRITES that matrix.  `rays` must be the forward call's rays, as the weights must be
+ *   its weights; ray_stride and g_ray_stride must both equal the stride in the saved header, else NSR_ERR_INVALID_ARG.  The
+ *   workspace must hold nsr_train_workspace_bytes_r (>= the _for figure: two (P, 3) matrices and 144 KiB of packed weight
+ *   columns per network), else NSR_ERR_WORKSPACE.  Both are returned before anything is enqueued.
+ *   A saved state of NSR_FP32 / NSR_F16X3_GEMM, or of a non-default descriptor, with g_rays or a flag is NSR_ERR_UNSUPPORTED:
+ *   those have nsr_train_arch_backward_r.
+ *   NSR_BACKWARD_NO_WEIGHT_GRADS (a frozen field): the weight-gradient launch and its finishing launches are not enqueued;
+ *   g_coarse / g_fine may be NULL and are not touched; everything else, g_rays included, has the same bits.  The flag without
+ *   g_rays is NSR_ERR_INVALID_ARG (nothing to compute), as is any other bit.
+ * The saved-state format and nsr_train_saved_bytes are unchanged; the workspace stays pure scratch behind its status block. */
+#define NSR_BACKWARD_NO_WEIGHT_GRADS 1u
+size_t nsr_train_workspace_bytes_r(int precision, int64_t ray_chunk, int n_coarse, int n_importance);
+int nsr_train_backward_r(const float* const* w_coarse, const float* const* w_fine, const float* rays, int ray_stride,
+                         const float* const* g_outs, float* const* g_coarse, float* const* g_fine, float* g_rays, int g_ray_stride,
+                         unsigned flags, void* workspace, size_t workspace_bytes, const void* saved, size_t saved_bytes, void* stream);
+
 /* One nn.Linear (+ activation) on the training GEMM, exposed for testing the kernel on its own:
  *   y (P, N) = act(x (P, K) · w (N, K)^T + b),  act: 0 none, 1 relu, 2 sigmoid;  y_t (N, P) optional transpose.
  * K % 32 == 0, ldx % 4 == 0, ldw % 4 == 0, 16-byte aligned pointers (the training step pads its operands). */

@@ -28,6 +28,7 @@ NSR_WHITE_BKGD, NSR_SIGMA_SOFTPLUS = 1, 2    # include/nsr.h: renderer option wo
 NSR_EMBED_NO_XYZ, NSR_EMBED_LINEAR_FREQS = 1, 2    # include/nsr.h: the embedding's option word (--no_xyz, --no_logscale)
 NSR_LAYOUT_BCHW, NSR_LAYOUT_BHWC = 0, 1      # include/nsr_metrics.h: memory order of nsr_ssim's images
 NSR_LOSS_TV, NSR_LOSS_GRADIENT, NSR_LOSS_LAPLACIAN = 0, 1, 2     # include/nsr_losses.h: `kind` of nsr_loss_workspace_bytes
+NSR_BACKWARD_NO_WEIGHT_GRADS = 1     # include/nsr_train.h: option word of nsr_train_backward_r
 NSR_TRAIN_GAMMA_CORRECT, NSR_TRAIN_COLOR_NONE, NSR_TRAIN_STOP_GRAD = 4, 8, 16    # include/nsr_train.h: the training entry points' own bits of that word
 PRECISIONS = {"fp32": NSR_FP32, "bf16": NSR_BF16, "f16x3": NSR_F16X3, "f16": NSR_F16}
 NSR_F16X3_BWD3, NSR_F16X3_BWD2, NSR_F16X3_BWD1, NSR_F16X3_BWDM = 19, 20, 21, 22   # chain path, MFMAs per product of the backward chain named explicitly
@@ -169,6 +170,11 @@ SIGNATURES = {
     "nsr_train_arch_backward_r": (c_int, [POINTER(NsrArch), c_uint, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                           POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_size_t,
                                           c_void_p]),
+    # the same on the chain pair: the forward call's rays and their stride in front of the upstream gradients, g_rays,
+    # g_ray_stride and the option word (NSR_BACKWARD_NO_WEIGHT_GRADS) behind the gradient arrays
+    "nsr_train_workspace_bytes_r": (c_size_t, [c_int, c_int64, c_int, c_int]),
+    "nsr_train_backward_r": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p),
+                                     POINTER(c_void_p), c_void_p, c_int, c_uint, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     "nsr_arch_fused_packed_bytes_e": (c_size_t, [POINTER(NsrArch), c_uint]),
     "nsr_arch_fused_pack_e": (c_int, [POINTER(NsrArch), c_uint, POINTER(c_void_p), c_void_p, c_void_p, c_void_p]),
     "nsr_arch_fused_forward_e": (c_int, [POINTER(NsrArch), c_uint, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64,

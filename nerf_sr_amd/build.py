@@ -30,6 +30,7 @@ UNITS = [
     ("nsr_gemm_f16.hip", ["-ffp-contract=off"]),
     ("nsr_wgrad_f16.hip", ["-ffp-contract=off"]),
     ("nsr_train_wgrad.hip", ["-ffp-contract=off"]),
+    ("nsr_train_raygrad_f16.hip", ["-ffp-contract=off"]),
     ("nsr_train.hip", ["-ffp-contract=off"]),
     ("nsr_train_gemm.hip", ["-ffp-contract=off"]),
     ("nsr_train_chain.hip", ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
@@ -181,6 +182,10 @@ if os.path.exists(_REDUCE_HOOKS_SRC):
 _RAYGRAD_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_raygrad.hip")
 if os.path.exists(_RAYGRAD_HOOKS_SRC):
     TEST_HOOKS_SRCS.append(_RAYGRAD_HOOKS_SRC)
+# ... and the packer and the launcher of the chain path's ray gradient (tests/test_gpu_chain_ray_grad_units.py); same condition
+_CHAIN_RAYGRAD_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_chain_raygrad.hip")
+if os.path.exists(_CHAIN_RAYGRAD_HOOKS_SRC):
+    TEST_HOOKS_SRCS.append(_CHAIN_RAYGRAD_HOOKS_SRC)
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -336,9 +336,11 @@ int64_t work_floats(int64_t chunk, int nc, int ni, const Shape* net, bool split,
     k.stream_b[n] = a.take((int64_t)(nsr_chain_bwd_packed_bytes() / 4), chain_path);
   }
   const bool rg = ray_grad && net;
+  const bool rgc = ray_grad && chain_path && !net;   // nsr_train_backward_r: per point (P, 3) + (P, 3), the packed columns
   k.gpe = a.take(rg ? net->n_pe() * P * net->Kx : 0, rg);
-  k.gdir = a.take(rg ? P * net->Dp : 0, rg && net->Dp > 0);
-  k.gx = a.take(P * 3, rg);
+  k.gdir = a.take(rg ? P * net->Dp : P * 3, (rg && net->Dp > 0) || rgc);
+  k.gx = a.take(P * 3, rg || rgc);
+  for (int n = 0; n < 2; ++n) k.rgw[n] = a.take(kRayGradImageFloats, rgc);
   return a.off;
 }
 
@@ -548,13 +550,16 @@ int pass_forward(hipStream_t st, const Work& k, const Run& c, const Pass& q, con
 // tensors, overwritten or accumulated (q.acc)
 int pass_backward(hipStream_t st, const Work& k, const Run& c, const Pass& q, const float* const* w, const float* z,
                   const float* g_comp, const float* g_depth, const float* g_opacity, const float* g_weights, float* const* g,
-                  void* stream, const RayGrad* rg = nullptr) {
+                  void* stream, const RayGrad* rg = nullptr, bool weight_grads = true) {
   NSR_TRY(composite_bwd(st, k.kept.rgb, k.kept.sig, z, g_comp, q.rc, q.N, c.flags, k.d4, c.chain ? k.gmax : nullptr,
                         c.chain ? k.bias_part : nullptr, g_depth, g_opacity, g_weights));
   if (c.chain) {
     NSR_TRY(nsr_chain_bwd(k.stream_b[q.net], k.kept.sgn, k.dpan, k.d4, 4, k.d4 + 3, 4, q.P, k.gmax, k.pscale,
                           chain_bwd_terms(c.precision), 1, stream));
-    return chain_weight_grads(st, k, q.P, q.rc, g, q.acc);
+    if (rg)   // the panels hold what the ray gradient needs: three products with the columns the chain does not multiply by
+      NSR_TRY(raygrad_f16(st, k.rgw[q.net], k.dpan, k.pscale, rg->in, c.ray_stride, rg->z, rg->rays, rg->N,
+                          (c.flags & NSR_TRAIN_STOP_GRAD) != 0, k.gx, k.gdir, rg->rows, rg->acc));
+    return weight_grads ? chain_weight_grads(st, k, q.P, q.rc, g, q.acc) : NSR_OK;
   }
   return net_backward(st, c.net, w, k.pack[q.net], k, q.P, g, q.acc, (c.flags & NSR_TRAIN_STOP_GRAD) != 0, rg);
 }
@@ -651,14 +656,32 @@ int train_forward(const nsr_arch* arch, unsigned embed, bool by_arch, const floa
   });
 }
 
+// nsr_train_backward_r: the forward call's rays and the call's option word (null: every other backward entry point)
+struct ChainRays {
+  const float* rays;
+  int ray_stride;
+  unsigned flags;
+};
 int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const float* const* w_coarse, const float* const* w_fine,
                    const float* const* g_outs, float* const* g_coarse, float* const* g_fine, void* workspace, size_t workspace_bytes,
-                   const void* saved, size_t saved_bytes, void* stream, float* g_rays = nullptr, int g_ray_stride = 0) {
+                   const void* saved, size_t saved_bytes, void* stream, float* g_rays = nullptr, int g_ray_stride = 0,
+                   const ChainRays* cr = nullptr) {
   Run c{};   // no sampling in this half: lindisp and noise_std stay unused
   if (g_rays && !nsr_ray_stride_ok(g_ray_stride)) return NSR_ERR_INVALID_ARG;
+  const bool weight_grads = !(cr && (cr->flags & NSR_BACKWARD_NO_WEIGHT_GRADS));
+  const bool chain_r = cr && (g_rays || cr->flags != 0u);   // what only a chain precision's saved state can serve
+  if (cr) {
+    if ((cr->flags & ~NSR_BACKWARD_NO_WEIGHT_GRADS) != 0u || (!weight_grads && !g_rays)) return NSR_ERR_INVALID_ARG;
+    if (g_rays && (!cr->rays || cr->ray_stride != g_ray_stride)) return NSR_ERR_INVALID_ARG;
+  }
   NSR_TRY(make_shape(arch, c.net, embed));
-  NSR_TRY(check_args({{w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, saved}, {w_coarse, w_fine, g_coarse, g_fine},
-                      nullptr, {}, {workspace, saved}, c.net.n_tensors(), by_arch}, nullptr, 1));
+  if (weight_grads) {
+    NSR_TRY(check_args({{w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, saved}, {w_coarse, w_fine, g_coarse, g_fine},
+                        nullptr, {}, {workspace, saved}, c.net.n_tensors(), by_arch}, nullptr, 1));
+  } else {   // no gradient tensor is written: the two arrays may be null
+    NSR_TRY(check_args({{w_coarse, w_fine, g_outs, workspace, saved}, {w_coarse, w_fine}, nullptr, {}, {workspace, saved},
+                        c.net.n_tensors(), by_arch}, nullptr, 1));
+  }
   if (saved_bytes < (size_t)kSavedHeaderFloats * sizeof(float)) return NSR_ERR_WORKSPACE;
   // the run's parameters, read back from the header the forward call wrote (waits for the stream)
   hipStream_t st = nsr_stream(stream);
@@ -667,7 +690,8 @@ int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const flo
   if (hipStreamSynchronize(st) != hipSuccess) return NSR_ERR_LAUNCH;
   if (h.magic != kSavedMagic) return NSR_ERR_INVALID_ARG;
   if (h.floats > saved_bytes / sizeof(float)) return NSR_ERR_WORKSPACE;   // the header says the state is larger than the buffer
-  if (!same_arch(h.arch, c.net.arch) || h.embed != embed) return NSR_ERR_INVALID_ARG;   // the forward ran another network
+  if (!same_arch(h.arch, c.net.arch) || h.embed != embed)   // the forward ran another network
+    return chain_r ? NSR_ERR_UNSUPPORTED : NSR_ERR_INVALID_ARG;
   // bounds before anything loops over them (a damaged header may hold anything): every ray and every chunk takes at least
   // 64 floats of the layout, so neither count can exceed what the buffer holds
   if (h.R <= 0 || h.chunk <= 0 || h.chunk > h.R || (uint64_t)h.R > h.floats / 64 ||
@@ -678,13 +702,16 @@ int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const flo
     return NSR_ERR_INVALID_ARG;
   const SavedLayout L = saved_layout(c.net, c.precision, c.R, c.nc, c.ni, c.chunk);
   if ((uint64_t)L.total != h.floats) return NSR_ERR_INVALID_ARG;
-  if (g_rays && (h.ray_stride != g_ray_stride || chain_selected(c.precision))) return NSR_ERR_INVALID_ARG;   // laid out for another stride
+  if (chain_r && !chain_selected(c.precision)) return NSR_ERR_UNSUPPORTED;   // those have nsr_train_arch_backward_r
+  if (g_rays && (h.ray_stride != g_ray_stride || (chain_selected(c.precision) && !chain_r)))
+    return NSR_ERR_INVALID_ARG;   // laid out for another stride
   c.ray_stride = h.ray_stride;
   Work k;
   NSR_TRY(open_work(c, w_coarse, w_fine, by_arch, workspace, workspace_bytes, k, g_rays != nullptr));
   float* sv = const_cast<float*>(static_cast<const float*>(saved));   // read only
   if (c.chain) {
     for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
+    if (g_rays) NSR_TRY(raygrad_f16_pack(st, w_coarse, k.rgw[0], w_fine, k.rgw[1]));
   } else {   // the padded weight copies the backward products read (no split halves: every gradient runs on the fp32 MFMA)
     NSR_TRY(prepare_weights(st, c.net, w_coarse, k.pack[0], false));
     NSR_TRY(prepare_weights(st, c.net, w_fine, k.pack[1], false));
@@ -695,9 +722,11 @@ int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const flo
     const float* const* go = g_outs + 4 * q.net;
     if (!go[0] && hipMemsetAsync(k.g_comp, 0, (size_t)q.rc * 3 * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
     // the chunk's rows of the ray gradient: the coarse pass writes them, the fine pass adds its part
-    const RayGrad rg{rows_of(g_rays, q, g_ray_stride), g_ray_stride, q.rc, q.N, k.kept.z, q.net};
+    const RayGrad rg{rows_of(g_rays, q, g_ray_stride), g_ray_stride, q.rc, q.N, k.kept.z, q.net,
+                     cr && cr->rays ? cr->rays + q.r0 * c.ray_stride : nullptr};
     return pass_backward(st, k, c, q, q.net ? w_fine : w_coarse, k.kept.z, rows_of(go[0], q, 3, k.g_comp), rows_of(go[1], q, 1),
-                         rows_of(go[2], q, 1), rows_of(go[3], q, q.N), q.net ? g_fine : g_coarse, stream, g_rays ? &rg : nullptr);
+                         rows_of(go[2], q, 1), rows_of(go[3], q, q.N), q.net ? g_fine : g_coarse, stream, g_rays ? &rg : nullptr,
+                         weight_grads);
   });
 }
 
@@ -882,6 +911,22 @@ extern "C" int nsr_train_arch_backward_r(const nsr_arch* arch, unsigned embed, c
                                          const void* saved, size_t saved_bytes, void* stream) {
   return train_backward(arch, embed, true, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved, saved_bytes,
                         stream, g_rays, g_ray_stride);
+}
+
+extern "C" size_t nsr_train_workspace_bytes_r(int precision, int64_t ray_chunk, int n_coarse, int n_importance) {
+  Shape S;
+  if (!sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) || make_shape(&kDefaultArch, S) != NSR_OK) return 0;
+  const bool chain = chain_selected(precision);
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, chain ? nullptr : &S, true, chain, nullptr, nullptr, chain) * sizeof(float);
+}
+
+extern "C" int nsr_train_backward_r(const float* const* w_coarse, const float* const* w_fine, const float* rays, int ray_stride,
+                                    const float* const* g_outs, float* const* g_coarse, float* const* g_fine, float* g_rays,
+                                    int g_ray_stride, unsigned flags, void* workspace, size_t workspace_bytes, const void* saved,
+                                    size_t saved_bytes, void* stream) {
+  const ChainRays cr{rays, ray_stride, flags};
+  return train_backward(&kDefaultArch, 0u, false, w_coarse, w_fine, g_outs, g_coarse, g_fine, workspace, workspace_bytes, saved,
+                        saved_bytes, stream, g_rays, g_ray_stride, &cr);
 }
 
 extern "C" int nsr_train_status_reset(void* workspace, void* stream) {

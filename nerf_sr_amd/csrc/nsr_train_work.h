@@ -123,6 +123,9 @@ struct Work {   // the workspace of a call, sized for P_max = chunk * (Nc + Ni) 
   // columns, n_pe() matrices (P, Kx) -- layer 0's, then each skip layer's --, of the encoded direction's columns (P, Dp), and
   // d(loss) / d(sample point) (P, 3)
   float *gpe, *gdir, *gx;
+  // chain path, nsr_train_backward_r with g_rays (null otherwise): gx (P, 3) and gdir (P, 3) = per point d(loss) / d(x) and the
+  // back-propagated direction term, and per network the packed weight columns of raygrad_f16 (kRayGradPieces KiB)
+  float* rgw[2];
 };
 // the pass's rows of d(loss) / d(rays) for net_backward: `rays` rays of N samples at depths z; acc: added to (the fine pass)
 struct RayGrad {
@@ -132,6 +135,7 @@ struct RayGrad {
   int N;
   const float* z;
   int acc;
+  const float* in = nullptr;   // chain path: the pass's rows of the forward call's rays (the encodings are recomputed from them)
 };
 
 struct Run {   // the validated arguments of one call
@@ -227,6 +231,21 @@ NSR_INTERNAL int encode_bwd(hipStream_t st, const float* const* src, int n_src, 
 NSR_INTERNAL int ray_grad(hipStream_t st, const float* g_x, const float* z, int64_t R, int N, const float* g_dir, int64_t ld_dir,
                           const float* dir_enc, int64_t ld_enc, int deg_dir, unsigned embed, const NsrBands* bands, float* g_rays,
                           int stride, int acc);
+// ---- nsr_train_raygrad_f16.hip: the gradient with respect to the rays on the chain path, from the backward chain's panels
+constexpr int kRayGradPieces = 144;                     // 1 KiB pieces of one network's packed columns: 64 + 64 + 16
+constexpr int64_t kRayGradImageFloats = kRayGradPieces * 256;
+// 64 w of xyz_encoding_1.weight, xyz_encoding_5.weight[:, 0:63] and dir_encoding.0.weight[:, 256:283] of both networks, split into
+// fp16 (hi, lo) and laid out as the MFMA A fragments of raygrad_f16 (one launch; img_*: kRayGradImageFloats floats, 16-byte aligned)
+NSR_INTERNAL int raygrad_f16_pack(hipStream_t st, const float* const* w_coarse, float* img_coarse, const float* const* w_fine,
+                                  float* img_fine);
+// one pass, after nsr_chain_bwd has filled dpan / pscale for its P = R N points (a multiple of 32, else NSR_ERR_UNSUPPORTED):
+// g_pe = dz_1 W_1 + dz_5 W_5[:, 0:63] and g_de = dz_dir W_dir[:, 256:] on the fp16 MFMA (W_hi g + W_lo g, pscale behind each
+// panel's partial sum), the encodings' backward in registers on sin / cos recomputed from rays (R, ray_stride) and z (R, N) by
+// the forward's expression -> g_x (P, 3), g_dv (P, 3) (scratch), then ray_grad: row r of g_rays (R, ray_stride) (+)= [sum_k g_x |
+// sum_k z g_x (+ sum_k g_dv at stride 8) | 0 0 | sum_k g_dv at stride 11].  stop_grad: no direction term (exact zeros)
+NSR_INTERNAL int raygrad_f16(hipStream_t st, const float* img, const char* dpan, const float* pscale, const float* rays,
+                             int ray_stride, const float* z, int64_t R, int N, int stop_grad, float* g_x, float* g_dv, float* g_rays,
+                             int acc);
 // ---- nsr_train_gemm.hip: the launchers of the reduction and placement kernels behind the layer-by-layer products
 // dst[(r0 + i) * dst_ld + c0 + j] = src[i * src_ld + col0 + j], i < rows, j < cols (transpose: dst[(r0 + j) * dst_ld + c0 + i]):
 // a copy of bits

@@ -199,7 +199,8 @@ class _TrainRun:
     """The arguments of one forward_rays_train call that are not tensors, and the pair of entry points it runs: the default
     network's, or with ``arch`` (struct nsr_arch) the layer-by-layer pair, which differs by that leading argument only."""
 
-    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace, arch=None, embed: int = 0, ray_grad: bool = False):
+    def __init__(self, nc, ni, flags, lindisp, noise_std, prec, chunk, workspace, arch=None, embed: int = 0, ray_grad: bool = False,
+                 chain_ray_grad: bool = False):
         self.nc, self.ni, self.flags, self.lindisp = nc, ni, flags, lindisp
         self.noise_std, self.prec, self.chunk, self.workspace = noise_std, prec, chunk, workspace
         self.arch = arch
@@ -215,6 +216,12 @@ class _TrainRun:
             self.names = {k: v + "_e" for k, v in self.names.items()}
         if self.ray_grad:
             self.names.update(workspace_bytes="nsr_train_arch_workspace_bytes_r", backward="nsr_train_arch_backward_r")
+        # rays that require grad on the chain pair (the default network under a chain precision, opt-in): the forward is
+        # nsr_train_forward as it is, the backward nsr_train_backward_r, which also takes the rays and an option word
+        self.chain_ray_grad = bool(chain_ray_grad)
+        if self.chain_ray_grad:
+            assert arch is None and not self.embed and not self.ray_grad
+            self.names.update(workspace_bytes="nsr_train_workspace_bytes_r", backward="nsr_train_backward_r")
 
     def call(self, what: str, *args):
         """``(name, result)`` of this run's entry point ``what`` on ``args`` behind the leading descriptor."""
@@ -244,7 +251,9 @@ class _ForwardRaysTrain(torch.autograd.Function):
             _p(u_c), _p(u_f), _p(n_c), _p(n_f), run.noise_std, run.prec, run.chunk, _ptr_array(outs),
             _p(ws), ws.numel(), _p(saved), saved.numel(), _stream())
         _lib.check(rc, what)
-        ctx.save_for_backward(*weights)      # an in-place update of a weight before the backward fails autograd's version check
+        # an in-place update of a weight before the backward fails autograd's version check; the chain pair's ray gradient
+        # recomputes the encodings from the rays, which are therefore kept the same way
+        ctx.save_for_backward(*weights, *((rays,) if run.chain_ray_grad else ()))
         ctx.run, ctx.state, ctx.rays_shape = run, saved, tuple(rays.shape)
         ctx.set_materialize_grads(False)     # an output the loss does not use arrives as None: a NULL upstream gradient
         return tuple(outs)
@@ -257,6 +266,8 @@ class _ForwardRaysTrain(torch.autograd.Function):
         if saved is None:
             raise RuntimeError("forward_rays_train: the saved state of this forward was released by its first backward")
         g_outs = [None if g is None else g.to(torch.float32).contiguous() for g in g_outs]
+        if ctx.run.chain_ray_grad:
+            return _ForwardRaysTrain._backward_chain_rays(ctx, weights[:-1], weights[-1], g_outs)
         grads = [torch.empty_like(w) for w in weights]
         ws = ctx.run.workspace.get(ctx.ws_need, saved.device)
         nt = len(weights) // 2
@@ -269,12 +280,32 @@ class _ForwardRaysTrain(torch.autograd.Function):
         ctx.state = None
         return (None, g_rays) + (None,) * 4 + tuple(grads)
 
+    @staticmethod
+    def _backward_chain_rays(ctx, weights, rays, g_outs):
+        """``nsr_train_backward_r``: d(loss)/d(rays) from the backward chain's panels; a frozen field (no weight leaf needs a
+        gradient) skips the weight-gradient launches."""
+        saved = ctx.state
+        nt = len(weights) // 2
+        frozen = not any(ctx.needs_input_grad[6:])
+        grads = [] if frozen else [torch.empty_like(w) for w in weights]
+        ws = ctx.run.workspace.get(ctx.ws_need, saved.device)
+        g_rays = torch.empty(ctx.rays_shape, dtype=torch.float32, device=saved.device)
+        what, rc = ctx.run.call(
+            "backward", _ptr_array(weights[:nt]), _ptr_array(weights[nt:]), _p(rays), ctx.rays_shape[1],
+            (c_void_p * 8)(*[_p(g) for g in g_outs]), None if frozen else _ptr_array(grads[:nt]),
+            None if frozen else _ptr_array(grads[nt:]), _p(g_rays), ctx.rays_shape[1],
+            _lib.NSR_BACKWARD_NO_WEIGHT_GRADS if frozen else 0, _p(ws), ws.numel(), _p(saved), saved.numel(), _stream())
+        _lib.check(rc, what)
+        ctx.state = None
+        return (None, g_rays) + (None,) * 4 + (tuple(grads) if not frozen else (None,) * len(weights))
+
 
 def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[Dict[str, Optional[torch.Tensor]]] = None, *,
                        N_coarse: int = 64, N_importance: int = 64, white_bkgd: bool = False, lindisp: bool = False,
                        noise_std: float = 0.0, gamma_correct: bool = False, sigma_activation: str = "relu",
                        color_activation: str = "sigmoid", stop_grad: bool = False, precision: str = "f16x3",
-                       ray_chunk: int = 0, workspace: Optional[TrainWorkspace] = None, arch=None, embed: int = 0) -> Dict[str, torch.Tensor]:
+                       ray_chunk: int = 0, workspace: Optional[TrainWorkspace] = None, arch=None, embed: int = 0,
+                       chain_ray_grad: bool = False) -> Dict[str, torch.Tensor]:
     """Train-mode ``forward_rays`` (``models/nerf_downX_model.py:280-313``) that autograd differentiates with respect to the
     24 + 24 weight tensors of ``params_c`` / ``params_f`` (the reference's ``netCoarse`` / ``netFine`` modules, their
     parameter lists, or state-dict-like dicts such as ``Trainer.params``).  Returns the eight ``OUT_KEYS`` outputs; any loss
@@ -298,12 +329,23 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     6:8 (near, far) get exact zeros -- the gradient with respect to near / far needs the resampler's backward and is not computed.
     At 11 columns the direction encoding's part goes to columns 8:11, at 8 it joins columns 3:6; none under ``stop_grad``.
 
+    ``chain_ray_grad=True`` (opt-in) lifts that refusal: rays that require grad under a chain precision on the default network
+    run the chain pair, and the backward is ``nsr_train_backward_r`` -- three small products of the backward chain's gradient
+    panels with the weight columns of the encoded position / direction on the fp16 MFMA, the encodings' backward on sin / cos
+    recomputed from the rays (which are saved like the weights: an in-place change before the backward is an error).  The
+    outputs and the weight gradients have the bits of the same call with rays that do not require grad.  When no weight needs
+    a gradient (a frozen field) the weight-gradient launches are skipped.  With ``arch=`` / ``embed=`` or 'fp32' / 'f16x3_gemm'
+    the keyword has no effect: those run the layer-by-layer pair as above.
+
     ``embed``: the embedding's option word (``weights.embed_of(opt)``: ``--no_xyz`` / ``--no_logscale``).  A non-zero word runs the
     layer-by-layer pair (``nsr_train_arch_forward_e`` / ``_backward_e``) -- on the default descriptor when ``arch`` is None -- over
     networks whose layer 0, skip layers and ``dir_encoding`` have the option's widths (``weights.arch_spec(no_xyz=...)``)."""
     ray_grad = bool(rays.requires_grad)
     if ray_grad:      # the tensor the extra gradient is for is looked at first
         _ray_stride(_f32(rays, "rays"))
+    chain_rays = ray_grad and bool(chain_ray_grad) and arch is None and not int(embed) and precision not in ARCH_PRECISIONS
+    if chain_rays:
+        ray_grad = False      # the chain pair itself: no descriptor, nsr_train_backward_r behind nsr_train_forward
     if ray_grad and arch is None and not int(embed) and precision not in ARCH_PRECISIONS:
         raise ValueError(f"forward_rays_train: rays require grad under precision={precision!r}: the gradient with respect to rays "
                          f"is the layer-by-layer pair's, precision {list(ARCH_PRECISIONS)} (or arch= / embed=); the chain kernels "
@@ -334,7 +376,7 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
         workspace = _DEFAULT_WS.setdefault(rays.device, TrainWorkspace())
     run = _TrainRun(int(N_coarse), int(N_importance), flags, int(bool(lindisp)), float(noise_std),
                     _lib.TRAIN_PRECISIONS[precision], int(ray_chunk), workspace,
-                    None if arch is None else _lib.NsrArch.from_arch(arch), embed, ray_grad)
+                    None if arch is None else _lib.NsrArch.from_arch(arch), embed, ray_grad, chain_rays)
     outs = _ForwardRaysTrain.apply(run, rays, *d, *wc, *wf)
     return dict(zip(OUT_KEYS, outs))
 
@@ -358,7 +400,10 @@ class Trainer:
                  use_var_loss: bool = False, lambda_coarse_var: float = 0.01, lambda_fine_var: float = 0.01,
                  use_depth_var_loss: bool = False, lambda_coarse_depth_var: float = 0.01, lambda_fine_depth_var: float = 0.01,
                  no_dir: bool = False, sigma_activation: str = "relu", color_activation: str = "sigmoid", stop_grad: bool = False,
-                 grad_clip_val: float = 0.0, grad_clip_type: str = "norm", arch=None, embed: int = 0):
+                 grad_clip_val: float = 0.0, grad_clip_type: str = "norm", arch=None, embed: int = 0, chain_ray_grad: bool = False):
+        # chain_ray_grad: forward() / backward() on rays that require grad run the chain pair under a chain precision
+        # (forward_rays_train); the fused step does not differentiate with respect to rays either way
+        self.chain_ray_grad = bool(chain_ray_grad)
         # embed: the embedding's option word (weights.embed_of(opt): --no_xyz / --no_logscale).  Non-zero: the architecture route
         # below (on the default descriptor when arch is None) with the `_e` pair; precision 'fp32' or 'f16x3_gemm'
         self.embed = int(embed)
@@ -586,13 +631,14 @@ class Trainer:
                                   white_bkgd=self.white_bkgd, lindisp=self.lindisp, noise_std=self.noise_std,
                                   gamma_correct=self.gamma_correct, sigma_activation=self.sigma_activation,
                                   color_activation=self.color_activation, stop_grad=self.stop_grad, precision=self.precision,
-                                  ray_chunk=self.ray_chunk, workspace=self._workspace, arch=self.arch, embed=self.embed)
+                                  ray_chunk=self.ray_chunk, workspace=self._workspace, arch=self.arch, embed=self.embed,
+                                  chain_ray_grad=self.chain_ray_grad)
 
     def backward(self, loss: torch.Tensor):
         """d(loss)/d(weights) of the forwards behind ``loss`` into ``self.grads`` / ``self.flat_grads`` (OVERWRITTEN; scaled by
         1 / world like ``loss_and_grads``, see ``grad_scale``), where ``all_reduce_grads`` and ``optimizer_step`` find them.
         A weight the loss does not reach gets a zero gradient.  Where a forward behind ``loss`` took rays that require grad
-        (``precision`` 'fp32' / 'f16x3_gemm'), the gradient also flows on through them: ``rays.grad`` -- or the ``.grad`` of
+        (``precision`` 'fp32' / 'f16x3_gemm', or a chain precision with ``chain_ray_grad=True``), the gradient also flows on through them: ``rays.grad`` -- or the ``.grad`` of
         whatever leaf produced the rays, a pose under ``cameras.rays_from_pose`` -- is accumulated as ``loss.backward()`` does."""
         gs = self._grad_scale()
         leaves = self._weight_leaves()
