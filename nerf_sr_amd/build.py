@@ -7,6 +7,7 @@ is MFMA code where fused accumulation is inherent.
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -129,63 +130,12 @@ def build(force: bool = False, verbose: bool = True, variant: str = "", defines=
 
 
 # ---- test-hook library (tests/hooks.py): the product's own objects -- same sources, same flags, the very files libnsr.so is
-# linked from -- plus ONE extra unit that lives with the tests and exports C wrappers over the library-internal matrix
-# kernels (nsr::gemm, gemm_f16x3, wgrad_jobs_plan, wgrad_jobs_f16).  A second link, not a variant: no define, no #if in csrc/,
-# libnsr.so and its export list stay as they are.
-TEST_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks.hip")
-# ... and the render launch with its skipped-window counter (tests/test_gpu_empty_skip.py)
-TEST_HOOKS_SRCS = [TEST_HOOKS_SRC, os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_render.hip")]
-# ... and the same launch with early ray termination and both of its counters (tests/test_gpu_early_stop.py)
-TEST_HOOKS_SRCS.append(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_ert.hip"))
-# ... and the render launch's counter at 192 and 256 samples, which the wrapper above refuses (tests/test_gpu_testtime.py)
-TEST_HOOKS_SRCS.append(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_testtime.hip"))
-# ... and the kernel choice of gemm_f16x3 as a value, and the explicit im2col (tests/test_gpu_conv_units.py)
-# (linked only where tests/ carries it: tests/hooks.py binds its two symbols by name, so a tests/ directory that uses them
-# without the unit fails when the library is loaded, and one from before the unit existed builds as it always did)
-_CONV_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_conv.hip")
-if os.path.exists(_CONV_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_CONV_HOOKS_SRC)
-# ... and the backward chain's packer, launch and size queries (tests/test_gpu_chain_units.py); linked on the same condition
-_CHAIN_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_chain.hip")
-if os.path.exists(_CHAIN_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_CHAIN_HOOKS_SRC)
-# ... and the launchers of the compositing backward, the loss head, the density noise and the per-sample gamma
-# (tests/test_gpu_train_heads.py); linked on the same condition
-_HEADS_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_heads.hip")
-if os.path.exists(_HEADS_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_HEADS_HOOKS_SRC)
-# ... and the launchers of the refinement network's train-mode kernels, csrc/nsr_refine_train_work.h
-# (tests/test_gpu_refine_units.py); linked on the same condition
-_REFINE_TRAIN_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_train.hip")
-if os.path.exists(_REFINE_TRAIN_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_REFINE_TRAIN_HOOKS_SRC)
-# ... and the launchers of its split-fp16 forward and input gradient (tests/test_gpu_refine_mixed_units.py); same condition
-_REFINE_MIXED_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_mixed.hip")
-if os.path.exists(_REFINE_MIXED_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_REFINE_MIXED_HOOKS_SRC)
-# ... and the launcher of its implicit split-fp16 weight gradient (tests/test_gpu_refine_wgrad_units.py); same condition
-_REFINE_WGRAD_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_refine_wgrad.hip")
-if os.path.exists(_REFINE_WGRAD_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_REFINE_WGRAD_HOOKS_SRC)
-# ... and nsr_sincos per element, the run-time-degree encoder's launcher and the TRAIN forward with its encoding panels
-# (tests/test_gpu_encoding.py); same condition
-_ENCODE_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_encode.hip")
-if os.path.exists(_ENCODE_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_ENCODE_HOOKS_SRC)
-# ... and the launchers of the gradient reduction and placement kernels of both training paths, and chain_weight_grads as a
-# whole (tests/test_gpu_train_reduce_units.py, test_gpu_train_finish_jobs.py, test_gpu_chain_weight_grads.py); same condition
-_REDUCE_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_reduce.hip")
-if os.path.exists(_REDUCE_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_REDUCE_HOOKS_SRC)
-# ... and the launchers of the two kernels of the gradient with respect to the rays (tests/test_gpu_ray_grad_units.py); same
-# condition
-_RAYGRAD_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_raygrad.hip")
-if os.path.exists(_RAYGRAD_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_RAYGRAD_HOOKS_SRC)
-# ... and the packer and the launcher of the chain path's ray gradient (tests/test_gpu_chain_ray_grad_units.py); same condition
-_CHAIN_RAYGRAD_HOOKS_SRC = os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks_chain_raygrad.hip")
-if os.path.exists(_CHAIN_RAYGRAD_HOOKS_SRC):
-    TEST_HOOKS_SRCS.append(_CHAIN_RAYGRAD_HOOKS_SRC)
+# linked from -- plus the units that live with the tests and export C wrappers over library-internal kernels and launchers
+# (each unit's header comment names its test).  A second link, not a variant: no define, no #if in csrc/, libnsr.so and its
+# export list stay as they are.  The units are listed by the directory, as scripts/isa_diff.py --hooks lists them: a tests/
+# directory without a unit simply does not link it (tests/hooks.py binds symbols by name, so a test that needs a missing unit
+# fails when the library is loaded).
+TEST_HOOKS_SRCS = sorted(glob.glob(os.path.join(os.path.dirname(HERE), "tests", "csrc", "nsr_test_hooks*.hip")))
 TEST_HOOKS_LIB = os.path.join(AB_DIR, "libnsr_testhooks.so")
 
 

@@ -26,7 +26,8 @@ static inline hipStream_t nsr_stream(void* s) { return reinterpret_cast<hipStrea
 constexpr size_t kBlobTailBytes = 16;
 constexpr unsigned kOptGamma = 1u, kOptColorNone = 2u;   // = NSR_OPT_* of include/nsr.h
 static inline size_t nsr_blob_tail_offset(size_t payload_bytes) { return (payload_bytes + 15) & ~(size_t)15; }
-NSR_INTERNAL size_t nsr_payload_bytes(int precision);   // nsr_mlp.hip
+// bytes of the precision's own layout in front of the tail; 0: not a built precision
+NSR_INTERNAL size_t nsr_payload_bytes(int precision);   // nsr_api.hip
 static inline unsigned* nsr_blob_tail(const void* packed_dev, int precision) {
   return reinterpret_cast<unsigned*>(const_cast<char*>(static_cast<const char*>(packed_dev)) +
                                      nsr_blob_tail_offset(nsr_payload_bytes(precision)));

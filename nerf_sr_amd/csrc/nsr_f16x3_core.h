@@ -13,11 +13,6 @@ using namespace nsr::dma;
 
 // NSR_ABL_*: ablation switches for the measurement ladder in profiles/r1_f16x3_pmc.txt (scripts/ablate.sh builds
 // variant libraries with them); never defined in the product build.
-#ifdef NSR_ABL_NO_BARRIER
-#define NSR_SYNC() ((void)0)
-#else
-#define NSR_SYNC() do { dma_drain(); __syncthreads(); } while (0)
-#endif
 
 // weights and biases enter the stream multiplied by 2^6 (see the header); |w| < 1023 stays inside fp16
 constexpr float kWScale = 64.0f, kWInvScale = 1.0f / 64.0f;
@@ -172,17 +167,6 @@ __device__ __forceinline__ void loader_issue(const Loader& ld, int i) {
   }
 }
 
-// pieces 2j, 2j + 1 (j = 0..3: always present) with one M0 write
-__device__ __forceinline__ void loader_issue2(const Loader& ld, int j) {
-#ifdef NSR_ABL_NO_DMA
-  return;
-#endif
-  const char* base = ld.dma_base + (j >> 1) * 4096;
-  const unsigned dst = ld.dma_lds + (unsigned)(j >> 1) * 4096u;
-  if (j & 1) glds16x2_asm<2048>(base, ld.lane_off, dst);
-  else glds16x2_asm<0>(base, ld.lane_off, dst);
-}
-
 __device__ __forceinline__ void loader_advance(Loader& ld) {
   const unsigned t = ld.slot_cur;
   ld.slot_cur = ld.slot_next;
@@ -247,65 +231,23 @@ __device__ __forceinline__ void prefetch_bias(Pre& pre, unsigned bias_addr, int 
   }
 }
 
-// NSTEP k-steps of one output block, fragments software-pipelined kPF k-steps ahead (the first kPF come
-// in through `pre`), order pinned by sched_barrier.  a_addr: LDS byte address (+ lane*16) of the
-// sequence's first piece.  b_of(s, part) yields the k-step's activation operands; hook(s) runs in the MFMA
-// shadow of k-step s; BAR >= 0 places the chunk's publish point + DMA issue (k-steps BAR..BAR+5);
-// next(k), k = 0..2, runs in the last three k-steps and prefetches the following sequence into `nxt`.
-template <int NSTEP, int BAR, int YOUNGER = 0, class BOf, class Hook, class Next>
-__device__ __forceinline__ void block_mma(Acc& acc, const Pre& pre, unsigned a_addr, Loader& ld, const ChunkRef& c2,
-                                          BOf&& b_of, Hook&& hook, Next&& next, bool strict = false) {
-  static_assert(NSTEP >= kPF, "sequence shorter than the prefetch depth");
-  const u32x4* a_pieces = lds_vec(a_addr);
-  u32x4 ah[NSTEP], al[NSTEP];
-#pragma unroll
-  for (int s = 0; s < kPF; ++s) {
-    ah[s] = pre.ah[s];
-    al[s] = pre.al[s];
-  }
-#pragma unroll
-  for (int s = 0; s < NSTEP; ++s) {
-#ifdef NSR_ABL_TIMELINE
-    if (ld.tk && NSTEP == 16 && (s == 0 || s == 4 || s == 8 || s == 11 || s == 14)) ld.tk[s == 0 ? 0 : (s == 4 ? 1 : (s == 8 ? 2 : (s == 11 ? 3 : 4)))] = tl_now();
-#endif
-    if (s == BAR) loader_publish<YOUNGER>(ld, c2, strict);
-    if (s + kPF < NSTEP) {
-      ah[s + kPF] = a_pieces[(2 * (s + kPF)) * 64];
-      al[s + kPF] = a_pieces[(2 * (s + kPF) + 1) * 64];
-    } else {
-      next(s + kPF - NSTEP);
-    }
-    const u32x4 bh = b_of(s, 0), bl = b_of(s, 1);
-    // a_lo first: it is the younger of the step's two fragment loads, so ONE lgkmcnt wait serves all three
-    acc.m = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(al[s]), as_h8(bh), acc.m, 0, 0, 0);
-    acc.m = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(ah[s]), as_h8(bl), acc.m, 0, 0, 0);
-    acc.m = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(ah[s]), as_h8(bh), acc.m, 0, 0, 0);
-    hook(s);
-    // DMA of chunk j+2: two pieces per k-step over six k-steps.  (Measured alternatives: bursts of four pieces
-    // sharing one M0 write -7 %: back-to-back LDS-DMA issues hold the wave longer than one MFMA; one piece per
-    // k-step from an earlier publish point (k-step 5) -3 %.)
-    if (BAR >= 0 && s >= BAR && s < BAR + 6) {
-      if (s - BAR < 4) {
-        loader_issue2(ld, s - BAR);   // pieces 0..7: every wave owns them, one M0 write per pair
-      } else {
-        loader_issue(ld, 2 * (s - BAR));
-        loader_issue(ld, 2 * (s - BAR) + 1);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-// Gap-aware form of block_mma (round 4; the inference kernel uses it everywhere).  A wave alone on its SIMD hides at most
-// ~5 single-issue instructions behind one 32-cycle MFMA, and only if they sit in THAT MFMA's gap: the k-step-granular form
-// above lets hipcc put all of a k-step's fillers (2 fragment reads + 7 re-split VALU + 2 DMA pieces and their SALU) behind
-// the k-step's FIRST MFMA, and the measured price was ~5 cycles for every filler beyond the fifth (profiles/
-// r4_timeline_before_128.json: quiet k-steps 103 cycles, the double-half-step k-steps 122, the DMA k-steps 140-155, against
-// 96 of matrix time).  Here every k-step is three fenced (MFMA + fillers) segments:
+// NSTEP k-steps of one output block, fragments software-pipelined kPF k-steps ahead (the first kPF come in through `pre`),
+// order pinned by sched_barrier.  a_addr: LDS byte address (+ lane*16) of the sequence's first piece.  b_of(s, part) yields
+// the k-step's activation operands; BAR >= 0 places the chunk's publish point (k-step BAR) and its DMA issue (k-steps
+// BAR..BAR+5); YOUNGER / strict: loader_publish.
+// Every k-step is three fenced (MFMA + fillers) segments (round 4).  A wave alone on its SIMD hides at most ~5 single-issue
+// instructions behind one 32-cycle MFMA, and only if they sit in THAT MFMA's gap: with one fence per k-step hipcc put all of
+// a k-step's fillers (2 fragment reads + 7 re-split VALU + 2 DMA pieces and their SALU) behind the k-step's FIRST MFMA, and
+// the measured price was ~5 cycles for every filler beyond the fifth (profiles/r4_timeline_before_128.json: quiet k-steps
+// 103 cycles, the double-half-step k-steps 122, the DMA k-steps 140-155, against 96 of matrix time).  So:
 //   gap 0: a_lo*b_hi + the fragment reads of k-step s + kPF (or next(k, 0)) + hook(s, 0)
 //   gap 1: a_hi*b_lo + hook(s, 1)
 //   gap 2: a_hi*b_hi + hook(s, 2) + next(k, 2)
-// and the chunk's DMA pieces go one per gap (gaps 1 and 2 of k-steps BAR..BAR+5, each with its own M0 write).
+// hook(s, gap) runs in that MFMA's shadow; next(k, gap), k = 0..2, runs in the last three k-steps and prefetches the
+// following sequence.  The chunk's DMA pieces go one per gap (gaps 1 and 2 of k-steps BAR..BAR+5, each with its own M0
+// write): two pieces per k-step over six k-steps.  (Measured alternatives: bursts of four pieces sharing one M0 write -7 %:
+// back-to-back LDS-DMA issues hold the wave longer than one MFMA; one piece per k-step from an earlier publish point
+// (k-step 5) -3 %.)
 // DMA = false: the publish point stays, but no chunk is fetched behind it (the last two chunks of a one-tile workgroup:
 // there is no next tile to fetch L1 for).
 // MMA = false (ablation builds only, -DNSR_ABL_NO_DENSITY_MMA): the block runs without its MFMAs -- what they cost.

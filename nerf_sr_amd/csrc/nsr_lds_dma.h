@@ -87,19 +87,6 @@ __device__ __forceinline__ void glds16_keep_asm(const char* base_uniform, unsign
       : "v"(lane_off), "s"(base_uniform), "i"(OFF)
       : "memory");
 }
-// two consecutive pieces (OFF, OFF + 1024) with ONE M0 write
-template <int OFF>
-__device__ __forceinline__ void glds16x2_asm(const char* base_uniform, unsigned lane_off, unsigned lds_dst_uniform) {
-  unsigned long long tmp;
-  asm volatile(
-      "s_mov_b32 m0, %3\n\t"
-      "s_mov_b64 %0, %2\n\t"
-      "global_load_lds_dwordx4 %1, %0 offset:%4\n\t"
-      "global_load_lds_dwordx4 %1, %0 offset:%5"
-      : "=&s"(tmp)
-      : "v"(lane_off), "s"(base_uniform), "s"(lds_dst_uniform), "i"(OFF), "i"(OFF + 1024)
-      : "memory");
-}
 // the dword form: 64 lanes x 4 B, lane-linear, global -> LDS
 __device__ __forceinline__ void glds4_asm(const void* base_uniform, unsigned lane_off, unsigned lds_dst_uniform) {
   unsigned long long tmp;

@@ -13,10 +13,13 @@
 //     one workgroup barrier per chunk;
 //   * sigma (256->1) and rgb (128->3) heads are VALU dot products on the
 //     register-resident activations; bias enters as the accumulator init.
+//
+// This unit is the fp32 family only: its kernels and their launchers (nsr_mlp_units.h).  Argument checks and the choice of
+// the precision are the dispatcher's (nsr_api.hip).
 #include "nsr_common.h"
 #include "nsr_lds_dma.h"
 #include "nsr_mlp_layout.h"
-#include "nsr_composite.h"
+#include "nsr_mlp_units.h"
 
 using namespace nsr;
 using namespace nsr::dma;
@@ -27,15 +30,6 @@ using namespace nsr::dma;
 struct PackPtrs {
   const float* p[NSR_N_STATE_TENSORS];
 };
-
-__device__ __forceinline__ int tensor_ld(int tensor) {
-  switch (tensor) {
-    case 0: return kPosCh;
-    case 8: return kWidth + kPosCh;
-    case 18: return kWidth + kDirCh;
-    default: return kWidth;
-  }
-}
 
 __global__ void __launch_bounds__(256) pack_fp32_kernel(PackPtrs w, float* __restrict__ out) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -66,36 +60,19 @@ __global__ void __launch_bounds__(256) pack_fp32_kernel(PackPtrs w, float* __res
   out[idx] = v;
 }
 
-// split-fp16 kernels (nsr_mlp_f16.hip)
-extern "C" NSR_INTERNAL size_t nsr_f16x3_packed_bytes(void);
-extern "C" NSR_INTERNAL int nsr_f16x3_pack(const float* const* w, void* packed_dev, float limit, unsigned* tail, void* stream);
-extern "C" NSR_INTERNAL int nsr_f16x3_mlp_forward(const void* packed, const float* x, int64_t P, int sigma_only, float* out,
-                                     unsigned* tail, void* stream);
-extern "C" NSR_INTERNAL int nsr_f16x3_render_rays(const void* packed, const float* rays, int ray_stride, const float* z, int64_t R,
-                                     int N, float* out, unsigned* tail, void* stream);
+extern "C" NSR_INTERNAL size_t nsr_fp32_packed_bytes(void) { return sizeof(float) * (size_t)(kStreamFloats + kAuxFloats); }
 
-// single 16-bit operand paths (nsr_mlp_h1.hip); bf = 1: bf16, 0: fp16
-extern "C" NSR_INTERNAL size_t nsr_h1_packed_bytes(void);
-extern "C" NSR_INTERNAL int nsr_h1_pack(int bf, const float* const* w, void* packed_dev, void* stream);
-extern "C" NSR_INTERNAL int nsr_h1_mlp_forward(int bf, const void* packed, const float* x, int64_t P, int sigma_only,
-                                               float* out, unsigned* tail, void* stream);
-extern "C" NSR_INTERNAL int nsr_h1_render_rays(int bf, const void* packed, const float* rays, int ray_stride,
-                                               const float* z, int64_t R, int N, float* out, unsigned* tail, void* stream);
-static inline bool precision_built(int precision) {
-  return precision == NSR_FP32 || precision == NSR_F16X3 || precision == NSR_BF16 || precision == NSR_F16;
-}
-static inline bool precision_h1(int precision) { return precision == NSR_BF16 || precision == NSR_F16; }
-
-NSR_INTERNAL size_t nsr_payload_bytes(int precision) {
-  if (precision == NSR_FP32) return sizeof(float) * (size_t)(kStreamFloats + kAuxFloats);
-  if (precision == NSR_F16X3) return nsr_f16x3_packed_bytes();
-  if (precision_h1(precision)) return nsr_h1_packed_bytes();
-  return 0;
-}
-
-extern "C" size_t nsr_packed_weights_bytes(int precision) {
-  const size_t payload = nsr_payload_bytes(precision);
-  return payload ? nsr_blob_tail_offset(payload) + kBlobTailBytes : 0;
+extern "C" NSR_INTERNAL int nsr_fp32_pack(const float* const* w, void* packed_dev, void* stream) {
+  PackPtrs pp;
+  for (int i = 0; i < NSR_N_STATE_TENSORS; ++i) {
+    if (!w[i]) return NSR_ERR_INVALID_ARG;
+    pp.p[i] = w[i];
+  }
+  const int total = kStreamFloats + kAuxFloats;
+  hipLaunchKernelGGL(pack_fp32_kernel, dim3((total + 255) / 256), dim3(256), 0, nsr_stream(stream), pp,
+                     static_cast<float*>(packed_dev));
+  NSR_CHECK_LAUNCH();
+  return NSR_OK;
 }
 
 // Range check of the 24 tensors the blob is made from (include/nsr.h, nsr_pack_weights); the tail is cleared by a
@@ -115,18 +92,6 @@ __global__ void __launch_bounds__(256) check_weights_kernel(CheckPtrs w, float l
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(tail, NSR_FLAG_WEIGHT_RANGE);
 }
 
-static const int kStateTensorSizes[NSR_N_STATE_TENSORS] = {
-    kWidth * kPosCh, kWidth, kWidth * kWidth, kWidth, kWidth * kWidth, kWidth, kWidth * kWidth, kWidth,
-    kWidth * (kWidth + kPosCh), kWidth, kWidth * kWidth, kWidth, kWidth * kWidth, kWidth, kWidth * kWidth, kWidth,
-    kWidth * kWidth, kWidth, (kWidth / 2) * (kWidth + kDirCh), kWidth / 2, kWidth, 1, 3 * (kWidth / 2), 3};
-
-// largest weight magnitude whose operand encoding is still finite: fp16 rounds to inf from 65,520 on
-static float precision_weight_limit(int precision) {
-  if (precision == NSR_F16X3) return 65519.996f / 64.0f;   // the stream carries 2^6 w (nsr_f16x3_core.h, kWScale)
-  if (precision == NSR_F16) return 65519.996f;
-  return 3.402823466e38f;
-}
-
 // both networks of a training step in ONE launch (round 6: the step's launch count; blockIdx.z = network)
 __global__ void __launch_bounds__(256) check_weights2_kernel(CheckPtrs w0, CheckPtrs w1, float limit, unsigned* tail) {
   const CheckPtrs& w = blockIdx.z ? w1 : w0;
@@ -143,88 +108,26 @@ extern "C" NSR_INTERNAL int nsr_check_weights_range2(const float* const* w0, con
   for (int i = 0; i < NSR_N_STATE_TENSORS; ++i) {
     if (!w0[i] || !w1[i]) return NSR_ERR_INVALID_ARG;
     a.p[i] = w0[i]; b.p[i] = w1[i];
-    a.n[i] = b.n[i] = kStateTensorSizes[i];
+    a.n[i] = b.n[i] = tensor_numel(i);
   }
   hipLaunchKernelGGL(check_weights2_kernel, dim3(16, NSR_N_STATE_TENSORS, 2), dim3(256), 0, nsr_stream(stream), a, b,
-                     precision_weight_limit(precision), word);
+                     nsr_weight_limit(precision), word);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
 
-// the weight-range check on its own (the training step runs it on the weights it re-packs every iteration)
+// one network (nsr_pack_weights_async, behind the memset that clears the blob's tail)
 extern "C" NSR_INTERNAL int nsr_check_weights_range(const float* const* w, int precision, unsigned* word, void* stream) {
   CheckPtrs cp;
   for (int i = 0; i < NSR_N_STATE_TENSORS; ++i) {
     if (!w[i]) return NSR_ERR_INVALID_ARG;
     cp.p[i] = w[i];
-    cp.n[i] = kStateTensorSizes[i];
+    cp.n[i] = tensor_numel(i);
   }
   hipLaunchKernelGGL(check_weights_kernel, dim3(16, NSR_N_STATE_TENSORS), dim3(256), 0, nsr_stream(stream), cp,
-                     precision_weight_limit(precision), word);
+                     nsr_weight_limit(precision), word);
   NSR_CHECK_LAUNCH();
   return NSR_OK;
-}
-
-extern "C" int nsr_pack_weights_async(const float* const* w, void* packed_dev, int precision, void* stream) {
-  if (!w || !packed_dev) return NSR_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(packed_dev) & 15) != 0) return NSR_ERR_INVALID_ARG;
-  if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
-  CheckPtrs cp;
-  for (int i = 0; i < NSR_N_STATE_TENSORS; ++i) {
-    if (!w[i]) return NSR_ERR_INVALID_ARG;
-    cp.p[i] = w[i];
-    cp.n[i] = kStateTensorSizes[i];
-  }
-  unsigned* tail = nsr_blob_tail(packed_dev, precision);
-  if (hipMemsetAsync(tail, 0, kBlobTailBytes, nsr_stream(stream)) != hipSuccess) return NSR_ERR_LAUNCH;
-  hipLaunchKernelGGL(check_weights_kernel, dim3(16, NSR_N_STATE_TENSORS), dim3(256), 0, nsr_stream(stream), cp,
-                     precision_weight_limit(precision), tail);
-  NSR_CHECK_LAUNCH();
-  // (folds xyz_encoding_final into dir_encoding first; the folded matrix is range-checked like the 24 tensors)
-  if (precision == NSR_F16X3) return nsr_f16x3_pack(w, packed_dev, precision_weight_limit(precision), tail, stream);
-  if (precision_h1(precision)) return nsr_h1_pack(precision == NSR_BF16, w, packed_dev, stream);
-  PackPtrs pp;
-  for (int i = 0; i < NSR_N_STATE_TENSORS; ++i) pp.p[i] = w[i];
-  const int total = kStreamFloats + kAuxFloats;
-  hipLaunchKernelGGL(pack_fp32_kernel, dim3((total + 255) / 256), dim3(256), 0, nsr_stream(stream), pp,
-                     static_cast<float*>(packed_dev));
-  NSR_CHECK_LAUNCH();
-  return NSR_OK;
-}
-
-extern "C" int nsr_weights_status(const void* packed_dev, int precision, int clear, unsigned* flags_out, void* stream) {
-  if (!packed_dev || !flags_out) return NSR_ERR_INVALID_ARG;
-  if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
-  unsigned* tail = nsr_blob_tail(packed_dev, precision);
-  hipStream_t st = nsr_stream(stream);
-  unsigned host = 0;
-  if (hipMemcpyAsync(&host, tail, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess) return NSR_ERR_LAUNCH;
-  if (clear && hipMemsetAsync(tail, 0, sizeof(unsigned), st) != hipSuccess) return NSR_ERR_LAUNCH;
-  if (hipStreamSynchronize(st) != hipSuccess) return NSR_ERR_LAUNCH;
-  *flags_out = host;
-  return NSR_OK;
-}
-
-extern "C" int nsr_pack_weights(const float* const* w, void* packed_dev, int precision, void* stream) {
-  const int rc = nsr_pack_weights_async(w, packed_dev, precision, stream);
-  if (rc != NSR_OK) return rc;
-  unsigned flags = 0;
-  const int rs = nsr_weights_status(packed_dev, precision, 0, &flags, stream);
-  if (rs != NSR_OK) return rs;
-  return (flags & NSR_FLAG_WEIGHT_RANGE) ? NSR_ERR_RANGE : NSR_OK;
-}
-
-extern "C" int nsr_weights_set_options(void* packed_dev, int precision, unsigned options, void* stream) {
-  static_assert(kOptGamma == NSR_OPT_GAMMA && kOptColorNone == NSR_OPT_COLOR_NONE, "option bits of include/nsr.h");
-  if (!packed_dev || (options & ~(NSR_OPT_GAMMA | NSR_OPT_COLOR_NONE)) != 0u) return NSR_ERR_INVALID_ARG;
-  if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
-  unsigned* tail = nsr_blob_tail(packed_dev, precision);
-  if (hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(tail + 1), (int)options, 1, nsr_stream(stream)) != hipSuccess)
-    return NSR_ERR_LAUNCH;
-  return NSR_OK;
-}
-extern "C" int nsr_weights_set_gamma(void* packed_dev, int precision, int enable, void* stream) {
-  return nsr_weights_set_options(packed_dev, precision, enable ? NSR_OPT_GAMMA : 0u, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -474,118 +377,39 @@ mlp_fp32_kernel(const float* __restrict__ packed, const float* __restrict__ x, c
   }
 }
 
-extern "C" int nsr_mlp_forward(const void* packed_dev, int precision, const float* x, int64_t P, int sigma_only,
-                               float* out, void* stream) {
-  if (P < 0 || !packed_dev) return NSR_ERR_INVALID_ARG;
-  if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
-  if (P == 0) return NSR_OK;   // empty batch: nothing to read or write (pointers may be null)
-  if (!x || !out) return NSR_ERR_INVALID_ARG;
-  if (!sigma_only && (reinterpret_cast<uintptr_t>(out) & 15) != 0) return NSR_ERR_INVALID_ARG;
-  unsigned* tail = nsr_blob_tail(packed_dev, precision);
-  if (precision == NSR_F16X3) return nsr_f16x3_mlp_forward(packed_dev, x, P, sigma_only, out, tail, stream);
-  if (precision_h1(precision)) return nsr_h1_mlp_forward(precision == NSR_BF16, packed_dev, x, P, sigma_only, out, tail, stream);
+extern "C" NSR_INTERNAL int nsr_fp32_mlp_forward(const void* packed, const float* x, int64_t P, int sigma_only, float* out,
+                                                 unsigned* tail, void* stream) {
   const dim3 grid((unsigned)((P + 127) / 128)), block(256);
-  const float* pk = static_cast<const float*>(packed_dev);
+  const float* pk = static_cast<const float*>(packed);
   if (sigma_only)
-    hipLaunchKernelGGL((mlp_fp32_kernel<0, true>), grid, block, 0, nsr_stream(stream), pk, x, nullptr, P, 1, 8, out, NsrTail{nsr_blob_tail(packed_dev, precision)});
+    hipLaunchKernelGGL((mlp_fp32_kernel<0, true>), grid, block, 0, nsr_stream(stream), pk, x, nullptr, P, 1, 8, out, NsrTail{tail});
   else
-    hipLaunchKernelGGL((mlp_fp32_kernel<0, false>), grid, block, 0, nsr_stream(stream), pk, x, nullptr, P, 1, 8, out, NsrTail{nsr_blob_tail(packed_dev, precision)});
+    hipLaunchKernelGGL((mlp_fp32_kernel<0, false>), grid, block, 0, nsr_stream(stream), pk, x, nullptr, P, 1, 8, out, NsrTail{tail});
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
 
-extern "C" int nsr_render_rays(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
-                               int64_t R, int n_samples, float* out, void* stream) {
-  if (!packed_dev || R < 0 || n_samples <= 0 || !nsr_ray_stride_ok(ray_stride)) return NSR_ERR_INVALID_ARG;
-  if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
-  if (R == 0) return NSR_OK;
-  if (!rays || !z || !out) return NSR_ERR_INVALID_ARG;
-  if ((reinterpret_cast<uintptr_t>(out) & 15) != 0 || (ray_stride == 8 && (reinterpret_cast<uintptr_t>(rays) & 15) != 0))
-    return NSR_ERR_INVALID_ARG;
-  unsigned* tail = nsr_blob_tail(packed_dev, precision);
-  if (precision == NSR_F16X3) return nsr_f16x3_render_rays(packed_dev, rays, ray_stride, z, R, n_samples, out, tail, stream);
-  if (precision_h1(precision))
-    return nsr_h1_render_rays(precision == NSR_BF16, packed_dev, rays, ray_stride, z, R, n_samples, out, tail, stream);
-  const int64_t P = R * n_samples;
+extern "C" NSR_INTERNAL int nsr_fp32_render_rays(const void* packed, const float* rays, int ray_stride, const float* z, int64_t R,
+                                                 int N, float* out, unsigned* tail, void* stream) {
+  const int64_t P = R * N;
   const dim3 grid((unsigned)((P + 127) / 128)), block(256);
   hipLaunchKernelGGL((mlp_fp32_kernel<1, false>), grid, block, 0, nsr_stream(stream),
-                     static_cast<const float*>(packed_dev), rays, z, P, n_samples, ray_stride, out, NsrTail{tail});
+                     static_cast<const float*>(packed), rays, z, P, N, ray_stride, out, NsrTail{tail});
   NSR_CHECK_LAUNCH();
   return NSR_OK;
 }
 
-/* D2 + V1 in one launch, see include/nsr.h */
-extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const float* rays, int ray_stride, const float* z,
-                                                       int64_t R, int N, float* raw, const NsrCompOut* co, unsigned* tail, void* stream);
-extern "C" NSR_INTERNAL int nsr_f16x3_render_density(const void* packed, const float* rays, int ray_stride, const float* z,
-                                                     int64_t R, int N, const NsrCompOut* co, unsigned* tail, void* stream);
-
-// sample counts of the fused launch: 128-point tiles of whole rays (fp32), ray groups walking N / 32 windows (split fp16)
-static inline bool fused_samples(int precision, int n_samples) {
-  if (n_samples == 64 || n_samples == 128) return precision == NSR_FP32 || precision == NSR_F16X3;
-  return precision == NSR_F16X3 && (n_samples == 192 || n_samples == 256);
-}
-
-// the one body of both entry points below: argument checks, then the launch.  ert_tau / cut: early ray termination of the
-// split-fp16 kernel (0 / null: off), already checked by the caller
-static int render_rays_composited(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
-                                  int64_t R, int n_samples, int white_bkgd, float* raw, float* comp_rgb, float* depth,
-                                  float* opacity, float* weights, float ert_tau, unsigned* cut, void* stream) {
-  if (!packed_dev || R < 0 || n_samples <= 0 || !nsr_ray_stride_ok(ray_stride) || (white_bkgd & ~(NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS)) != 0)
-    return NSR_ERR_INVALID_ARG;
-  if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
-  if (!fused_samples(precision, n_samples)) return NSR_ERR_UNSUPPORTED;
-  if (R == 0) return NSR_OK;
-  if (!rays || !z) return NSR_ERR_INVALID_ARG;
-  if ((raw && (reinterpret_cast<uintptr_t>(raw) & 15) != 0) || (ray_stride == 8 && (reinterpret_cast<uintptr_t>(rays) & 15) != 0))
-    return NSR_ERR_INVALID_ARG;
-  NsrCompOut co{comp_rgb, depth, opacity, weights, white_bkgd};
-  co.ert_tau = ert_tau;
-  co.cut = cut;
-  unsigned* tail = nsr_blob_tail(packed_dev, precision);
-  if (precision == NSR_F16X3) return nsr_f16x3_render_composite(packed_dev, rays, ray_stride, z, R, n_samples, raw, &co, tail, stream);
-  const int64_t P = R * n_samples;
+extern "C" NSR_INTERNAL int nsr_fp32_render_composite(const void* packed, const float* rays, int ray_stride, const float* z,
+                                                      int64_t R, int N, float* raw, const NsrCompOut* co, unsigned* tail, void* stream) {
+  const int64_t P = R * N;
   const dim3 grid((unsigned)((P + 127) / 128)), block(256);
-  const float* pk = static_cast<const float*>(packed_dev);
-  if (n_samples == 64)
-    hipLaunchKernelGGL((mlp_fp32_kernel<1, false, 64>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, n_samples, ray_stride, raw, NsrTail{tail}, co);
+  const float* pk = static_cast<const float*>(packed);
+  if (N == 64)
+    hipLaunchKernelGGL((mlp_fp32_kernel<1, false, 64>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, NsrTail{tail}, *co);
+  else if (N == 128)
+    hipLaunchKernelGGL((mlp_fp32_kernel<1, false, 128>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, N, ray_stride, raw, NsrTail{tail}, *co);
   else
-    hipLaunchKernelGGL((mlp_fp32_kernel<1, false, 128>), grid, block, 0, nsr_stream(stream), pk, rays, z, P, n_samples, ray_stride, raw, NsrTail{tail}, co);
+    return NSR_ERR_UNSUPPORTED;
   NSR_CHECK_LAUNCH();
   return NSR_OK;
-}
-
-extern "C" int nsr_render_rays_composited(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
-                                          int64_t R, int n_samples, int white_bkgd, float* raw, float* comp_rgb, float* depth,
-                                          float* opacity, float* weights, void* stream) {
-  return render_rays_composited(packed_dev, precision, rays, ray_stride, z, R, n_samples, white_bkgd, raw, comp_rgb, depth, opacity,
-                                weights, 0.0f, nullptr, stream);
-}
-
-/* the same launch with early ray termination (split-fp16 kernel only), see include/nsr.h.  It lives here, next to its parent
- * and the launch both share, not in nsr_render.hip (the stand-alone compositor) */
-extern "C" int nsr_render_rays_composited_ert(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
-                                              int64_t R, int n_samples, int render_flags, float early_stop, float* comp_rgb,
-                                              float* depth, float* opacity, float* weights, unsigned* windows_cut, void* stream) {
-  const int rc = nsr_ert_check(early_stop, precision, n_samples, render_flags);
-  if (rc != NSR_OK) return rc;
-  const bool on = early_stop > 0.0f;
-  return render_rays_composited(packed_dev, precision, rays, ray_stride, z, R, n_samples, render_flags, nullptr, comp_rgb, depth, opacity,
-                                weights, on ? (float)(-log((double)early_stop)) : 0.0f,      // -ln eps in double, rounded once
-                                on ? windows_cut : nullptr, stream);
-}
-
-/* the density-only pass of the same launch (split-fp16 kernel only), see include/nsr.h */
-extern "C" int nsr_render_rays_density(const void* packed_dev, int precision, const float* rays, int ray_stride, const float* z,
-                                       int64_t R, int n_samples, int render_flags, float* depth, float* opacity, float* weights,
-                                       void* stream) {
-  if (!packed_dev || R < 0 || n_samples <= 0 || !nsr_ray_stride_ok(ray_stride) || (render_flags & ~(NSR_WHITE_BKGD | NSR_SIGMA_SOFTPLUS)) != 0)
-    return NSR_ERR_INVALID_ARG;
-  if (!precision_built(precision)) return NSR_ERR_UNSUPPORTED;
-  if (precision != NSR_F16X3 || !fused_samples(precision, n_samples)) return NSR_ERR_UNSUPPORTED;
-  if (R == 0) return NSR_OK;
-  if (!rays || !z) return NSR_ERR_INVALID_ARG;
-  if (ray_stride == 8 && (reinterpret_cast<uintptr_t>(rays) & 15) != 0) return NSR_ERR_INVALID_ARG;
-  NsrCompOut co{nullptr, depth, opacity, weights, render_flags};
-  return nsr_f16x3_render_density(packed_dev, rays, ray_stride, z, R, n_samples, &co, nsr_blob_tail(packed_dev, precision), stream);
 }

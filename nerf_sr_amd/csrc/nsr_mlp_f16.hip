@@ -19,7 +19,7 @@
 // next layer's hi/lo operand registers on the VALU while the next block occupies the
 // matrix pipe; two register sets alternate roles layer by layer.
 #include "nsr_f16x3_core.h"
-#include "nsr_composite.h"
+#include "nsr_mlp_units.h"
 #include <type_traits>
 #include <utility>
 
@@ -30,16 +30,6 @@ struct PackPtrsH {
   const float* p[NSR_N_STATE_TENSORS];
 };
 
-__device__ __forceinline__ int tensor_ld_h(int tensor) {
-  switch (tensor) {
-    case 0: return kPosCh;
-    case 8: return kWidth + kPosCh;
-    case 18: return kWidth + kDirCh;
-    default: return kWidth;
-  }
-}
-
-
 // The fold (nsr_mlp_layout.h, "Folded dir_encoding"): one thread per element of W' (128 x 256), then of b' (128).  Each sums
 // its 256 products in double, in index order, and rounds once to float: two more fp32 roundings per element would be the
 // precision the 22-bit hi + lo split of W' exists to keep.  W' enters the fp16 stream x 2^6 like every weight, so it gets
@@ -47,7 +37,7 @@ __device__ __forceinline__ int tensor_ld_h(int tensor) {
 __global__ void __launch_bounds__(256) fold_final_kernel(PackPtrsH w, float* __restrict__ out, float limit, unsigned* __restrict__ tail) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   constexpr int kW = (kWidth / 2) * kWidth;
-  const int kLd = tensor_ld_h(18);
+  const int kLd = tensor_ld(18);
   if (idx >= kW + kWidth / 2) return;
   const float* wd = w.p[18];
   double acc;
@@ -99,7 +89,7 @@ __device__ __forceinline__ void pack_f16x3_body(const PackPtrsH& w, unsigned* __
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const int col = column_of(18, s, 2 * jj + e, h);
-          f[e] = (col == kPad) ? 0.0f : kWScale * (col < kWidth ? fw[n * kWidth + col] : w.p[18][n * tensor_ld_h(18) + col]);
+          f[e] = (col == kPad) ? 0.0f : kWScale * (col < kWidth ? fw[n * kWidth + col] : w.p[18][n * tensor_ld(18) + col]);
         }
         v = pack_hl(f[0], f[1], part);
       }
@@ -118,7 +108,7 @@ __device__ __forceinline__ void pack_f16x3_body(const PackPtrsH& w, unsigned* __
       const int s = rem >> 1, part = rem & 1;
       const int lane = word >> 2, jj = word & 3;
       const int n = 32 * (c.nb0 + g) + (lane & 31), h = lane >> 5;
-      const int ld = tensor_ld_h(c.tensor);
+      const int ld = tensor_ld(c.tensor);
       float f[2];
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
@@ -401,7 +391,7 @@ __device__ __forceinline__ void prefetch_next_chunk(Pre& nxt, int k, int g, cons
 // operand of the weight gradients -- are written to the training panels (panel L - 1 holds trunk layer L's output, see
 // nsr_f16x3_core.h): its two units as two 16-byte stores in k-steps 14 and 15 (+ the block's sign word), i.e. BEHIND the
 // chunk's last DMA piece (k-step 13).  Vector-memory operations complete in issue order, so the next publish point --
-// which must see that DMA landed -- may leave those stores in flight (block_mma's YOUNGER); they have a whole further
+// which must see that DMA landed -- may leave those stores in flight (block_mma3's YOUNGER); they have a whole further
 // chunk to reach HBM.  (Rounds 2-4 stored the sixteen raw fp32 accumulators of a block here.)
 // Only the TRAIN forward evaluates xyz_encoding_final (L == 8); everywhere else it is folded into dir_encoding.
 // K0 / KA0 / KA1 (the render kernels): pieces per wave (nsr_f16x3_core.h, constant shares) of this layer's chunks and of the two

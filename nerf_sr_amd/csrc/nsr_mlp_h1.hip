@@ -12,6 +12,7 @@
 #include "nsr_lds_dma.h"
 #include "nsr_mlp_layout.h"
 #include "nsr_mlp_encode.h"
+#include "nsr_mlp_units.h"
 
 using namespace nsr;
 using namespace nsr::dma;
@@ -165,14 +166,6 @@ __device__ __forceinline__ unsigned pack2(float a, float b) {   // round to near
 struct PackPtrs {
   const float* p[NSR_N_STATE_TENSORS];
 };
-__device__ __forceinline__ int tensor_ld(int tensor) {
-  switch (tensor) {
-    case 0: return kPosCh;
-    case 8: return kWidth + kPosCh;
-    case 18: return kWidth + kDirCh;
-    default: return kWidth;
-  }
-}
 template <bool BF>
 __global__ void __launch_bounds__(256) pack_kernel(PackPtrs w, unsigned* __restrict__ out) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -259,7 +252,7 @@ __device__ __forceinline__ void init_acc(Acc2& acc, const u32x4& bias_frag, cons
   acc.a0 = mma<BF>(bias_frag, b0, zero);
 }
 
-// NSTEP k-steps of a block pair; same pipeline discipline as block_mma in nsr_mlp_f16.hip
+// NSTEP k-steps of a block pair; same pipeline discipline as block_mma3 (nsr_f16x3_core.h), at k-step granularity
 template <bool BF, int NSTEP, int BAR, class BOf, class Hook, class Next>
 __device__ __forceinline__ void pair_mma(Acc2& acc, const Pre2& pre, unsigned a_addr, Loader& ld, const ChunkRef& c2,
                                          BOf&& b_of, Hook&& hook, Next&& next) {

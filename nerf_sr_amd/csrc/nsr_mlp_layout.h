@@ -106,6 +106,30 @@ NSR_HD int seg_col(int src, int t, int h) {
   return src == SRC_PE ? pecol(t, h) : (src == SRC_ACT ? act_feature(t, h) : dircol(t, h));
 }
 
+// ---- shapes of the 24 state_dict tensors (row-major (rows, ld) weights, biases of `rows` elements) ----
+// leading dimension of the weight matrices the pack kernels gather from: L1 (pe), the skip layer (cat([pe, h])),
+// dir_encoding (cat([g, de])); every other one they index is kWidth wide.  (rgb.weight, 128 wide, is copied flat: below.)
+NSR_HD constexpr int tensor_ld(int tensor) {
+  switch (tensor) {
+    case 0: return kPosCh;
+    case 8: return kWidth + kPosCh;
+    case 18: return kWidth + kDirCh;
+    default: return kWidth;
+  }
+}
+// output features of weight `tensor` and of the bias behind it
+NSR_HD constexpr int tensor_rows(int tensor) {
+  const int w = tensor & ~1;
+  return w == 18 ? kWidth / 2 : (w == 20 ? 1 : (w == 22 ? 3 : kWidth));
+}
+// elements of state_dict entry `tensor`
+NSR_HD constexpr int tensor_numel(int tensor) {
+  if (tensor & 1) return tensor_rows(tensor);
+  return tensor_rows(tensor) * (tensor == 22 ? kWidth / 2 : tensor_ld(tensor));
+}
+constexpr int state_numel(int n) { return n == 0 ? 0 : state_numel(n - 1) + tensor_numel(n - 1); }
+static_assert(state_numel(24) == 595844, "parameters of the default 8 x 256 network");
+
 }  // namespace nsr
 
 // ===========================================================================

@@ -243,8 +243,8 @@ __device__ __forceinline__ void bwd_half(int hs, Acc& p, unsigned mz, Scale& sc,
     default: break;
   }
 }
-// Schedule over the gaps of a 16-step chunk (block_mma3, round 5; rounds 2-4 ran this kernel on the k-step-granular
-// block_mma, whose fillers all queue behind the k-step's first MFMA): half-step i (0..15) in gap 1 + (i & 1) of k-step
+// Schedule over the gaps of a 16-step chunk (block_mma3, round 5; rounds 2-4 ran this kernel with one fence per
+// k-step, where the fillers all queue behind the k-step's first MFMA): half-step i (0..15) in gap 1 + (i & 1) of k-step
 // i >> 1, the last one (two instructions) in gap 0 of k-step 8 -- the forward kernel's pending_gap.  Everything is done
 // before the publish point's DMA gaps (k-steps 8..13) and long before the operands of k-steps 14, 15 are used.
 template <bool MASK, bool CONV, int HB>
@@ -259,7 +259,7 @@ __device__ __forceinline__ void bwd_gap(int s, int g, Acc& p, unsigned mz, Scale
 }
 // Stores of the pending block: its two units in k-steps 14 and 15 (the hi registers are final after half-step 15 =
 // k-step 12), i.e. BEHIND the chunk's last DMA piece (k-step 13).  Vector-memory operations complete in issue order, so
-// the next publish point -- which must see that DMA landed -- can leave these stores in flight (block_mma's YOUNGER
+// the next publish point -- which must see that DMA landed -- can leave these stores in flight (block_mma3's YOUNGER
 // count); they only have to be done one block later.  (With the stores spread over k-steps 8..13 the publish point's
 // wait covered them too and the wave stalled on HBM write latency every block.)
 // These are PLAIN (compiler-visible, non-temporal) stores, unlike the forward kernel's asm ones: the kernel also has

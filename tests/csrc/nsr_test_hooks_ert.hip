@@ -4,13 +4,9 @@
 // `skipped`, the windows ended after the density head by the empty-window skip, which the public entry points never pass.
 // `tau` is the kernel's threshold -ln(eps) itself (0 = option off).  The wrapper marshals arguments and does no arithmetic.
 #include <stddef.h>
-#include "nsr_common.h"
-#include "nsr_composite.h"
+#include "nsr_mlp_units.h"
 
 #define NSR_TEST_API extern "C" __attribute__((visibility("default")))
-
-extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const float* rays, int ray_stride, const float* z,
-                                                       int64_t R, int N, float* raw, const NsrCompOut* co, unsigned* tail, void* stream);
 
 NSR_TEST_API int nsr_test_f16x3_render_composite_ert(const void* packed, const float* rays, int ray_stride, const float* z, int64_t R,
                                                      int N, int white_bkgd, float tau, float* comp_rgb, float* depth, float* opacity,

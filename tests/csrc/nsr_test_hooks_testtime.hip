@@ -3,13 +3,9 @@
 // `skipped`, the device word the kernel adds 1 to for every window (4 rays x 32 samples) it ends after the density head.  The
 // counter exists only here: libnsr.so always passes null.  The wrapper marshals arguments and does no arithmetic.
 #include <stddef.h>
-#include "nsr_common.h"
-#include "nsr_composite.h"
+#include "nsr_mlp_units.h"
 
 #define NSR_TEST_API extern "C" __attribute__((visibility("default")))
-
-extern "C" NSR_INTERNAL int nsr_f16x3_render_composite(const void* packed, const float* rays, int ray_stride, const float* z,
-                                                       int64_t R, int N, float* raw, const NsrCompOut* co, unsigned* tail, void* stream);
 
 NSR_TEST_API int nsr_test_f16x3_render_composite_wide(const void* packed, const float* rays, int ray_stride, const float* z, int64_t R,
                                                       int N, int white_bkgd, float* raw, float* comp_rgb, float* depth, float* opacity,
