@@ -12,7 +12,10 @@ and the iterations per second of the loop.
 (``nsr_train_backward_r``) takes the ray gradient from the backward chain's panels and -- the field being frozen, no weight
 requires grad -- skips the weight-gradient launches (``NSR_BACKWARD_NO_WEIGHT_GRADS``).
 
-    python examples/refine_pose.py [--iters 300] [--batch 512] [--rot 0.02] [--trans 0.02] [--chain]
+``--precision`` names the layer-by-layer pair's arithmetic: 'fp32', 'f16x3_gemm' (forward products split-fp16) or
+'f16x3_gemm_bwd' (the gradient products split-fp16 as well).
+
+    python examples/refine_pose.py [--iters 300] [--batch 512] [--rot 0.02] [--trans 0.02] [--chain | --precision f16x3_gemm_bwd]
 """
 import argparse
 import os
@@ -52,11 +55,13 @@ def main():
     ap.add_argument("--trans", type=float, default=0.02, help="norm of the translation offset")
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--chain", action="store_true", help="the chain pair under precision 'f16x3' (chain_ray_grad=True)")
+    ap.add_argument("--precision", default="fp32", choices=train.ARCH_PRECISIONS,
+                    help="the layer-by-layer pair's arithmetic (without --chain)")
     a = ap.parse_args()
     W, H, s = 96, 72, 2
     focal = cameras.llff_focal(504) * W / 504
     field = [{k: torch.from_numpy(v).cuda() for k, v in make_state_dict(seed).items()} for seed in (99, 100)]
-    route = dict(precision="f16x3", chain_ray_grad=True) if a.chain else dict(precision="fp32")
+    route = dict(precision="f16x3", chain_ray_grad=True) if a.chain else dict(precision=a.precision)
     render = lambda rays: train.forward_rays_train(field[0], field[1], rays, None, ray_chunk=4096, **route)
     c2w_true = torch.from_numpy(cameras.spiral_pose(0.5)).float()
     with torch.no_grad():      # the teacher: the deterministic train-mode forward from the true pose

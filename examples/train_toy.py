@@ -26,6 +26,9 @@ def main():
     ap.add_argument("--arch", default="", help="D,W,skips of a non-default network, skips joined by '+' ('6,192,1+3'; '4,128,' = none)")
     ap.add_argument("--no-xyz", action="store_true", help="the embedding's --no_xyz (the layer-by-layer pair, on the default network without --arch)")
     ap.add_argument("--no-logscale", action="store_true", help="the embedding's --no_logscale (likewise)")
+    ap.add_argument("--precision", default="f16x3_gemm", choices=train.ARCH_PRECISIONS,
+                    help="the student's arithmetic with --arch / --no-xyz / --no-logscale (the layer-by-layer pair): 'f16x3_gemm_bwd' "
+                         "runs the gradient products on the split-fp16 MFMA as well")
     a = ap.parse_args()
     W, H, s = 504, 378, 2
     if a.arch or a.no_xyz or a.no_logscale:
@@ -68,7 +71,7 @@ def main_arch(a, W, H, s):
                                            ray_chunk=16384, embed=embed)
         frames.append((rays, out["fine_comp_rgbs"].view(rays.shape[0], s * s, 3).mean(1)))
     student = train.Trainer(sd(7), sd(8), randomized=True, noise_std=1.0,
-                            lr=5e-4, ray_chunk=4 * a.batch, precision="f16x3_gemm", arch=arch, embed=embed)
+                            lr=5e-4, ray_chunk=4 * a.batch, precision=a.precision, arch=arch, embed=embed)
     t0 = time.time()
     for it in range(a.iters):
         rays, target = frames[it % len(frames)]

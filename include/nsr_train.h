@@ -49,6 +49,26 @@ extern "C" {
 #define NSR_F16X3_BWD2 20
 #define NSR_F16X3_BWD1 21
 #define NSR_F16X3_BWDM 22
+/* NSR_F16X3_GEMM with its BACKWARD products on the split-fp16 MFMA too (opt-in; 23 stays unknown).  It is accepted wherever
+ * NSR_F16X3_GEMM is (nsr_train_loss_and_grads[_var], nsr_train_forward / _backward, nsr_train_arch_* with their _e / _r forms,
+ * every size function) and refused wherever that is (e.g. nsr_train_backward_r with g_rays: NSR_ERR_UNSUPPORTED).
+ *   Forward: NSR_F16X3_GEMM's -- the same launches, the same bits, the same saved-state format and size.
+ *   Backward: every product of the layer-by-layer network -- the input gradients, the weight gradients, the products onto the
+ *   encoded-position / encoded-direction columns of nsr_train_arch_backward_r -- runs on v_mfma_f32_32x32x16_f16 with three
+ *   terms (lo hi + hi lo + hi hi, small terms first, fp32 accumulation: products exact to ~2^-21) instead of
+ *   v_mfma_f32_32x32x2_f32.  Everything that is not a product (bias sums, reductions, encodings' and compositing backward,
+ *   --stop_grad, Adam) is what it is under NSR_F16X3_GEMM; the colour and density heads' bias gradients have its bits.
+ *   Range: gradients are brought into fp16's range by exact powers of two, removed again before the store.  An input gradient
+ *   scales every ROW (sample point) of the incoming gradient by its own power of two (row max -> [2^13, 2^14)): a row of the
+ *   result depends on that row, its mask row and the weights only -- not on the batch, the ray chunk or its neighbours -- so
+ *   the rows of g_rays stay bit-identical across ray_chunk and batch order.  A weight gradient (a contraction over the
+ *   points) scales the matrix by one power of two from its largest magnitude, kept in a device word by integer maximum.
+ *   Zero rows / matrices and NaN use 1; non-finite values pass through.  No float atomics: identical calls, identical bits;
+ *   scaling the upstream gradients by a power of two scales every gradient by exactly it.
+ *   Workspace: NSR_F16X3_GEMM's layout with a tail behind it (the transposed split copies of the weights the input gradients
+ *   read, re-made by every call that runs a backward, and 64 range words); the size functions include it for this value only.
+ * The backward takes its arithmetic from the precision recorded in the saved header. */
+#define NSR_F16X3_GEMM_BWD 24
 
 /* Workspace for one pass over `ray_chunk` rays (activations of one network, gradient buffers, padded weight copies,
  * split-K partials; for NSR_F16X3 the activation / gradient panels, ~24 KB per sample point in all).  0 on invalid

@@ -34,6 +34,7 @@ UNITS = [
     ("nsr_train_raygrad_f16.hip", ["-ffp-contract=off"]),
     ("nsr_train.hip", ["-ffp-contract=off"]),
     ("nsr_train_gemm.hip", ["-ffp-contract=off"]),
+    ("nsr_train_bwd_f16.hip", ["-ffp-contract=off"]),
     ("nsr_train_chain.hip", ["-ffp-contract=off", "-mllvm", "-amdgpu-mfma-vgpr-form=1"]),
     ("nsr_warp.hip", ["-ffp-contract=off"]),
     ("nsr_refine.hip", ["-ffp-contract=off"]),

@@ -40,7 +40,8 @@ NSR_INTERNAL int gemm(const GemmArgs& g, hipStream_t st);
 
 // ---- split-fp16 variant (nsr_gemm_f16.hip): the same product on v_mfma_f32_32x32x16_f16 with every fp32 value carried
 // as hi + lo fp16 halves (a b = a_hi b_hi + a_hi b_lo + a_lo b_hi, fp32 accumulate: products exact to ~2^-21, the
-// scheme of the NSR_F16X3 inference kernel) at 3/16 of the fp32-MFMA cycle cost.  Forward products only: A (fp32,
+// scheme of the NSR_F16X3 inference kernel) at 3/16 of the fp32-MFMA cycle cost.  Forward products only (the gradient products
+// of NSR_F16X3_GEMM_BWD are kernels of their own: nsr_train_bwd_f16.hip, declared in nsr_train_work.h): A (fp32,
 // K-contiguous, values within fp16 range) is split while it is staged into LDS; B (weights, N x K, K-contiguous) is
 // given pre-split (split_f16).  With `conv.cin > 0` A is not a matrix but an NHWC activation and the rows of the 3 x 3 /
 // pad 1 im2col matrix (K = 9 cin, taps-major) are gathered on the fly (cin % 32 == 0): g.A = activation base,

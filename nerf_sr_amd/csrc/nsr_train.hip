@@ -17,7 +17,7 @@
 //   it makes anyway; the input gradients are one launch of the backward chain (nsr_train_chain.hip), which keeps its fp16
 //   operands likewise.  Both write 2-byte "panels" in 1 KiB units (nsr_f16x3_core.h) that the weight gradients are computed
 //   from (nsr_train_wgrad.hip, chain_weight_grads).
-//   LAYER-BY-LAYER network (NSR_FP32, NSR_F16X3_GEMM): nsr_train_gemm.hip, a function of an architecture descriptor.
+//   LAYER-BY-LAYER network (NSR_FP32, NSR_F16X3_GEMM, NSR_F16X3_GEMM_BWD): nsr_train_gemm.hip, a function of an architecture descriptor.
 // and two families of entry points over the SAME drivers: nsr_train_* run the default network (the descriptor
 // {8, 256, skips {4}, 10, 4, 0} on the layer-by-layer precisions), nsr_train_arch_* the network of the caller's descriptor
 // (layer-by-layer precisions only).  One saved-state header and layout serves both; it records the descriptor.
@@ -300,8 +300,9 @@ Kept carve_kept(Carver& a, int64_t P, const Shape* net, bool chain_path) {
 // matrices (11 KB per sample point less)
 // ray_grad: behind everything else (the layout in front of them is the same with and without), the three matrices of the
 // gradient with respect to the rays
+// bwd (NSR_F16X3_GEMM_BWD): behind the ray-gradient matrices, the transposed split halves of both packs and the range words
 int64_t work_floats(int64_t chunk, int nc, int ni, const Shape* net, bool split, bool chain_path, Work* w, float* base,
-                    bool ray_grad = false) {
+                    bool ray_grad = false, bool bwd = false) {
   const int64_t nf = nc + ni, P = chunk * nf;
   Carver a{base};
   Work tmp;
@@ -341,6 +342,10 @@ int64_t work_floats(int64_t chunk, int nc, int ni, const Shape* net, bool split,
   k.gdir = a.take(rg ? P * net->Dp : P * 3, (rg && net->Dp > 0) || rgc);
   k.gx = a.take(P * 3, rg || rgc);
   for (int n = 0; n < 2; ++n) k.rgw[n] = a.take(kRayGradImageFloats, rgc);
+  const bool tail = bwd && net;
+  if (tail)
+    for (int n = 0; n < 2; ++n) carve_pack_t(a, *net, k.pack[n]);
+  k.range = reinterpret_cast<unsigned*>(a.take(kRangeWords, tail));
   return a.off;
 }
 
@@ -354,8 +359,12 @@ constexpr int kDefaultBwdTerms = 12;   // NSR_F16X3_BWDM
 int chain_bwd_terms(int precision) {
   return precision == NSR_F16X3_BWD3 ? 3 : (precision == NSR_F16X3_BWD2 ? 2 : (precision == NSR_F16X3_BWD1 ? 1 : (precision == NSR_F16X3_BWDM ? 12 : kDefaultBwdTerms)));
 }
-bool train_precision_ok(int precision) { return precision == NSR_FP32 || chain_selected(precision) || precision == NSR_F16X3_GEMM; }
-bool split_selected(int precision) { return precision == NSR_F16X3_GEMM; }   // split-fp16 forward products of the layer-by-layer network
+bool bwd_selected(int precision) { return precision == NSR_F16X3_GEMM_BWD; }   // ... and its gradient products split-fp16 too
+bool train_precision_ok(int precision) {
+  return precision == NSR_FP32 || chain_selected(precision) || precision == NSR_F16X3_GEMM || bwd_selected(precision);
+}
+// split-fp16 forward products of the layer-by-layer network
+bool split_selected(int precision) { return precision == NSR_F16X3_GEMM || bwd_selected(precision); }
 
 using CompositeBwdFn = decltype(&composite_bwd_kernel<1, false>);
 template <bool FULL> CompositeBwdFn composite_bwd_for(int K) {   // K: samples per lane
@@ -482,15 +491,17 @@ int open_work(Run& c, const float* const* w_coarse, const float* const* w_fine, 
     NSR_TRY(check_alignment(*net, w_fine));
   }
   const bool split = !by_precision || split_selected(c.precision);
-  if (workspace_bytes < (size_t)work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, nullptr, nullptr, ray_grad) * sizeof(float))
+  const bool bwd = bwd_selected(c.precision);
+  if (workspace_bytes < (size_t)work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, nullptr, nullptr, ray_grad, bwd) * sizeof(float))
     return NSR_ERR_WORKSPACE;
-  work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, &k, static_cast<float*>(workspace), ray_grad);
+  work_floats(c.chunk, c.nc, c.ni, net, split, c.chain, &k, static_cast<float*>(workspace), ray_grad, bwd);
   return NSR_OK;
 }
 
 // the weights of both networks in the form the path's kernels read, once per call
+// with_backward: the call also runs the backward half (the fused step; nsr_train_forward's launches are the forward's alone)
 int prepare_call(hipStream_t st, const Work& k, const float* const* w_coarse, const float* const* w_fine, const Run& c,
-                 void* stream) {
+                 void* stream, bool with_backward = true) {
   if (c.chain) {
     // the weights are re-packed every iteration: a run whose weights drift beyond what the split-fp16 stream carries
     // (|w| >= 1023.75, or NaN) raises NSR_FLAG_WEIGHT_RANGE in the step's status word, like nsr_pack_weights does.
@@ -505,6 +516,10 @@ int prepare_call(hipStream_t st, const Work& k, const float* const* w_coarse, co
   } else {
     NSR_TRY(prepare_weights(st, c.net, w_coarse, k.pack[0], split_selected(c.precision)));
     NSR_TRY(prepare_weights(st, c.net, w_fine, k.pack[1], split_selected(c.precision)));
+    if (with_backward && bwd_selected(c.precision)) {
+      NSR_TRY(prepare_weights_t(st, c.net, w_coarse, k.pack[0]));
+      NSR_TRY(prepare_weights_t(st, c.net, w_fine, k.pack[1]));
+    }
     if (hipMemsetAsync(k.carry, 0, 8 * sizeof(double), st) != hipSuccess) return NSR_ERR_LAUNCH;
   }
   return NSR_OK;
@@ -644,7 +659,7 @@ int train_forward(const nsr_arch* arch, unsigned embed, bool by_arch, const floa
   const SavedHeader h{kSavedMagic, (uint64_t)L.total, R, c.chunk, n_coarse, n_importance, render_flags, precision, c.net.arch, embed, ray_stride};
   hipLaunchKernelGGL(saved_header_kernel, dim3(1), dim3(64), 0, st, h, reinterpret_cast<unsigned*>(sv));
   NSR_CHECK_LAUNCH();
-  NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream));
+  NSR_TRY(prepare_call(st, k, w_coarse, w_fine, c, stream, false));
   const float* z_c = nullptr;   // the coarse pass's samples of the chunk at hand
   return for_each_pass(c, [&](const Pass& q) -> int {
     k.kept = saved_kept(sv, L, c, q);
@@ -712,9 +727,14 @@ int train_backward(const nsr_arch* arch, unsigned embed, bool by_arch, const flo
   if (c.chain) {
     for (int n = 0; n < 2; ++n) k.stream_b[n] = saved_stream(sv, L, n);
     if (g_rays) NSR_TRY(raygrad_f16_pack(st, w_coarse, k.rgw[0], w_fine, k.rgw[1]));
-  } else {   // the padded weight copies the backward products read (no split halves: every gradient runs on the fp32 MFMA)
+  } else {   // the padded weight copies the backward products read (no forward halves: NSR_FP32 / NSR_F16X3_GEMM run every
+             // gradient on the fp32 MFMA), and under NSR_F16X3_GEMM_BWD their transposed split halves
     NSR_TRY(prepare_weights(st, c.net, w_coarse, k.pack[0], false));
     NSR_TRY(prepare_weights(st, c.net, w_fine, k.pack[1], false));
+    if (bwd_selected(c.precision)) {
+      NSR_TRY(prepare_weights_t(st, c.net, w_coarse, k.pack[0]));
+      NSR_TRY(prepare_weights_t(st, c.net, w_fine, k.pack[1]));
+    }
   }
   // the fused step's order of passes: the first chunk overwrites the gradients, later chunks accumulate
   return for_each_pass(c, [&](const Pass& q) -> int {
@@ -736,13 +756,14 @@ extern "C" size_t nsr_train_workspace_bytes_for(int precision, int64_t ray_chunk
   Shape S;
   if (!sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) || make_shape(&kDefaultArch, S) != NSR_OK) return 0;
   const bool chain = chain_selected(precision);
-  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, chain ? nullptr : &S, true, chain, nullptr, nullptr) * sizeof(float);
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, chain ? nullptr : &S, true, chain, nullptr, nullptr, false,
+                             bwd_selected(precision)) * sizeof(float);
 }
 
 extern "C" size_t nsr_train_workspace_bytes(int64_t ray_chunk, int n_coarse, int n_importance) {
   Shape S;
   if (!sizes_ok(ray_chunk, n_coarse, n_importance) || make_shape(&kDefaultArch, S) != NSR_OK) return 0;
-  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, true, true, nullptr, nullptr) * sizeof(float);
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, true, true, nullptr, nullptr, false, true) * sizeof(float);
 }
 
 extern "C" size_t nsr_train_arch_workspace_bytes(const nsr_arch* arch, int precision, int64_t ray_chunk, int n_coarse,
@@ -755,7 +776,8 @@ extern "C" size_t nsr_train_arch_workspace_bytes_e(const nsr_arch* arch, unsigne
   if (make_shape(arch, S, embed) != NSR_OK || !sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) ||
       chain_selected(precision))
     return 0;
-  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, split_selected(precision), false, nullptr, nullptr) * sizeof(float);
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, split_selected(precision), false, nullptr, nullptr, false,
+                             bwd_selected(precision)) * sizeof(float);
 }
 
 extern "C" size_t nsr_train_arch_workspace_bytes_r(const nsr_arch* arch, unsigned embed, int precision, int64_t ray_chunk,
@@ -764,7 +786,8 @@ extern "C" size_t nsr_train_arch_workspace_bytes_r(const nsr_arch* arch, unsigne
   if (make_shape(arch, S, embed) != NSR_OK || !sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) ||
       chain_selected(precision))
     return 0;
-  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, split_selected(precision), false, nullptr, nullptr, true) * sizeof(float);
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, &S, split_selected(precision), false, nullptr, nullptr, true,
+                             bwd_selected(precision)) * sizeof(float);
 }
 
 extern "C" int nsr_arch_n_tensors(const nsr_arch* arch) {
@@ -917,7 +940,8 @@ extern "C" size_t nsr_train_workspace_bytes_r(int precision, int64_t ray_chunk, 
   Shape S;
   if (!sizes_ok(ray_chunk, n_coarse, n_importance) || !train_precision_ok(precision) || make_shape(&kDefaultArch, S) != NSR_OK) return 0;
   const bool chain = chain_selected(precision);
-  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, chain ? nullptr : &S, true, chain, nullptr, nullptr, chain) * sizeof(float);
+  return (size_t)work_floats(ray_chunk, n_coarse, n_importance, chain ? nullptr : &S, true, chain, nullptr, nullptr, chain,
+                             bwd_selected(precision)) * sizeof(float);
 }
 
 extern "C" int nsr_train_backward_r(const float* const* w_coarse, const float* const* w_fine, const float* rays, int ray_stride,

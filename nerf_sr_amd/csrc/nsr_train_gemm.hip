@@ -1,5 +1,5 @@
-// The layer-by-layer network of the training step (precisions NSR_FP32 and NSR_F16X3_GEMM; the drivers of nsr_train.hip call
-// it), for ANY architecture the reference's flags describe (include/nsr_train.h, nsr_arch: --D --W --skips --deg_pos --deg_dir
+// The layer-by-layer network of the training step (precisions NSR_FP32, NSR_F16X3_GEMM and NSR_F16X3_GEMM_BWD; the drivers of
+// nsr_train.hip call it), for ANY architecture the reference's flags describe (include/nsr_train.h, nsr_arch: --D --W --skips --deg_pos --deg_dir
 // --no_dir).  The default 8 x 256 network is the descriptor {8, 256, skips {4}, 10, 4, 0}: there is no second implementation.
 //
 // The MLP runs layer by layer on one fp32-MFMA GEMM kernel (nsr_gemm.hip; nsr_gemm_f16.hip for the split-fp16 forward
@@ -7,7 +7,9 @@
 // orientation of each operand, so all three products of a linear layer (forward, input gradient, weight gradient) read
 // the row-major (P, C) activations and the nn.Linear weights as they lie: nothing is transposed and nothing is stored
 // twice.  The weight gradient is a split-K GEMM over the sample points with a deterministic second-pass reduction (no
-// atomics: results are run-to-run identical).
+// atomics: results are run-to-run identical).  Under NSR_F16X3_GEMM_BWD the input and weight gradients run on the split-fp16 MFMA
+// instead (nsr_train_bwd_f16.hip: the same contracts, the same order of products; the input gradients read transposed split
+// copies of the weights, Pack::ht, the one thing that precision stores twice).
 //
 // Everything is a function of the descriptor at run time (Shape, nsr_train_work.h: the layout of a pass is described there):
 // the padded shapes, the kept state, the padded weight copies and their split-fp16 halves (Pack), the drivers over the D trunk
@@ -384,9 +386,21 @@ int lin_fwd_at(hipStream_t st, const float* x, int64_t ldx, int K, const float* 
 // dx (P, N) = (dy (P, K) w[:, 0 : N]) * [mask > 0], w (K, ldw) in the nn.Linear layout (mask may be null);
 // bias_grad (N) (+)= column sums of dx = the bias gradient of the layer that produced the masked activation
 // n_bias (0: N): how many of the N columns the bias has (a padded layer's trailing columns are exact zeros)
+// t.hi non-null (a pack prepared for NSR_F16X3_GEMM_BWD): the product on the split-fp16 MFMA from the transposed halves of the
+// same columns (nsr_train_bwd_f16.hip), which also raises *out_max (may be null) to the float bits of the largest |dx|
+struct WT {   // rows [0, N) of a transposed split copy: hi halves, the lo halves lo_off behind them, row stride ld halves
+  const unsigned short* hi;
+  int64_t lo_off;
+  int ld;
+};
 int lin_dgrad(hipStream_t st, float* col_tiles, const float* dy, int64_t lddy, int K, const float* w, int ldw,
               const float* mask, int64_t ldm, float* dx, int64_t lddx, int64_t P, int N, float* bias_grad, int acc,
-              int n_bias) {
+              int n_bias, WT t = WT{nullptr, 0, 0}, unsigned* out_max = nullptr) {
+  if (t.hi) {
+    NSR_TRY(dgrad_f16x3(st, dy, lddy, K, t.hi, t.hi + t.lo_off, t.ld, mask, ldm, dx, lddx, P, N, bias_grad ? col_tiles : nullptr,
+                        out_max));
+    return bias_grad ? tile_sums(st, col_tiles, (P + 127) / 128, N, n_bias, bias_grad, acc) : NSR_OK;
+  }
   GemmArgs g{};
   g.A = dy; g.lda = lddy; g.B = w; g.ldb = ldw; g.b_kmajor = 1; g.C = dx; g.ldc = lddx;
   g.mask = mask; g.ldm = ldm; g.M = P; g.N = N; g.K = K; g.n_valid = N; g.act = kActNone; g.splits = 1;
@@ -398,7 +412,9 @@ int lin_dgrad(hipStream_t st, float* col_tiles, const float* dy, int64_t lddy, i
 // partial[z] (M x N) = sum over the z-th slice of the points of dy[p][0..M) x[p][0..N)^T
 // (slice z at partial + z * stride)
 int lin_wgrad(hipStream_t st, const float* dy, int64_t lddy, int M, const float* x, int64_t ldx, int N, int64_t P,
-              float* partial, int splits, int64_t stride) {
+              float* partial, int splits, int64_t stride, const unsigned* max_bits = nullptr) {
+  // max_bits non-null (NSR_F16X3_GEMM_BWD): on the split-fp16 MFMA, dy scaled by one power of two from the matrix's range word
+  if (max_bits) return wgrad_f16x3(st, dy, lddy, M, x, ldx, N, P, max_bits, partial, splits, stride);
   GemmArgs g{};
   g.A = dy; g.lda = lddy; g.a_kmajor = 1; g.B = x; g.ldb = ldx; g.b_kmajor = 1; g.C = partial; g.ldc = N;
   g.M = M; g.N = N; g.K = P; g.n_valid = N; g.act = kActNone; g.splits = splits; g.split_stride = stride;
@@ -546,6 +562,26 @@ int nsr::prepare_weights(hipStream_t st, const Shape& S, const float* const* w, 
   }
   return NSR_OK;
 }
+// the transposed split halves of the matrices the input gradients multiply by (Pack::ht; hi then lo)
+void nsr::carve_pack_t(Carver& a, const Shape& S, Pack& q) {
+  for (int l = 0; l < S.D; ++l) q.ht[l] = reinterpret_cast<unsigned short*>(a.take((int64_t)S.Wp * S.kin(l)));
+  q.ht[kFinalE] = reinterpret_cast<unsigned short*>(a.take((int64_t)(S.Wp + 32) * S.Wp));
+  q.ht[kSigmaE] = nullptr;
+  q.ht[kDirE] = reinterpret_cast<unsigned short*>(a.take((int64_t)S.Hp * S.Ci));
+  q.ht[kRgbE] = reinterpret_cast<unsigned short*>(a.take(32 * (int64_t)S.Hp));
+}
+int nsr::prepare_weights_t(hipStream_t st, const Shape& S, const float* const* w, const Pack& q) {
+  if (!q.ht[0]) return NSR_ERR_INVALID_ARG;
+  for (int l = 0; l < S.D; ++l) {
+    const Lin a = trunk_lin(S, q, w, l);
+    NSR_TRY(split_f16_t(st, a.w, S.Wp, S.kin(l), a.ldw, q.ht[l], q.ht[l] + (int64_t)S.Wp * S.kin(l)));
+  }
+  const int ldg = S.Wp + 32;
+  NSR_TRY(split_f16_t(st, q.w9, ldg, S.Wp, S.Wp, q.ht[kFinalE], q.ht[kFinalE] + (int64_t)ldg * S.Wp));
+  NSR_TRY(split_f16_t(st, q.wdir, S.Hp, S.Ci, S.Ci, q.ht[kDirE], q.ht[kDirE] + (int64_t)S.Hp * S.Ci));
+  NSR_TRY(split_f16_t(st, q.wrgb, 32, S.Hp, S.Hp, q.ht[kRgbE], q.ht[kRgbE] + 32 * (int64_t)S.Hp));
+  return NSR_OK;
+}
 
 // one encoded row per sample point, columns [0, 4 n_groups), into each of the n_dst destinations (row stride ld floats)
 int nsr::encode_arch(hipStream_t st, const float* rays, int ray_stride, const float* z, int64_t P, int N, int deg, int view_dir,
@@ -593,14 +629,30 @@ int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, con
   const int64_t ps = S.part_stride;
   float* part = k.partial;
   const int ldg = S.Wp + 32;
+  // NSR_F16X3_GEMM_BWD: every product below on the split-fp16 MFMA.  Range word i holds the float bits of the largest magnitude
+  // of one gradient matrix: 0 = d rgb_pre, 1 = d sigma (both from d4), 2 = the colour head's input gradient, 3 = dir_encoding's,
+  // 4 = the stacked final + sigma layer's, 5 .. = the trunk layers' top down -- raised by the product that writes the matrix,
+  // read by the weight gradient that contracts it over the points
+  const bool f16 = q.ht[0] != nullptr;
+  auto word = [&](int i) -> unsigned* { return f16 ? k.range + i : nullptr; };
+  auto wt = [&](int e, int K, int64_t n, int row0) -> WT {   // rows row0 .. of entry e, a (rows x K) transposed copy of n halves
+    return f16 ? WT{q.ht[e] + (int64_t)row0 * K, n, K} : WT{nullptr, 0, 0};
+  };
+  if (f16) {
+    if (hipMemsetAsync(k.range, 0, kRangeWords * sizeof(unsigned), st) != hipSuccess) return NSR_ERR_LAUNCH;
+    NSR_TRY(absmax_bits(st, k.d4, 4, P, 0, 3, word(0)));
+    NSR_TRY(absmax_bits(st, k.d4, 4, P, 3, 1, word(1)));
+  }
+  const int64_t n_rgb = 32 * (int64_t)S.Hp, n_dir = (int64_t)S.Hp * S.Ci, n_w9 = (int64_t)ldg * S.Wp;
   NSR_TRY(scatter_heads(st, k.d4, P, k.drgb, k.g1 + S.Wp, ldg));
   // rgb head
-  NSR_TRY(lin_wgrad(st, k.drgb, 32, 32, s.cc, S.Hp, S.Hp, P, part, sp, ps));
+  NSR_TRY(lin_wgrad(st, k.drgb, 32, 32, s.cc, S.Hp, S.Hp, P, part, sp, ps, word(0)));
   NSR_TRY(reduce_place(st, g[S.rgb_w()], S.H, 0, 3, S.H, part, sp, S.Hp, 0, 0, acc, 1.0f, ps));
   NSR_TRY(colsum(st, k.drgb, 32, P, 0, 3, g[S.rgb_w() + 1], acc, part));
-  NSR_TRY(lin_dgrad(st, k.col_tiles, k.drgb, 32, 32, q.wrgb, S.Hp, s.cc, S.Hp, k.g0, S.Hp, P, S.Hp, g[S.dir_w() + 1], acc, S.H));
+  NSR_TRY(lin_dgrad(st, k.col_tiles, k.drgb, 32, 32, q.wrgb, S.Hp, s.cc, S.Hp, k.g0, S.Hp, P, S.Hp, g[S.dir_w() + 1], acc, S.H,
+                    wt(kRgbE, 32, n_rgb, 0), word(2)));
   // dir_encoding: its input is [final | dir pe]
-  NSR_TRY(lin_wgrad(st, k.g0, S.Hp, S.Hp, s.ci, S.Ci, S.Ci, P, part, sp, ps));
+  NSR_TRY(lin_wgrad(st, k.g0, S.Hp, S.Hp, s.ci, S.Ci, S.Ci, P, part, sp, ps, word(2)));
   NSR_TRY(reduce_place(st, g[S.dir_w()], S.dir_in(), 0, S.H, S.W, part, sp, S.Ci, 0, 0, acc, 1.0f, ps));
   if (!S.no_dir) NSR_TRY(reduce_place(st, g[S.dir_w()], S.dir_in(), S.W, S.H, S.in_dir, part, sp, S.Ci, 0, S.Wp, acc, 1.0f, ps));
   const int F = S.final_w();
@@ -608,26 +660,30 @@ int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, con
     if (hipMemset2DAsync(k.g1, (size_t)ldg * sizeof(float), 0, (size_t)S.Wp * sizeof(float), (size_t)P, st) != hipSuccess) return NSR_ERR_LAUNCH;
     if (!acc && hipMemsetAsync(g[F + 1], 0, (size_t)S.W * sizeof(float), st) != hipSuccess) return NSR_ERR_LAUNCH;
   } else {
-    NSR_TRY(lin_dgrad(st, k.col_tiles, k.g0, S.Hp, S.Hp, q.wdir, S.Ci, nullptr, 0, k.g1, ldg, P, S.Wp, g[F + 1], acc, S.W));
+    NSR_TRY(lin_dgrad(st, k.col_tiles, k.g0, S.Hp, S.Hp, q.wdir, S.Ci, nullptr, 0, k.g1, ldg, P, S.Wp, g[F + 1], acc, S.W,
+                      wt(kDirE, S.Hp, n_dir, 0), word(3)));
   }
   // --stop_grad detaches dir_encoding's whole input, the encoded direction included
   const bool dir_term = rg && !S.no_dir && !stop_grad;
-  if (dir_term) NSR_TRY(lin_dgrad(st, k.col_tiles, k.g0, S.Hp, S.Hp, q.wdir + S.Wp, S.Ci, nullptr, 0, k.gdir, S.Dp, P, S.Dp, nullptr, 0, 0));
+  if (dir_term) NSR_TRY(lin_dgrad(st, k.col_tiles, k.g0, S.Hp, S.Hp, q.wdir + S.Wp, S.Ci, nullptr, 0, k.gdir, S.Dp, P, S.Dp, nullptr, 0, 0,
+                                  wt(kDirE, S.Hp, n_dir, S.Wp)));
   // xyz_encoding_final + sigma: the (Wp + 32)-row layer over the trunk's last activation
   const Mat hD = out_of(S, s, S.D - 1);
-  NSR_TRY(lin_wgrad(st, k.g1, ldg, S.Wp, hD.p, hD.ld, S.Wp, P, part, sp, ps));
+  NSR_TRY(lin_wgrad(st, k.g1, ldg, S.Wp, hD.p, hD.ld, S.Wp, P, part, sp, ps, word(3)));
   NSR_TRY(reduce_place(st, g[F], S.W, 0, S.W, S.W, part, sp, S.Wp, 0, 0, acc, 1.0f, ps));
-  NSR_TRY(lin_wgrad(st, k.g1 + S.Wp, ldg, 32, hD.p, hD.ld, S.Wp, P, part, sp, ps));
+  NSR_TRY(lin_wgrad(st, k.g1 + S.Wp, ldg, 32, hD.p, hD.ld, S.Wp, P, part, sp, ps, word(1)));
   NSR_TRY(reduce_place(st, g[S.sigma_w()], S.W, 0, 1, S.W, part, sp, S.Wp, 0, 0, acc, 1.0f, ps));
   NSR_TRY(colsum(st, k.g1, ldg, P, S.Wp, 1, g[S.sigma_w() + 1], acc, part));
-  NSR_TRY(lin_dgrad(st, k.col_tiles, k.g1, ldg, ldg, q.w9, S.Wp, hD.p, hD.ld, k.g0, S.Wp, P, S.Wp, g[2 * (S.D - 1) + 1], acc, S.W));
+  NSR_TRY(lin_dgrad(st, k.col_tiles, k.g1, ldg, ldg, q.w9, S.Wp, hD.p, hD.ld, k.g0, S.Wp, P, S.Wp, g[2 * (S.D - 1) + 1], acc, S.W,
+                    wt(kFinalE, ldg, n_w9, 0), word(4)));
   // trunk, top down; the gradient of a layer's pre-activation alternates between the two buffers
   const float* dy = k.g0;
   float* nx = k.g1;
+  int dyw = 4;   // the range word of dy
   for (int l = S.D - 1; l >= 0; --l) {
     const Mat x = in_of(S, s, l);
     const int kin = S.kin(l), fi = S.fan_in(l);
-    NSR_TRY(lin_wgrad(st, dy, S.Wp, S.Wp, x.p, x.ld, kin, P, part, sp, ps));
+    NSR_TRY(lin_wgrad(st, dy, S.Wp, S.Wp, x.p, x.ld, kin, P, part, sp, ps, word(dyw)));
     float* gw = g[2 * l];
     if (S.skip(l)) {   // [pe | h] columns of the padded product -> the nn.Linear columns
       NSR_TRY(reduce_place(st, gw, fi, 0, S.W, S.in_xyz, part, sp, kin, 0, 0, acc, 1.0f, ps));
@@ -638,14 +694,15 @@ int nsr::net_backward(hipStream_t st, const Shape& S, const float* const* w, con
     if (rg && (l == 0 || S.skip(l))) {   // the layer reads the encoded position: the gradient of its pe columns
       const Lin a = trunk_lin(S, q, w, l);
       NSR_TRY(lin_dgrad(st, k.col_tiles, dy, S.Wp, S.Wp, a.w, a.ldw, nullptr, 0, k.gpe + (int64_t)(l == 0 ? 0 : 1 + S.x_of[l]) * P * S.Kx, S.Kx, P, S.Kx,
-                        nullptr, 0, 0));
+                        nullptr, 0, 0, wt(l, S.Wp, (int64_t)S.Wp * kin, 0)));
     }
     if (l == 0) break;
     // the layer's input h is the ReLU output of layer l - 1: its mask, and that layer's bias gradient
     const Mat m = out_of(S, s, l - 1);
     const Lin a = trunk_lin(S, q, w, l);
     NSR_TRY(lin_dgrad(st, k.col_tiles, dy, S.Wp, S.Wp, a.w + (S.skip(l) ? S.Kx : 0), a.ldw, m.p, m.ld, nx, S.Wp, P, S.Wp, g[2 * (l - 1) + 1],
-                      acc, S.W));
+                      acc, S.W, wt(l, S.Wp, (int64_t)S.Wp * kin, S.skip(l) ? S.Kx : 0), word(dyw + 1)));
+    ++dyw;
     const float* t0 = dy; dy = nx; nx = const_cast<float*>(t0);
   }
   if (!rg) return NSR_OK;

@@ -87,6 +87,10 @@ struct Pack {
   float* bl[kMaxD];
   float *w9, *b9, *wdir, *bdir, *wrgb, *brgb;
   unsigned short* hi[kNumE];
+  // NSR_F16X3_GEMM_BWD only (else null): the TRANSPOSED split halves the input-gradient products read (nsr_train_bwd_f16.hip),
+  // hi then lo, each (fan-in x fan-out) with the fan-out contiguous: trunk layer l (kin(l) x Wp), kFinalE = the stacked
+  // xyz_encoding_final + sigma layer (Wp x (Wp + 32)), kDirE (Ci x Hp), kRgbE (Hp x 32); kSigmaE is not used
+  unsigned short* ht[kNumE];
 };
 
 // What the forward half of a pass over P sample points leaves for its backward half (all row-major).  The fused step keeps
@@ -126,7 +130,11 @@ struct Work {   // the workspace of a call, sized for P_max = chunk * (Nc + Ni) 
   // chain path, nsr_train_backward_r with g_rays (null otherwise): gx (P, 3) and gdir (P, 3) = per point d(loss) / d(x) and the
   // back-propagated direction term, and per network the packed weight columns of raygrad_f16 (kRayGradPieces KiB)
   float* rgw[2];
+  // NSR_F16X3_GEMM_BWD (null otherwise; behind everything else, with the packs' transposed halves): kRangeWords words, cleared by
+  // net_backward, each the float bits of the largest magnitude of one gradient matrix (the weight gradients' range)
+  unsigned* range;
 };
+constexpr int kRangeWords = 64;
 // the pass's rows of d(loss) / d(rays) for net_backward: `rays` rays of N samples at depths z; acc: added to (the fine pass)
 struct RayGrad {
   float* rows;
@@ -197,6 +205,9 @@ NSR_INTERNAL int make_shape(const nsr_arch* a, Shape& S, unsigned embed = 0u);
 NSR_INTERNAL int64_t tensor_numel_of(const Shape& S, int t);
 NSR_INTERNAL void carve_net_kept(Carver& a, const Shape& S, int64_t P, Kept& q);   // x, h, ci, cc
 NSR_INTERNAL Pack carve_pack(Carver& a, const Shape& S, bool split);
+// NSR_F16X3_GEMM_BWD: the pack's transposed split halves (Pack::ht), and their preparation once per call (after prepare_weights)
+NSR_INTERNAL void carve_pack_t(Carver& a, const Shape& S, Pack& q);
+NSR_INTERNAL int prepare_weights_t(hipStream_t st, const Shape& S, const float* const* w, const Pack& q);
 // a trunk layer without a padded copy is the GEMMs' operand where the caller holds it: 16-byte aligned, else NSR_ERR_INVALID_ARG
 NSR_INTERNAL int check_alignment(const Shape& S, const float* const* w);
 // split: also the (hi, lo) fp16 halves of the forward matrices (NSR_F16X3_GEMM; the pack must have been carved with them)
@@ -216,6 +227,24 @@ NSR_INTERNAL int net_forward(hipStream_t st, const Shape& S, const float* rays, 
 // rg (null: none): also the pass's rows of d(loss) / d(rays), through k.gpe / k.gdir / k.gx
 NSR_INTERNAL int net_backward(hipStream_t st, const Shape& S, const float* const* w, const Pack& q, const Work& k, int64_t P,
                               float* const* g, int acc, int stop_grad, const RayGrad* rg = nullptr);
+// ---- nsr_train_bwd_f16.hip: the gradient products on the split-fp16 MFMA (three terms, small terms first, fp32 accumulation)
+// hi[c * rows + r] = fp16(v), lo[c * rows + r] = fp16(v - hi), v = 2^6 w[r * ldw + c]: the transposed split copy of (rows x cols)
+NSR_INTERNAL int split_f16_t(hipStream_t st, const float* w, int rows, int cols, int ldw, unsigned short* hi, unsigned short* lo);
+// *word = max(*word, float bits of the largest |src[p * ld + col0 + c]|, p < P, c < cols): integer atomicMax on the bit patterns
+NSR_INTERNAL int absmax_bits(hipStream_t st, const float* src, int64_t ld, int64_t P, int col0, int cols, unsigned* word);
+// dx (P, N) = (dy (P, K) wt^T) * [mask > 0] with wt (N, K) the transposed split halves (row stride ldwt halves, a multiple of
+// 8); K, N multiples of 32, lddy a multiple of 4 (else NSR_ERR_UNSUPPORTED), any P >= 1.  mask (row stride ldm), col_tiles
+// ((ceil(P / 128), N): per-128-row-tile column sums of dx, what tile_sums reads) and out_max (raised to the float bits of the
+// largest |dx|) may be null.  dy is scaled PER ROW: a row of dx depends on that row of dy, its mask row and the weights only
+NSR_INTERNAL int dgrad_f16x3(hipStream_t st, const float* dy, int64_t lddy, int K, const unsigned short* wt_hi,
+                             const unsigned short* wt_lo, int ldwt, const float* mask, int64_t ldm, float* dx, int64_t lddx, int64_t P,
+                             int N, float* col_tiles, unsigned* out_max);
+// partial[z] (M x N, row stride N, at partial + z * stride) = sum over the points p of slice z of dy[p][0 : M) x[p][0 : N)^T;
+// slice z = points [z L, min((z + 1) L, P)), L = bwd_f16_slice_len(P, splits) (a slice behind P writes zeros); M, N multiples
+// of 32, lddy, ldx of 4.  *max_bits: float bits of a bound of max |dy| (device memory): ONE power of two for the matrix
+NSR_INTERNAL int64_t bwd_f16_slice_len(int64_t P, int splits);
+NSR_INTERNAL int wgrad_f16x3(hipStream_t st, const float* dy, int64_t lddy, int M, const float* x, int64_t ldx, int N, int64_t P,
+                             const unsigned* max_bits, float* partial, int splits, int64_t stride);
 // ---- nsr_train_gemm.hip: the two kernels of the gradient with respect to the rays
 // backward of encode_arch's row: g_x (P, 3) = d(loss) / d(x) from the gradients of the encoded columns, summed over the n_src
 // (1 .. kMaxD) sources src[j] (P, ld_src; ld_src a multiple of 4, rows 16-byte aligned; columns [0, 4 n_groups) are read,

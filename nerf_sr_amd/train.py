@@ -128,7 +128,9 @@ def _weights(params, name: str, arch: Optional[dict] = None, no_xyz: bool = Fals
 # ---------------------------------------------------------------------------------------------------------------------
 # non-default architectures (--D --W --skips --deg_pos --deg_dir --no_dir): struct nsr_arch of include/nsr_train.h
 # ---------------------------------------------------------------------------------------------------------------------
-ARCH_PRECISIONS = ("fp32", "f16x3_gemm")      # what the layer-by-layer training pair runs; 'f16x3' maps to 'f16x3_gemm'
+# what the layer-by-layer training pair runs; 'f16x3' maps to 'f16x3_gemm'.  'f16x3_gemm_bwd' (opt-in) is 'f16x3_gemm' with every
+# gradient product on the split-fp16 MFMA as well (three terms, fp32 accumulation; include/nsr_train.h NSR_F16X3_GEMM_BWD)
+ARCH_PRECISIONS = ("fp32", "f16x3_gemm", "f16x3_gemm_bwd")
 _ARCH_WARNED = set()
 
 
@@ -142,7 +144,7 @@ def normalize_arch(arch) -> dict:
 
 
 def arch_precision(arch: dict, precision: str) -> str:
-    """The precision the layer-by-layer pair runs for ``precision``: 'fp32' and 'f16x3_gemm' as they are; 'f16x3' (the
+    """The precision the layer-by-layer pair runs for ``precision``: 'fp32', 'f16x3_gemm' and 'f16x3_gemm_bwd' as they are; 'f16x3' (the
     chain kernels, laid out for the default network) maps to 'f16x3_gemm' -- the same split-fp16 forward products, gradients
     on the fp32 MFMA -- with one RuntimeWarning per architecture and process; the other chain names raise ValueError."""
     if precision in ARCH_PRECISIONS:
@@ -319,8 +321,12 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     ``arch``: the architecture flags of both networks (a dict with any of D, W, skips, deg_pos, deg_dir, no_dir, or an options
     object carrying ``--D --W --skips --deg_pos --deg_dir --no_dir``): the layer-by-layer pair ``nsr_train_arch_forward`` /
     ``nsr_train_arch_backward`` over the 2 D + 8 tensors of each network, e.g. the reference's own ``netCoarse`` /
-    ``netFine`` built with those flags.  ``precision``: 'fp32' or 'f16x3_gemm' ('f16x3' maps to 'f16x3_gemm' with one
-    RuntimeWarning per architecture; the chain names raise ValueError).  None = the default network, as before.
+    ``netFine`` built with those flags.  ``precision``: 'fp32', 'f16x3_gemm' or 'f16x3_gemm_bwd' ('f16x3' maps to 'f16x3_gemm' with
+    one RuntimeWarning per architecture; the chain names raise ValueError).  None = the default network, as before.
+    'f16x3_gemm_bwd' (opt-in) has 'f16x3_gemm''s forward, bit for bit, and runs every product of the backward -- input gradients,
+    weight gradients, the ray gradient's products -- on the split-fp16 MFMA too: hi / lo fp16 halves, three MFMAs per product
+    (lo hi + hi lo + hi hi), fp32 accumulation, gradients scaled by exact powers of two per sample point (input gradients) or
+    per matrix (weight gradients).
 
     ``rays`` that require grad get ``d(loss)/d(rays)`` (``nsr_train_arch_backward_r``) when the run is the layer-by-layer pair's:
     ``arch=`` or ``embed=`` given, or ``precision`` 'fp32' / 'f16x3_gemm' on the default network (which then runs as the default
@@ -432,7 +438,9 @@ class Trainer:
                              "kernels: forward on the split-fp16 MFMA, weight gradients on one fp16 MFMA per product, input "
                              "gradients on the default number of MFMA terms), 'f16x3_bwd3' / 'f16x3_bwd2' / 'f16x3_bwd1' / 'f16x3_bwdm' (the "
                              "chain kernels with three / two / one / mixed two-one MFMAs per product of the input gradients, include/nsr_train.h) "
-                             "or 'f16x3_gemm' (layer by layer, forward products split-fp16, gradients fp32)")
+                             "'f16x3_gemm' (layer by layer, forward products split-fp16, gradients fp32) or 'f16x3_gemm_bwd' "
+                             "(the same forward; every gradient product split-fp16 as well: three fp16 MFMAs per product, fp32 "
+                             "accumulation, power-of-two scaling per sample point / per matrix)")
         self.precision, self._prec = precision, _lib.TRAIN_PRECISIONS[precision]
         self.device = torch.device(device)
         # --no_dir (models/networks.py:160-169): the networks are trained as the full layout with 27 zero columns in
