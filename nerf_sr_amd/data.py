@@ -226,7 +226,7 @@ class RaySet:
         s = self.downscale
         rays = self.view_rays(i)
         out = {"rays": rays, "rays_ori": unflatten_reshape(rays.view(-1, 8), self.img_wh, s).reshape(H * W, 8),
-               "c2w": torch.from_numpy(self.poses_host[i].copy()).to(self.device)}
+               "c2w": self.poses[i].view(3, 4).clone()}      # the device copy of poses_host[i]: no host staging
         if self.hr is None:
             return out
         n = (H // s) * (W // s)

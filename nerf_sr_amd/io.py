@@ -272,6 +272,35 @@ def lanczos_tables(in_size: int, out_size: int):
     return bounds, kk
 
 
+# (in_size, out_size, device) -> (bounds, kk, ksize, event of the copy): a function of the two sizes, never modified
+_DEVICE_TABLES = {}
+
+
+def _device_tables(in_size: int, out_size: int, device):
+    """``lanczos_tables`` on ``device`` (the CURRENT device: ``resize_lanczos_u8`` checks that), made once per size pair.  A new
+    pair is staged through pinned memory and copied on the current stream without waiting for it (torch keeps the pinned block
+    until the copy has run).  Every use, on whatever stream, is ordered behind that copy by its event: a wait on the device,
+    never on the host.  A new pair cannot be staged while the stream is being captured (the graph would replay a copy from a
+    pinned block that torch recycles): ``RuntimeError``; resize once at these sizes before capturing."""
+    import torch
+    key = (int(in_size), int(out_size), torch.device(device))
+    hit = _DEVICE_TABLES.get(key)
+    capturing = torch.cuda.is_current_stream_capturing()
+    if hit is None:
+        if capturing:
+            raise RuntimeError(f"resize_lanczos_u8: the tables for {in_size} -> {out_size} samples are not on the device yet and cannot "
+                               "be staged inside a stream capture; resize once at these sizes before capturing")
+        bounds, kk = lanczos_tables(in_size, out_size)
+        b_dev = torch.from_numpy(bounds).pin_memory().to(device, non_blocking=True)
+        k_dev = torch.from_numpy(kk).pin_memory().to(device, non_blocking=True)
+        copied = torch.cuda.Event()
+        copied.record()
+        _DEVICE_TABLES[key] = hit = (b_dev, k_dev, int(kk.shape[1]), copied)
+    if not capturing:     # a capture cannot wait for an event recorded outside it; the copy ran long before a capture's replay
+        torch.cuda.current_stream().wait_event(hit[3])
+    return hit[:3]
+
+
 def resize_lanczos_u8(img, out_wh):
     """``PIL.Image.resize(out_wh, Image.LANCZOS)`` of an (H, W, C) uint8 image ON THE DEVICE, bit-identical to Pillow
     (horizontal pass, then vertical pass; include/nsr_image.h).  ``img``: uint8 torch tensor on the GPU.
@@ -298,10 +327,9 @@ def resize_lanczos_u8(img, out_wh):
         in_size = W if axis == 1 else H
         if out_size == in_size:
             continue
-        bounds, kk = lanczos_tables(in_size, out_size)
-        b_dev, k_dev = torch.from_numpy(bounds).to(img.device), torch.from_numpy(kk).to(img.device)
+        b_dev, k_dev, ksize = _device_tables(in_size, out_size, img.device)
         dst = torch.empty((H, out_size, C) if axis == 1 else (out_size, W, C), dtype=torch.uint8, device=img.device)
-        _lib.check(lib.nsr_resample_pass_u8(_p(img), H, W, C, axis, out_size, _p(b_dev), _p(k_dev), kk.shape[1], _p(dst),
+        _lib.check(lib.nsr_resample_pass_u8(_p(img), H, W, C, axis, out_size, _p(b_dev), _p(k_dev), ksize, _p(dst),
                                             _stream()), "nsr_resample_pass_u8")
         img = dst
     if rgba:

@@ -132,8 +132,9 @@ class MaxPoolingModel:
             dev.append(v.to(device=self.device, dtype=torch.float32).contiguous())
         ptrs = (c_void_p * len(dev))(*[c_void_p(t.data_ptr()) for t in dev])
         pack = _lib.load().nsr_refine_pack_weights_noref if self.not_use_ref else _lib.load().nsr_refine_pack_weights
+        # enqueue only: `dev` may be dropped here -- torch's allocator hands a freed block to later work of this stream alone,
+        # which runs behind the pack kernels
         _lib.check(pack(ptrs, _p(self.packed), self._prec, _stream()), "nsr_refine_pack_weights")
-        torch.cuda.current_stream().synchronize()       # `dev` may be freed once the pack kernels have run
         self._loaded = True
         return self
 
