@@ -305,7 +305,9 @@ def resize_lanczos_u8(img, out_wh):
     """``PIL.Image.resize(out_wh, Image.LANCZOS)`` of an (H, W, C) uint8 image ON THE DEVICE, bit-identical to Pillow
     (horizontal pass, then vertical pass; include/nsr_image.h).  ``img``: uint8 torch tensor on the GPU.
     C = 4 is an RGBA image: resampled premultiplied, like Pillow does (``convert("RGBa")`` -> resample ->
-    ``convert("RGBA")``); C = 1 / 3: plain channels.  Other channel counts have no Pillow mode behind them."""
+    ``convert("RGBA")``); C = 1 / 3: plain channels.  Other channel counts have no Pillow mode behind them.
+    Another dtype than uint8 raises ``TypeError`` (nothing is converted); a view is read through a dense copy.  The result is
+    a fresh tensor, except that a resize to the size the image already has returns the (contiguous) input itself."""
     import torch
     from . import _lib
     from .ops import _check_device, _p, _stream

@@ -7,6 +7,11 @@ difference, product and sum in double: the values agree with the reference's cla
 identical calls give identical bits.  Each call returns a 0-d fp32 tensor on the inputs' device that back-propagates to every
 input that requires grad (``|.|`` differentiates to ``sign`` with ``sign(0) = 0``, as ``torch.abs`` does).  All arithmetic runs
 in libnsr.so; there is no CPU path.
+
+Inputs ("Inputs"): device tensors of any floating dtype and memory form; they are CONVERTED to dense float32
+(``.to(torch.float32).contiguous()``, as the reference's torch ops would promote them), never written, and the gradient comes
+back in the input's dtype and shape through that conversion.  The host or another GPU raises ``ValueError``, a shape that does
+not fit ``ValueError``, both before anything is enqueued.
 """
 from __future__ import annotations
 

@@ -5,6 +5,10 @@ table) and ``PSNR`` ``:27-36`` (``value[valid_mask]`` with an element mask or a 
 fixed-order reduction with every product and sum in double, so the values agree with the reference evaluated in fp64 and
 a frame gives the same bits whatever batch it is part of.  ``SSIM`` is differentiable as the reference's is: with an input
 that requires grad it back-propagates through ``nsr_ssim_backward``.  All arithmetic runs in libnsr.so; there is no CPU path.
+
+Inputs ("Inputs"): images are float32 on the current device -- another dtype raises ``TypeError``, nothing is
+converted (so "the inputs' dtype" of a result is float32) --, in any memory form (a view is read through a dense copy); a mask
+is bool or uint8.  Results are fresh tensors.
 """
 from __future__ import annotations
 
@@ -14,7 +18,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .ops import _f32, _p, _stream
+from .ops import _check_device, _f32, _p, _stream
 
 LAYOUTS = {"BCHW": _lib.NSR_LAYOUT_BCHW, "BHWC": _lib.NSR_LAYOUT_BHWC}
 REDUCTIONS = ("mean", "sum", "none")
@@ -53,7 +57,8 @@ class SSIM:
     """``SSIM(data_range, kernel_size, sigma, k1, k2, gaussian)(output, target, reduction)`` of the reference, on the GPU.
 
     ``layout='BHWC'`` reads (B, H, W, C) frames (the NeRF side's images) without a permute; ``return_map=True`` also returns
-    the (B, C, H, W) fp32 map the means are taken over.  Returns a tensor of the inputs' dtype: the per-image values for
+    the (B, C, H, W) fp32 map the means are taken over.  Returns a tensor of the inputs' dtype (float32: any other raises
+    ``TypeError``): the per-image values for
     ``reduction='none'``, their mean or sum otherwise.
 
     As the reference's chain of torch ops does, the result back-propagates: when ``output`` or ``target`` requires grad, the
@@ -177,6 +182,7 @@ def _mask_bytes(valid_mask: Optional[torch.Tensor], shape, lead: int) -> Tuple[O
         group *= int(d)
     if not valid_mask.is_cuda:
         raise ValueError("valid_mask must live on the GPU (nerf_sr_amd has no CPU path)")
+    _check_device(valid_mask.device, "valid_mask")
     m = valid_mask.contiguous()
     return (m.view(torch.uint8) if m.dtype == torch.bool else m), group
 

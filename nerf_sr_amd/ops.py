@@ -3,7 +3,11 @@
 Same names, argument meaning and return shapes as the reference functions they
 replace (cited per function), implemented as calls into libnsr.so through the C
 ABI.  PyTorch is plumbing only: it owns the device buffers and the stream.
-All tensors are fp32, contiguous, on the current HIP device.
+Tensor arguments are fp32 on the current HIP device: another dtype raises ``TypeError``, the host or another GPU
+``ValueError`` (``_f32``; nothing is converted silently), a shape that does not fit the other arguments ``ValueError`` --
+all before the first allocation and the first library call.  A non-contiguous view is read through a dense copy (the bits
+of the dense call), inputs are never written, and results are fresh tensors unless a docstring says otherwise
+(INTEGRATION.md, "Inputs").
 """
 from __future__ import annotations
 
@@ -57,6 +61,29 @@ def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def _i32(t: torch.Tensor, name: str) -> torch.Tensor:
+    """An integer index tensor as the dense int32 the kernels read: any integer dtype is converted (``torch.tensor([[0, 0]])``
+    is int64), a floating-point or bool tensor is a ``TypeError``; on the current device, like ``_f32``."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must live on the GPU (nerf_sr_amd has no CPU path)")
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise TypeError(f"{name} must be an integer tensor, got {t.dtype}")
+    _check_device(t.device, name)
+    return t.detach().to(torch.int32).contiguous()
+
+
+def _rays_z(rays: torch.Tensor, z_vals: torch.Tensor):
+    """``(rays, z_vals)`` dense fp32 with z_vals (R, N >= 1) for the R rows of rays (R, 8 | 11): the kernels take R and N from
+    ``z_vals`` and read R rows of ``rays``."""
+    rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
+    _ray_stride(rays)
+    if z_vals.ndim != 2 or z_vals.shape[0] != rays.shape[0] or z_vals.shape[1] < 1:
+        raise ValueError(f"z_vals must be (R, N >= 1) with R = {rays.shape[0]} rays, got {tuple(z_vals.shape)}")
+    return rays, z_vals
+
+
 def _ray_stride(rays: torch.Tensor) -> int:
     """8: nerf_downX rows [o, d, near, far]; 11: vanilla rows with the view direction in columns 8:11."""
     if rays.ndim != 2 or rays.shape[1] not in (8, 11):
@@ -65,10 +92,30 @@ def _ray_stride(rays: torch.Tensor) -> int:
 
 
 def _pack_rays(ori, dir, near, far) -> torch.Tensor:
+    """(R, 8) rows [o, d, near, far] from ``ori`` / ``dir`` (R, 3), already through ``_f32``; a tensor ``near`` / ``far`` goes
+    through the same checks and holds one value per ray ((R,) or (R, 1)), a number is broadcast."""
+    if ori.ndim != 2 or ori.shape[1] != 3 or tuple(dir.shape) != tuple(ori.shape):
+        raise ValueError(f"ori and dir must both be (R, 3), got {tuple(ori.shape)} and {tuple(dir.shape)}")
     R = ori.shape[0]
-    near = near.reshape(R, 1) if isinstance(near, torch.Tensor) else torch.full((R, 1), float(near), device=ori.device)
-    far = far.reshape(R, 1) if isinstance(far, torch.Tensor) else torch.full((R, 1), float(far), device=ori.device)
-    return torch.cat([ori, dir, near, far], 1).contiguous()
+    bounds = []
+    for t, name in ((near, "near"), (far, "far")):
+        if isinstance(t, torch.Tensor):
+            t = _f32(t, name)
+            if tuple(t.shape) not in ((R,), (R, 1)):
+                raise ValueError(f"{name} must hold one value per ray, (R,) or (R, 1) with R = {R}, got {tuple(t.shape)}")
+            bounds.append(t.reshape(R, 1))
+        else:
+            bounds.append(torch.full((R, 1), float(t), dtype=torch.float32, device=ori.device))
+    return torch.cat([ori, dir] + bounds, 1).contiguous()
+
+
+def _jitter(u, R: int, num_samples: int):
+    if u is None:
+        return None
+    u = _f32(u, "u")
+    if tuple(u.shape) != (R, num_samples):
+        raise ValueError(f"u must be (R, num_samples) = ({R}, {num_samples}), got {tuple(u.shape)}")
+    return u
 
 
 def state_dict_to_device(sd, spec, device, own: bool = False) -> Dict[str, torch.Tensor]:
@@ -156,8 +203,7 @@ def sample_along_rays(ori, dir, near, far, num_samples: int, randomized: bool, l
     R = rays.shape[0]
     if randomized and u is None:
         u = torch.rand(R, num_samples, device=rays.device)
-    if u is not None:
-        u = _f32(u, "u")
+    u = _jitter(u, R, num_samples)
     z = torch.empty(R, num_samples, dtype=torch.float32, device=rays.device)
     pts = torch.empty(R, num_samples, 3, dtype=torch.float32, device=rays.device)
     _lib.check(_lib.load().nsr_sample_along_rays(_p(rays), 8, R, num_samples, int(bool(lindisp)), _p(u), _p(z), _p(pts),
@@ -171,12 +217,14 @@ def resample_along_rays(ori, dir, z_vals, weights, num_samples: int, randomized:
     Returns ``(z_vals (R, N+num_samples) sorted, points)``."""
     ori, dir = _f32(ori, "ori"), _f32(dir, "dir")
     z_vals, weights = _f32(z_vals, "z_vals"), _f32(weights, "weights")
-    R, Nc = z_vals.shape
     rays = _pack_rays(ori, dir, 0.0, 1.0)
+    if z_vals.ndim != 2 or z_vals.shape[0] != rays.shape[0] or tuple(weights.shape) != tuple(z_vals.shape):
+        raise ValueError(f"z_vals and weights must both be (R, Nc) with R = {rays.shape[0]} rays, got {tuple(z_vals.shape)} and "
+                         f"{tuple(weights.shape)}")
+    R, Nc = z_vals.shape
     if randomized and u is None:
         u = torch.rand(R, num_samples, device=z_vals.device)
-    if u is not None:
-        u = _f32(u, "u")
+    u = _jitter(u, R, num_samples)
     z_out = torch.empty(R, Nc + num_samples, dtype=torch.float32, device=z_vals.device)
     pts = torch.empty(R, Nc + num_samples, 3, dtype=torch.float32, device=z_vals.device)
     _lib.check(_lib.load().nsr_resample_along_rays(_p(rays), 8, _p(z_vals), _p(weights), R, Nc, num_samples, _p(u),
@@ -683,10 +731,7 @@ def _arch_render_rays(model: "GenericMLP", rays: torch.Tensor, z_vals: torch.Ten
                          "use the explicit route, model(cat([PositionalEncoding(points), PositionalEncoding(dirs) repeated]))")
     if model._sd is None:
         raise RuntimeError("render_rays called before load_state_dict")
-    rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
-    _ray_stride(rays)
-    if z_vals.ndim != 2 or z_vals.shape[0] != rays.shape[0] or z_vals.shape[1] < 1:
-        raise ValueError(f"z_vals must be (R, N >= 1) with R = {rays.shape[0]} rays, got {tuple(z_vals.shape)}")
+    rays, z_vals = _rays_z(rays, z_vals)
     R, N = z_vals.shape
     raw = torch.empty(R, N, 1 if sigma_only else 4, dtype=torch.float32, device=rays.device)
     model._route.render_rays(rays, z_vals, raw, sigma_only)
@@ -705,7 +750,7 @@ def render_rays(model, rays: torch.Tensor, z_vals: torch.Tensor):
     if isinstance(model, GenericMLP):
         raw = _arch_render_rays(model, rays, z_vals, False)
         return raw[..., :3], raw[..., 3]
-    rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
+    rays, z_vals = _rays_z(rays, z_vals)
     R, N = z_vals.shape
     stride = _ray_stride(rays)
     raw = torch.empty(R, N, 4, dtype=torch.float32, device=rays.device)
@@ -755,7 +800,7 @@ def render_rays_composited(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.
     window once every one of its rays has optical depth >= -ln(eps); outputs move by at most eps + 2e-6 (include/nsr.h).
     Not bit-identical to anything, not combinable with ``want_raw``.  ``want_cut_count`` appends the number of windows not
     run as a 1-element int32 device tensor (0 with the option off)."""
-    rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
+    rays, z_vals = _rays_z(rays, z_vals)
     R, N = z_vals.shape
     dev = rays.device
     eps = check_early_stop(early_stop, model, N, sigma_activation)
@@ -802,7 +847,7 @@ def render_rays_density(model: VanillaMLP, rays: torch.Tensor, z_vals: torch.Ten
     head at every sample, no colour branch, then compositing.  Returns ``(depth (R), opacity (R), weights (R, N))``,
     bit-identical to the same three outputs of ``render_rays_composited`` under either density: what a coarse pass that only
     feeds the resampler needs (the reference's ``sigma_only``, models/networks.py:182-226)."""
-    rays, z_vals = _f32(rays, "rays"), _f32(z_vals, "z_vals")
+    rays, z_vals = _rays_z(rays, z_vals)
     R, N = z_vals.shape
     dev = rays.device
     check_density_coarse(model, N)
@@ -920,7 +965,10 @@ class HipEvents:
 def sr_mean(hr: torch.Tensor, n_lr: int, s2: int) -> torch.Tensor:
     """``reshape(N_lr, s^2, c).mean(1)`` (models/nerf_downX_model.py:337-348)."""
     hr = _f32(hr, "hr")
-    c = hr.numel() // (n_lr * s2)
+    n_lr, s2 = int(n_lr), int(s2)
+    if hr.ndim not in (1, 2) or n_lr < 0 or s2 < 1 or hr.shape[0] != n_lr * s2:
+        raise ValueError(f"hr must be (n_lr * s2, c) or (n_lr * s2,) with n_lr * s2 = {n_lr * s2}, got {tuple(hr.shape)}")
+    c = int(hr.shape[1]) if hr.ndim == 2 else 1
     lr = torch.empty(n_lr, c, dtype=torch.float32, device=hr.device)
     _lib.check(_lib.load().nsr_sr_mean(_p(hr), n_lr, s2, c, _p(lr), _stream()), "nsr_sr_mean")
     return lr
@@ -930,7 +978,9 @@ def unflatten_reshape(x: torch.Tensor, img_wh: Tuple[int, int], downscale: int) 
     """(N_lr*s^2, c) -> HR image (H, W, c) (models/nerf_downX_model.py:410-416)."""
     x = _f32(x, "x")
     W, H = int(img_wh[0]), int(img_wh[1])
-    c = x.numel() // (H * W)
+    if x.ndim not in (1, 2) or x.shape[0] != H * W:
+        raise ValueError(f"x must be (H * W, c) or (H * W,) with H * W = {H * W}, got {tuple(x.shape)}")
+    c = int(x.shape[1]) if x.ndim == 2 else 1
     out = torch.empty(H, W, c, dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().nsr_unflatten(_p(x), H, W, int(downscale), c, _p(out), _stream()), "nsr_unflatten")
     return out

@@ -54,6 +54,10 @@ def render_warp_refine(model: NeRFDownXModel, net: refine.MaxPoolingModel, c2w, 
     def mark(i):
         if events is not None:
             events[i].record()
+    W, H = int(model.opt.img_wh[0]), int(model.opt.img_wh[1])
+    ref_img = ops._f32(ref_img, "ref_img")          # looked at before anything is enqueued
+    if tuple(ref_img.shape) != (3, H, W):
+        raise ValueError(f"ref_img must be (3, H, W) = (3, {H}, {W}), the HR frame of the model, got {tuple(ref_img.shape)}")
     mark(0)
     res = model.render_image(c2w, focal, ndc, near, far, coarse_rgb=coarse_rgb)
     depth_hw = model.unflatten_reshape(model.out_fine_depth_ori.reshape(-1, 1))[..., 0].contiguous()   # {i}-fine-depth-ori
@@ -66,7 +70,7 @@ def render_warp_refine(model: NeRFDownXModel, net: refine.MaxPoolingModel, c2w, 
     mark(2)
     # the refine dataset normalises images to [-1, 1] (T.Normalize(0.5, 0.5), data/llff_refine_dataset.py:252-255)
     sr = (res["hr_rgb"].permute(2, 0, 1) * 2.0 - 1.0).contiguous()
-    refined = refine.refine_image(net, sr, (ops._f32(ref_img, "ref_img") * 2.0 - 1.0).contiguous(), locs, patch_len,
+    refined = refine.refine_image(net, sr, (ref_img * 2.0 - 1.0).contiguous(), locs, patch_len,
                                   num_ref_patches, batch)
     mark(3)
     return {"hr_rgb": res["hr_rgb"], "depth": depth_hw, "locs": locs, "refined": (refined + 1.0) * 0.5,

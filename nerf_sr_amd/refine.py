@@ -22,7 +22,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .ops import _f32, _p, _stream
+from .ops import _check_device, _f32, _i32, _p, _stream
 
 # (name, cin, cout, stride, batch-norm name or None) in forward = state_dict order
 LAYERS = [
@@ -191,7 +191,8 @@ def tile_refs(locs: torch.Tensor, patch_len: int = 64, num_ref_patches: int = 8)
     the SR tile), as ``LLFFRefineDataset.__getitem__`` picks them (data/llff_refine_dataset.py:303-329)."""
     if not locs.is_cuda or locs.dtype != torch.float64 or locs.ndim != 3 or locs.shape[2] != 3:
         raise ValueError("locs must be a (H, W, 3) float64 tensor on the GPU")
-    locs = locs.contiguous()
+    _check_device(locs.device, "locs")
+    locs = locs.detach().contiguous()
     H, W = locs.shape[:2]
     n = -(-W // patch_len) * -(-H // patch_len)
     starts = torch.empty(n, 2, dtype=torch.int32, device=locs.device)
@@ -202,23 +203,36 @@ def tile_refs(locs: torch.Tensor, patch_len: int = 64, num_ref_patches: int = 8)
 
 
 def gather_patches(sr_img: torch.Tensor, ref_img: torch.Tensor, starts: torch.Tensor, ref_starts: torch.Tensor, patch_len: int = 64):
-    """sr_img, ref_img (3, H, W) -> sr_patch (n, 3, p, p), ref_patches (n, R, 3, p, p) (the dataset's sample)."""
+    """sr_img, ref_img (3, H, W) fp32 -> sr_patch (n, 3, p, p), ref_patches (n, R, 3, p, p) (the dataset's sample).
+    ``starts`` (n, 2) / ``ref_starts`` (n, R, 2): integer tensors on the device, converted to the int32 the kernel reads
+    (``tile_refs`` returns int32; ``torch.tensor([[0, 0]])`` is int64); a floating-point index raises ``TypeError``."""
     sr_img, ref_img = _f32(sr_img, "sr_img"), _f32(ref_img, "ref_img")
+    starts, ref_starts = _i32(starts, "starts"), _i32(ref_starts, "ref_starts")
+    if sr_img.ndim != 3 or sr_img.shape[0] != 3 or tuple(ref_img.shape) != tuple(sr_img.shape):
+        raise ValueError(f"sr_img and ref_img must both be (3, H, W), got {tuple(sr_img.shape)} and {tuple(ref_img.shape)}")
+    if starts.ndim != 2 or starts.shape[1] != 2 or ref_starts.ndim != 3 or ref_starts.shape[0] != starts.shape[0] \
+            or ref_starts.shape[1] < 1 or ref_starts.shape[2] != 2:
+        raise ValueError(f"starts must be (n, 2) and ref_starts (n, R >= 1, 2), got {tuple(starts.shape)} and {tuple(ref_starts.shape)}")
     _, H, W = sr_img.shape
     n, R = ref_starts.shape[:2]
     sr = torch.empty(n, 3, patch_len, patch_len, dtype=torch.float32, device=sr_img.device)
     ref = torch.empty(n, R, 3, patch_len, patch_len, dtype=torch.float32, device=sr_img.device)
-    _lib.check(_lib.load().nsr_refine_gather(_p(sr_img), _p(ref_img), H, W, patch_len, R, _p(starts.contiguous()),
-                                             _p(ref_starts.contiguous()), n, _p(sr), _p(ref), _stream()), "nsr_refine_gather")
+    _lib.check(_lib.load().nsr_refine_gather(_p(sr_img), _p(ref_img), H, W, patch_len, R, _p(starts),
+                                             _p(ref_starts), n, _p(sr), _p(ref), _stream()), "nsr_refine_gather")
     return sr, ref
 
 
 def stitch_patches(patches: torch.Tensor, starts: torch.Tensor, img_wh) -> torch.Tensor:
-    """Paste predictions back in tile order, later tiles overwrite earlier ones (models/refine_model.py:211-214)."""
-    patches = _f32(patches, "patches")
+    """Paste predictions (n, 3, p, p) fp32 back in tile order, later tiles overwrite earlier ones (models/refine_model.py:211-214).
+    ``starts`` (n, 2): an integer tensor on the device, converted to int32 like ``gather_patches``' (``TypeError`` otherwise)."""
+    patches, starts = _f32(patches, "patches"), _i32(starts, "starts")
+    if patches.ndim != 4 or patches.shape[1] != 3 or patches.shape[2] != patches.shape[3]:
+        raise ValueError(f"patches must be (n, 3, p, p), got {tuple(patches.shape)}")
+    if tuple(starts.shape) != (patches.shape[0], 2):
+        raise ValueError(f"starts must be (n, 2) with n = {patches.shape[0]} patches, got {tuple(starts.shape)}")
     W, H = int(img_wh[0]), int(img_wh[1])
     img = torch.empty(3, H, W, dtype=torch.float32, device=patches.device)
-    _lib.check(_lib.load().nsr_refine_stitch(_p(patches), _p(starts.contiguous()), patches.shape[0], patches.shape[-1], H, W,
+    _lib.check(_lib.load().nsr_refine_stitch(_p(patches), _p(starts), patches.shape[0], patches.shape[-1], H, W,
                                              _p(img), _stream()), "nsr_refine_stitch")
     return img
 
@@ -229,6 +243,11 @@ def refine_image(net: MaxPoolingModel, sr_img: torch.Tensor, ref_img: torch.Tens
     Images are (3, H, W) in [-1, 1] (the dataset's Normalize(0.5, 0.5)); returns the refined (3, H, W) image.
     ``batch``: tiles per network call.  The default takes the 169 tiles of an 800 x 800 frame in ONE call (3.5 GB of
     activations): the 8 x 8-pixel decoder layers of a 32-tile batch fill an eighth of the chip (57 vs 45 ms per frame)."""
+    sr_img, ref_img = _f32(sr_img, "sr_img"), _f32(ref_img, "ref_img")
+    if sr_img.ndim != 3 or sr_img.shape[0] != 3 or tuple(ref_img.shape) != tuple(sr_img.shape):
+        raise ValueError(f"sr_img and ref_img must both be (3, H, W), got {tuple(sr_img.shape)} and {tuple(ref_img.shape)}")
+    if not isinstance(locs, torch.Tensor) or tuple(locs.shape) != (sr_img.shape[1], sr_img.shape[2], 3):
+        raise ValueError(f"locs must be (H, W, 3) for images of {sr_img.shape[1]} x {sr_img.shape[2]}, got {tuple(getattr(locs, 'shape', ()))}")
     starts, refs = tile_refs(locs, patch_len, num_ref_patches)
     sr, ref = gather_patches(sr_img, ref_img, starts, refs, patch_len)
     pred = torch.cat([net(sr[i:i + batch], ref[i:i + batch]) for i in range(0, sr.shape[0], batch)], 0)
@@ -248,9 +267,10 @@ def evaluate_image(net: MaxPoolingModel, sr_img: torch.Tensor, ref_img: torch.Te
     refined = refine_image(net, sr_img, ref_img, locs, patch_len, num_ref_patches, batch)
     sr = _f32(sr_img, "sr_img")
     ssim, psnr = metrics.SSIM(data_range=(-1, 1)), metrics.PSNR()
-    return {"refined": refined,
-            "psnr_input": psnr(sr, gt), "psnr_refine": psnr(refined, gt),
-            "ssim_input": ssim(sr.unsqueeze(0), gt.unsqueeze(0)), "ssim_refine": ssim(refined.unsqueeze(0), gt.unsqueeze(0))}
+    with torch.no_grad():       # scores, not losses: an image that requires grad does not make them differentiable
+        return {"refined": refined,
+                "psnr_input": psnr(sr, gt), "psnr_refine": psnr(refined, gt),
+                "ssim_input": ssim(sr.unsqueeze(0), gt.unsqueeze(0)), "ssim_refine": ssim(refined.unsqueeze(0), gt.unsqueeze(0))}
 
 
 # ------------------------------------------------------------------------------------------------------- training
@@ -371,8 +391,9 @@ def forward_train(params, running, x_synth: torch.Tensor, list_x_candi: torch.Te
     ps, rs = [params[k] for k in TRAIN_PARAM_KEYS], [running[k] for k in RUNNING_KEYS]
     for k, t in list(zip(TRAIN_PARAM_KEYS, ps)) + list(zip(RUNNING_KEYS, rs)):
         if not isinstance(t, torch.Tensor) or t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous() \
-                or tuple(t.shape) != tuple(REFINE_SPEC[k]):
-            raise ValueError(f"forward_train: {k} must be a contiguous float32 tensor of shape {REFINE_SPEC[k]} on {x.device}")
+                or tuple(t.shape) != tuple(REFINE_SPEC[k]) or t.data_ptr() % 16:
+            # 16-byte aligned: the BatchNorm kernels read the per-channel vectors four floats at a time
+            raise ValueError(f"forward_train: {k} must be a contiguous, 16-byte aligned float32 tensor of shape {REFINE_SPEC[k]} on {x.device}")
     run = _TrainRun(rs, float(momentum), 0 if img_chunk is None else int(img_chunk), prec, wgrad)
     return _ForwardTrain.apply(run, x, c, *ps)
 
@@ -427,8 +448,17 @@ class RefineTrainer:
         self._ssim = None
 
     def set_input(self, input):
-        for name in ("sr_patch", "ref_patches", "gt_patch"):
-            setattr(self, f"data_{name}", input[name].to(device=self.device, dtype=torch.float32).contiguous())
+        """``sr_patch`` / ``gt_patch`` (B, 3, H, W) and ``ref_patches`` (B, R, 3, H, W), on the host or the device, of any floating
+        dtype: copied to the trainer's device as dense fp32 (the reference's ``set_input`` moves its batches the same way); the
+        inputs are never written.  Shapes that do not fit each other raise ``ValueError`` here, before anything runs."""
+        data = {name: input[name].to(device=self.device, dtype=torch.float32).contiguous() for name in ("sr_patch", "ref_patches", "gt_patch")}
+        sr, ref, gt = data["sr_patch"], data["ref_patches"], data["gt_patch"]
+        if sr.ndim != 4 or sr.shape[1] != 3 or ref.ndim != 5 or ref.shape[0] != sr.shape[0] or tuple(ref.shape[2:]) != tuple(sr.shape[1:]) \
+                or tuple(gt.shape) != tuple(sr.shape):
+            raise ValueError(f"expected sr_patch and gt_patch (B, 3, H, W) and ref_patches (B, R, 3, H, W), got {tuple(sr.shape)}, "
+                             f"{tuple(gt.shape)} and {tuple(ref.shape)}")
+        for name, v in data.items():
+            setattr(self, f"data_{name}", v)
 
     def forward(self):
         self.pred = forward_train(self.params, self.running, self.data_sr_patch, self.data_ref_patches, self.momentum, self.img_chunk,

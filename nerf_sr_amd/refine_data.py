@@ -70,7 +70,10 @@ class RefinePatchSet:
     """8-bit ground-truth / synthesised images + perspective table on the device; patch batches from them.
 
     gt_u8, sr_u8     (H, W, 3) or (n, H, W, 3) uint8, numpy or torch.  split 'train': the pair of view ``ref_idx`` is used;
-                     split 'val': all n views, the reference image is ``gt_u8[ref_idx]``
+                     split 'val': all n views, the reference image is ``gt_u8[ref_idx]``.  Host images and views are copied to
+                     the device as dense tensors; a dense uint8 tensor that is already on the device is KEPT, not copied (the
+                     set reads it in place and never writes it: do not change it while the set lives).  Another dtype raises
+                     ``TypeError``
     patch_len, num_ref_patches, ref_offset, with_gt_patch, aug_num, distort_scale   the reference's options of the same names
     generator        host ``torch.Generator`` the perspectives are drawn with (``perspective_params``)
     coeffs           (aug_num, 8) coefficients instead of drawn ones (row 0 the identity, by the reference's convention)
@@ -160,7 +163,9 @@ class RefinePatchSet:
         if t.dtype.is_floating_point or t.dtype == torch.bool:
             raise TypeError(f"{name} must be integers")
         _check_device(t.device, name)
-        t = t.to(torch.int32).reshape(shape).contiguous()
+        if len(shape) == 2 and t.numel() % shape[1]:
+            raise ValueError(f"{name} must hold rows of {shape[1]} words, got {tuple(t.shape)}")
+        t = t.detach().to(torch.int32).reshape(shape).contiguous()
         return t
 
     def _launch(self, aug_idx, starts=None, draws=None) -> Dict[str, torch.Tensor]:

@@ -55,11 +55,19 @@ def linear(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None, a
     """One ``nn.Linear`` (+ activation) on the training GEMM (``nsr_linear``): y = act(x w^T + b).
     K must be a multiple of 32; returns y (P, N) and, if asked, also y^T (N, P)."""
     x, w = _f32(x, "x"), _f32(w, "w")
+    if x.ndim != 2 or w.ndim != 2 or w.shape[1] != x.shape[1] or x.shape[1] % 32:
+        raise ValueError(f"x must be (P, K) and w (N, K) with K a multiple of 32, got {tuple(x.shape)} and {tuple(w.shape)}")
     P, K = x.shape
     N = w.shape[0]
+    if transposed and P % 4:
+        raise ValueError(f"transposed=True needs a multiple of 4 rows (the leading dimension of y^T), got P = {P}")
+    if b is not None:
+        b = _f32(b, "b")
+        if tuple(b.shape) != (N,):
+            raise ValueError(f"b must be (N,) = ({N},), got {tuple(b.shape)}")
     y = torch.empty(P, N, dtype=torch.float32, device=x.device)
     yt = torch.empty(N, P, dtype=torch.float32, device=x.device) if transposed else None
-    _lib.check(_lib.load().nsr_linear(_p(x), K, _p(w), K, _p(None if b is None else _f32(b, "b")), act, _p(y), N,
+    _lib.check(_lib.load().nsr_linear(_p(x), K, _p(w), K, _p(b), act, _p(y), N,
                                       _p(yt), P, P, K, N, _stream()), "nsr_linear")
     return (y, yt) if transposed else y
 
@@ -183,6 +191,24 @@ def train_flags(white_bkgd: bool = False, gamma_correct: bool = False, sigma_act
         raise ValueError("gamma_correct with color_activation='none': pow(rgb, 1 / 2.2) of an unbounded head is NaN for every negative value")
     return renderer_flags(white_bkgd, sigma_activation) | (_lib.NSR_TRAIN_GAMMA_CORRECT if gamma_correct else 0) \
         | (_lib.NSR_TRAIN_COLOR_NONE if color_activation == "none" else 0) | (_lib.NSR_TRAIN_STOP_GRAD if stop_grad else 0)
+
+
+DRAW_KEYS = ("u_coarse", "u_fine", "noise_coarse", "noise_fine")
+
+
+def _draws(draws, R: int, nc: int, ni: int, device) -> Dict[str, Optional[torch.Tensor]]:
+    """The four random tensors of one train-mode forward as dense fp32 device tensors of the shapes the kernels read --
+    ``u_coarse`` / ``noise_coarse`` (R, Nc), ``u_fine`` (R, Ni), ``noise_fine`` (R, Nc + Ni) -- or None; ValueError otherwise."""
+    shapes = {"u_coarse": (R, nc), "u_fine": (R, ni), "noise_coarse": (R, nc), "noise_fine": (R, nc + ni)}
+    out = {}
+    for k in DRAW_KEYS:
+        v = (draws or {}).get(k)
+        if v is not None:
+            v = _f32(torch.as_tensor(v, device=device), k)
+            if tuple(v.shape) != shapes[k]:
+                raise ValueError(f"draws[{k!r}] must be {shapes[k]} for {R} rays and {nc} + {ni} samples, got {tuple(v.shape)}")
+        out[k] = v
+    return out
 
 
 def _rays_per_pass(ray_chunk: int, R: int) -> int:
@@ -313,8 +339,8 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     parameter lists, or state-dict-like dicts such as ``Trainer.params``).  Returns the eight ``OUT_KEYS`` outputs; any loss
     written in torch over them back-propagates through ``nsr_train_backward`` (once: the backward is not differentiable).
 
-    ``draws``: ``u_coarse`` (R, Nc), ``u_fine`` (R, Ni), ``noise_coarse`` (R, Nc), ``noise_fine`` (R, Nc + Ni) on the device,
-    or None for the deterministic branch of that stage (``Trainer.draw`` makes them in the reference's order).  ``ray_chunk``:
+    ``draws``: ``u_coarse`` (R, Nc), ``u_fine`` (R, Ni), ``noise_coarse`` (R, Nc), ``noise_fine`` (R, Nc + Ni) fp32 on the device
+    (a host tensor or array is copied there; another shape is a ``ValueError``), or None for the deterministic branch of that stage (``Trainer.draw`` makes them in the reference's order).  ``ray_chunk``:
     rays per pass (0 = all).  Every call keeps its own saved state (5.4 KB per sample point under 'f16x3', include/nsr_train.h)
     until its backward; ``workspace`` (shared scratch + the sticky status block) defaults to one per device.
 
@@ -375,9 +401,7 @@ def forward_rays_train(params_c, params_f, rays: torch.Tensor, draws: Optional[D
     for t in wc + wf:
         if t.device != rays.device:
             raise ValueError("the weights must live on the rays' device")
-    draws = draws or {}
-    d = [None if draws.get(k) is None else _f32(torch.as_tensor(draws[k], device=rays.device), k)
-         for k in ("u_coarse", "u_fine", "noise_coarse", "noise_fine")]
+    d = list(_draws(draws, rays.shape[0], int(N_coarse), int(N_importance), rays.device).values())
     if workspace is None:
         workspace = _DEFAULT_WS.setdefault(rays.device, TrainWorkspace())
     run = _TrainRun(int(N_coarse), int(N_importance), flags, int(bool(lindisp)), float(noise_std),
@@ -512,6 +536,8 @@ class Trainer:
     def set_input(self, rays: torch.Tensor, rgbs: torch.Tensor):
         """rays (N_lr, s2, 8 | 11) or (N_lr * s2, 8 | 11); rgbs (N_lr, 3) LR targets (set_input, :235-248)."""
         rays = _f32(rays.reshape(-1, rays.shape[-1]), "rays")
+        if rgbs.ndim < 1 or rgbs.shape[-1] != 3:
+            raise ValueError(f"rgbs must be (N_lr, 3), got {tuple(rgbs.shape)}")
         self.data_rays, self.data_rgbs = rays, _f32(rgbs.reshape(-1, 3), "rgbs")
         if rays.shape[0] != self.data_rgbs.shape[0] * self.s2:
             raise ValueError("rays must hold s^2 sub-rays per LR target pixel")
@@ -540,8 +566,7 @@ class Trainer:
         R, stride = rays.shape[0], _ray_stride(rays)
         if draws is None:
             draws = self.draw(R)
-        draws = {k: (None if v is None else _f32(torch.as_tensor(v, device=self.device), k)) for k, v in draws.items()
-                 if k != "noise_std"}
+        draws = _draws(draws, R, self.N_coarse, self.N_importance, self.device)
         nc, chunk = self.N_coarse, self._chunk(R)
         lib = _lib.load()
         need = lib.nsr_train_workspace_bytes_for(self._prec, chunk, nc, self.N_importance)   # the buffers of the path this precision takes
@@ -694,6 +719,9 @@ class Trainer:
         device tensor [tv_coarse, tv_fine] (before the lambda).  ``fused_tv``: the two losses and their gradients through
         ``losses.TVLoss`` (two launches forward, one backward, double arithmetic) instead of the chain of torch ops."""
         side = int(patch_len) * int(round(self.s2 ** 0.5))
+        if not isinstance(patch_rays, torch.Tensor) or patch_rays.ndim < 2 or patch_rays.numel() != side * side * patch_rays.shape[-1]:
+            raise ValueError(f"patch_rays must hold the {side} x {side} rays of the HR patch in raster order, got "
+                             f"{tuple(getattr(patch_rays, 'shape', ()))}")
         out = self.forward(draws, rays=patch_rays)
         tv = tv_loss
         if fused_tv:
